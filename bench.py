@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """bench.py - sampled trajectory-steps/sec of the GP-posterior-sample rollout on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: set-up, the warm-up (W steps, the `--prewarm` clock ramp, W steps),
+EXACTLY K timed steps, the outputs of the last timed step if `--dump-outputs DIR` is given, and ONE JSON line on stdout
+(the contract keys: `metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype`, ...).  Everything else described
+below - the cold region, the roofline's event-pair pass, the standalone gather, the CPU baseline, the reachable-set,
+end-to-end and extra legs, the stderr extras line and bench_extra.json - runs only with `--full`.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/X_traj.npy (float64): the trajectories
+(Ns, nx, H+1) at N = 1, the assembled tube (N*Ns, nx, H+1) for N > 1 (rank 0 writes it).  Above 64 MB every k-th sample is
+kept (fixed stride, `X_traj_stride` in the line).  The inputs are seeded (counter-based base samples, synthetic data), so
+two runs with the same arguments - or two builds of the project - can be compared output for output.
 
 Both forms work for N > 1: started WITHOUT a launcher (WORLD_SIZE unset), this process - before it has touched HIP -
 starts the N ranks as fresh child processes through torch.distributed.run (one per GPU), forwards rank 0's JSON line and
@@ -88,6 +99,10 @@ def parse():
     ap.add_argument("--gather-every", type=int, default=4,
                     help="N > 1: rollouts per all-gather (one collective assembles the tubes of this many consecutive rollouts; "
                          "a collective costs the host ~30 us to enqueue whatever its size)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cold region, roofline, gather, CPU baseline and every informational leg (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's trajectories as DIR/X_traj.npy (float64, at most 64 MB)")
     return ap.parse_args()
 
 
@@ -675,6 +690,30 @@ def emit(out):
     sys.stdout.flush()
 
 
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(d, X):
+    """--dump-outputs: X (N*Ns, nx, H+1) float64 -> d/X_traj.npy, every k-th sample when the whole would exceed
+    DUMP_MAX_BYTES (k = 1 at the default sizes: 0.5 MB per GPU).  Returns k."""
+    X = X.detach().cpu().numpy()
+    max_rows = (DUMP_MAX_BYTES - 4096) // (X[0].nbytes)          # (4096: room for the .npy header)
+    stride = -(-X.shape[0] // max_rows)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "X_traj.npy"), np.ascontiguousarray(X[::stride], dtype=np.float64))
+    return stride
+
+
+def flush_c_stdio():
+    """The contract line is the LAST thing on stdout: once the process group is gone, whatever the C side (RCCL's version
+    banner) still holds in its stdio buffer is flushed in front of it."""
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except OSError:
+        pass
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -759,15 +798,57 @@ def main():
             wall = float(t.item())
         return wall
 
-    # cold: what a fresh process sees (W warmup steps, then K timed steps, clocks not yet ramped)
+    # cold (--full): what a fresh process sees (W warmup steps, then K timed steps, clocks not yet ramped)
     run_steps(a.warmup)
-    wall_cold = timed(a.steps)
+    wall_cold = timed(a.steps) if a.full else None
     # clock ramp: the same step, a fixed count on every rank (it contains the collective), untimed and reported
     run_steps(max(a.prewarm, 0))
     fence()
     run_steps(a.warmup)
     # timed region: EXACTLY a.steps steps between two fences
     wall = timed(a.steps)
+    X_last = runner.X_traj if pipe is None else pipe.buffer(a.steps - 1)
+    dump_stride = None
+    if a.dump_outputs and rank == 0:                            # what a caller of the timed path receives: the tube for N > 1
+        dump_stride = dump_outputs(a.dump_outputs, X_last if pipe is None else
+                                   pipe.tube(a.steps - 1).reshape(pipe.world * Ns, agent.nx, H + 1))
+    bits = int(runner.info.max().item())
+    assert torch.isfinite(X_last).all() and not (bits & (_lib.INFO_TRAIN_CHOL_FAIL | _lib.INFO_ROOT_FAIL)), bits
+    if rank == 0:
+        name, cus, _ = _lib.device_info(local_rank)
+        units = world * Ns * H                                  # sampled trajectory-steps per step
+        out = {
+            "metric": "sampled trajectory-steps/sec (Ns*H per wall second)",
+            "value": units * a.steps / wall,
+            "unit": "trajectory-steps/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "prewarm_steps": max(a.prewarm, 0),     # untimed clock-ramp steps between the cold and the reported region
+            "ms_per_step": wall / a.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: params_pendulum1D_samples, sequential re-conditioned rollout "
+                                   "(mode R, value+gradient labels T=3), Ns=%d per GPU, H=%d" % (Ns, H),
+                       "Ns_per_gpu": Ns, "H": H, "Ns_total": world * Ns,
+                       "parallelism": "samples sharded over %d GPU(s); base samples generated per shard; RCCL all-gather of "
+                                      "X_traj per rollout on a side stream, overlapping the next rollout" % world,
+                       "device": name, "cus": cus},
+        }
+        if dump_stride is not None:
+            out["X_traj_stride"] = dump_stride
+    if not a.full:
+        if multi:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            flush_c_stdio()
+            sys.stdout.write(json.dumps(out) + "\n")
+            sys.stdout.flush()
+        return
     # the rollout kernel's launch duration, one HIP event pair per launch (what rocprofv3 --kernel-trace reports per
     # dispatch): a second, untimed pass of the same launches, so that the instrumentation stays out of the timed region
     kern_ms_pairs, _ = time_launches(runner.launch, a.steps)
@@ -786,9 +867,6 @@ def main():
                   "every": pipe.every, "bytes_per_rank": Ns * agent.nx * (H + 1) * 8, "bytes_per_collective_per_rank": src.numel() * 8,
                   "standalone_ms": g_ms, "standalone_ms_per_step": g_ms / pipe.every,
                   "exposed_ms_per_step": max(wall / a.steps * 1e3 - kern_ms, 0.0), "overlapped_with_next_rollout": True}
-    X_last = runner.X_traj if pipe is None else pipe.buffer(a.steps - 1)
-    bits = int(runner.info.max().item())
-    assert torch.isfinite(X_last).all() and not (bits & (_lib.INFO_TRAIN_CHOL_FAIL | _lib.INFO_ROOT_FAIL)), bits
 
     reach = reachable_set_leg(a, rank, world if not (force_dist and world == 1) else 1, dist if world > 1 else None, sg, _lib,
                               RolloutRunner, wl)
@@ -806,35 +884,14 @@ def main():
             sharded_cl = {"workload": "sharded_closed_loop_leg", "error": "another rank failed"}
 
     if rank == 0:
-        name, cus, _ = _lib.device_info(local_rank)
-        units = world * Ns * H                                  # sampled trajectory-steps per step
         prof, tf = {}, os.path.join(REPO, "profiles", "latest_traffic.json")
         if os.path.exists(tf) and Ns == 1024 and H == 30:     # PMC counters cannot be read in-process: last profiled run
             prof = json.load(open(tf))
         traffic = prof.get("hbm_bytes_per_launch_gfx950_corrected")
         flop = wl.flop_mode_r(1, 3, 36, 36, H) * Ns * H         # per launch (one GPU): 2.55e4 per trajectory-step at H = 30
-        out = {
-            "metric": "sampled trajectory-steps/sec (Ns*H per wall second)",
-            "value": units * a.steps / wall,
-            "unit": "trajectory-steps/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "prewarm_steps": max(a.prewarm, 0),     # untimed clock-ramp steps between the cold and the reported region
-            "ms_per_step": wall / a.steps * 1e3,
+        out.update({
             "cold": {"ms_per_step": wall_cold / a.steps * 1e3, "value": units * a.steps / wall_cold,
                      "note": "the same K steps right after the W warmup steps of a fresh process, before the clock ramp"},
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: params_pendulum1D_samples, sequential re-conditioned rollout "
-                                   "(mode R, value+gradient labels T=3), Ns=%d per GPU, H=%d" % (Ns, H),
-                       "Ns_per_gpu": Ns, "H": H, "Ns_total": world * Ns,
-                       "parallelism": "samples sharded over %d GPU(s); base samples generated per shard; RCCL all-gather of "
-                                      "X_traj per rollout on a side stream, overlapping the next rollout" % world,
-                       "device": name, "cus": cus},
             "roofline": roofline(
                 flop, kern_ms, {4: "rollout_one_kernel<4,pendulum1D> (one chain per wave, the factor in AGPR-pinned MFMA panels)",
                                 3: "rollout_tiles_kernel<4,9,pendulum1D,32>"}.get(
@@ -859,7 +916,7 @@ def main():
                 mfma_busy=prof.get("mfma_busy_frac", 0.0 if head_path == 1 else None),
                 kernel_ms_per_launch_event_pairs=kern_ms_pairs),
             "gather": gather,
-        }
+        })
         if world == 1 and a.cpu_sample > 0:
             v, dt, th, probe = cpu_baseline(a.cpu_sample, H, u_ff, a.cpu_repeats)
             out["cpu_baseline"] = {"value": v, "unit": "trajectory-steps/s", "cores": th, "kind": "port",
@@ -892,13 +949,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the contract line is the LAST thing on stdout: the process group is gone, and whatever the C side (RCCL's version banner)
-        # still holds in its stdio buffer is flushed in front of it
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except OSError:
-            pass
+        flush_c_stdio()
         emit(out)
 
 

@@ -1,12 +1,13 @@
-"""GPU: bench.py prints ONE short JSON line on stdout (the driver's contract keys, the roofline and cpu_baseline objects, the
-compact `legs` table; < 4096 characters, the last stdout line) and the full objects of every leg as one JSON line on stderr; with
-GPMPC_BENCH_FORCE_DIST=1 the N > 1 code path (process group, per-shard base samples, pipelined all-gather) runs with a
-world of one rank."""
+"""GPU: bench.py --full prints ONE short JSON line on stdout (the driver's contract keys, the roofline and cpu_baseline objects,
+the compact `legs` table; < 4096 characters, the last stdout line) and the full objects of every leg as one JSON line on stderr;
+with GPMPC_BENCH_FORCE_DIST=1 the N > 1 code path (process group, per-shard base samples, pipelined all-gather) runs with a
+world of one rank.  A plain run prints the contract keys alone and can dump the outputs of its last timed step."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from tests.helpers import REPO
@@ -17,7 +18,7 @@ pytestmark = pytest.mark.gpu
 def _run(extra_env=None, args=()):
     env = dict(os.environ)
     env.update(extra_env or {})
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--prewarm", "20",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--prewarm", "20",
                           "--cpu-sample", "16", "--reach-ns", "512", *args], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     all_lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -81,3 +82,28 @@ def test_bench_sharded_closed_loop_leg_with_one_rank():
     assert all(i["finite"] and i["draw_ms"] > 0 and i["gather_ms"] > 0 and i["wall_ms_per_iteration"] >= i["draw_ms"] for i in its)
     assert its[0]["n_o"] == 45 and its[3]["n_o"] == 45 + 3 * 120 and its[4]["n_o"] == 45 + 4 * 120    # the reset-after-build quirk
     assert its[0]["gathered_bytes"] == 32 * 4 * 40 * 7 * 8
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: one JSON line with the contract keys and nothing else measured (no extras line on stderr), `steps` =
+    --steps, `value` = Ns*H per `ms_per_step`; --dump-outputs writes the last timed step's trajectories, the same in two runs
+    (seeded inputs)."""
+    dumps = []
+    for k in range(2):
+        dst = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "7", "--warmup", "2", "--prewarm", "20",
+                              "--dump-outputs", str(dst)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        all_lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        lines = [ln for ln in all_lines if ln.startswith("{")]
+        assert len(lines) == 1 and all_lines[-1] == lines[0], out.stdout[-2000:]
+        assert '{"bench_extra"' not in out.stderr
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["n_gpus"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+        assert d["unit"] == "trajectory-steps/s" and d["metric"].startswith("sampled trajectory-steps/sec")
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / (1024 * 30) - 1.0) < 1e-9
+        assert not set(d) & {"roofline", "cpu_baseline", "cold", "gather", "legs", "extra", "reachable_set"}
+        X = np.load(dst / "X_traj.npy")
+        assert X.dtype == np.float64 and X.shape == (1024, 2, 31) and np.isfinite(X).all() and d["X_traj_stride"] == 1
+        dumps.append(X)
+    np.testing.assert_allclose(dumps[1], dumps[0], rtol=1e-12, atol=0)

@@ -63,7 +63,7 @@ def test_bench_self_launch_path_on_a_gpu_box():
     world of one rank), prints the line, and its exit status propagates."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update({"GPMPC_BENCH_SELF_LAUNCH": "1", "GPMPC_BENCH_FORCE_DIST": "1"})
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--no-extra", "--cpu-sample", "0",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--no-extra", "--cpu-sample", "0",
                           "--prewarm", "20", "--reach-ns", "512"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _launcher_record(out.stderr)

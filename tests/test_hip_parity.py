@@ -902,11 +902,16 @@ def test_derivative_observing_real_data(sg, pname):
     np.testing.assert_allclose(agent.model_i_call.mean.cpu().numpy(), oagent.model_i_call.mean.numpy(), rtol=1e-6, atol=1e-9)
     np.testing.assert_allclose(agent.model_i_call.variance.cpu().numpy(), oagent.model_i_call.variance.numpy(),
                                rtol=1e-3, atol=1e-13)
-    lvl = ((agent.model_i_call.last_info.cpu().numpy() >> 1) & 7).max(axis=1)
-    ojit = oagent.model_i_call.root_info.jitter_added.numpy().max(axis=1)
-    same = (lvl > 0) == (ojit > 0)
+    lvl = (agent.model_i_call.last_info.cpu().numpy() >> 1) & 7                     # (Ns, g_ny): per GP task
+    ojit = oagent.model_i_call.root_info.jitter_added.numpy()
+    same_task = (lvl > 0) == (ojit > 0)
+    assert same_task.any()
     # with gradient labels on the grid the posterior is nearly degenerate (variances at the jitter level), so the
-    # samples carry O(sqrt(jitter)) branch/round-off noise; mean, variance above are the sharp checks
+    # samples carry O(sqrt(jitter)) branch/round-off noise; mean, variance above are the sharp checks.  Whether a task's
+    # Cholesky needs the jitter is decided by round-off, and it comes out differently with the host's BLAS: a state row
+    # (f + B_d g) is compared where every task it takes from B_d took the same branch on both sides
+    uses = oagent.env_model.B_d.numpy() != 0                                         # (nx, g_ny)
+    same = (same_task[:, None, :] | ~uses[None]).all(axis=2)                         # (Ns, nx)
     print(f"{pname}: derivative data, max |gp_val - oracle| = {np.abs(gp_val[same] - ogp_val[same]).max():.2e}")
     np.testing.assert_allclose(gp_val[same], ogp_val[same], rtol=1e-5, atol=2e-4)
     # rollout with the same data (forward-sampling layout)

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the kernel trace is of bench.py's default command (its CPU leg skipped); the PMC passes replay a shorter run of the
 # headline workload only
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $ROOT/bench.py --cpu-sample 0 > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $ROOT/bench.py --full --cpu-sample 0 > $OUT/trace.log 2>&1
 ARGS="$ROOT/bench.py --steps 20 --warmup 3 --cpu-sample 0 --no-extra --reach-ns 0 --prewarm 200"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python3 $ARGS > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o pmc -- python3 $ARGS > $OUT/pmc_write.log 2>&1
