@@ -316,7 +316,7 @@ int    gpmpc_joint_pending_written(void);    /* 1: the last gpmpc_joint_sample[_
  * The two paths of gpmpc_joint_sample (ABI 7).  GPMPC_JOINT_VALU: one launch, one label row per thread, blocked left-looking
  * factorisation on the vector pipe (every size).  GPMPC_JOINT_MFMA: four launches on the same stream - joint_test_mfma_kernel
  * extends the factor by the rows of the new hallucinated slots (their entries against the old columns, the Schur complement),
- * joint_kernel factorises the Schur complement, joint_test_mfma_kernel forms V^T = L^-1 K_o*, the mean and S = K** - V^T V on the
+ * joint_chol_mfma_kernel factorises the Schur complement, joint_test_mfma_kernel forms V^T = L^-1 K_o*, the mean and S = K** - V^T V on the
  * FP64 matrix pipe with the whole test block in registers, the tail draws - instantiated for n_r <= 64 real slots,
  * n_r + n_ho <= 416 conditioning slots (<= 544 with the test rows in two launches; that form needs the caller's factor cache) and
  * m*T + 1 <= 128; taken from 100 hallucinated slots on, from 48 when m*T >= 84
@@ -325,7 +325,9 @@ int    gpmpc_joint_pending_written(void);    /* 1: the last gpmpc_joint_sample[_
  * chain against the plan's shared inverse factor (GPMPC_JOINT_REAL_KERNEL=0: joint_kernel's head as before); the same kernel
  * is the matrix-pipe path's factor extension while nothing is cached.  Results of the two paths agree to rounding, not bit for bit: a caller that compares launches bit
  * for bit (cache on / off, sample shards against the whole batch) pins the path.  gpmpc_joint_pin_path(GPMPC_JOINT_AUTO) releases
- * the pin; a pinned GPMPC_JOINT_MFMA falls back to the VALU path for sizes it is not instantiated for.
+ * the pin; a pinned GPMPC_JOINT_MFMA falls back to the VALU path for sizes it is not instantiated for.  Which kernels a call
+ * launches is decided in one place, plan_joint_draw (sampling_gpmpc_amd/csrc/joint_plan.hpp), a pure function of the call's shape
+ * and the knobs.
  */
 #define GPMPC_JOINT_AUTO 0
 #define GPMPC_JOINT_VALU 1

@@ -20,10 +20,13 @@
 //   * root = Cholesky of S with the jitter-on-failure chain (A.7), y = mean + R z, post-processing of sample_gp.
 //   * S is left in a per-chain buffer: when any chain of the batch fails all retries, joint_eigh_kernel
 //     (joint_eigh.hpp, launched right behind this kernel) redraws the whole batch with the eigendecomposition root.
+#include <cstdio>
+#include <string>
 #include <type_traits>
 #include "gpmpc_host.hpp"
 #include "joint_args.hpp"
 #include "joint_eigh.hpp"
+#include "joint_plan.hpp"
 
 namespace gpmpc {
 
@@ -1009,49 +1012,36 @@ struct JointWs {
 
 static int fc_row_stride(int n_r, int rows) { return (n_r + rows + 1) & ~1; }
 
-// the launch sizes from which the matrix-pipe path (factor phase + joint_test_mfma_kernel + tail) is taken
-static int joint_mfma_from() {
-    // hallucinated slots from which it is used (0: never).  configs[4] shard (car, Ns = 1024, H = 40, closed-loop points), VALU path
-    // against this one: k = 3 (360 slots) 7.15 / 4.53 ms, k = 2 (240) 4.45 / 3.15, k = 1 (120) 2.16 / 2.12 (Ns = 4096: 7.68 / 7.49) - the
-    // fixed per-chain phases of joint_test_mfma_kernel (descriptors, tile inversion, kernel entries) only pay behind a
-    // substitution of some length; below ~100 slots the one-launch VALU form wins
-    static const char* env = getenv("GPMPC_JOINT_MFMA_FROM");
-    return env ? atoi(env) : 100;
-}
-static int g_tail_kernel_force = -1;      // gpmpc_debug_joint_tail_kernel: -1 default (on), 0 / 1 forced
-static int g_chol_kernel_force = -1;      // gpmpc_debug_joint_chol_kernel: -1 default (on), 0 / 1 forced (tests, A/B timing)
 static int g_real_kernel_force = -1;      // gpmpc_debug_joint_real_kernel: -1 default (on), 0 / 1 forced (tests, A/B timing)
 static int g_eigh_narrow_force = -1;      // gpmpc_debug_eigh_narrow: -1 heuristic, 0 / 1 forced (tests)
 static int g_joint_path_pin = 0;          // gpmpc_joint_pin_path: 0 auto, 1 VALU path, 2 matrix-pipe path where instantiated
 static int g_joint_last_path = 0;
-static bool joint_mfma_wanted(int n_ho, int mT) {
-    if (g_joint_path_pin == 1) return false;
-    if (g_joint_path_pin == 2) return true;
-    const int from = joint_mfma_from();
-    if (from > 0 && n_ho >= from) return true;
-    // Round 6 (the factor rows with nothing cached by joint_real_mfma_kernel, the Cholesky and the tail one wave per chain, S written once): with
-    // a WIDE test block the matrix pipe also wins below 100 slots - Ns = 1024, scattered points, VALU / matrix pipe in ms: pendulum H = 30 at
-    // 90 slots 0.547 / 0.458 (its closed loop's second SQP iteration: 0.489 -> 0.405), car H = 30 at 90 slots 2.44 / 2.30; with a narrow one it
-    // does not (car H = 20 at 60 / 120 slots 1.44 / 1.61 and 1.89 / 2.33; pendulum H = 15 at 90 slots 0.38 / 0.52: the fixed per-chain parts
-    // of joint_test_mfma_kernel do not shrink with the columns).  GPMPC_JOINT_MFMA_FROM, when set, is the whole rule.
-    static const char* env = getenv("GPMPC_JOINT_MFMA_FROM");
-    return !env && n_ho >= 48 && mT >= 84;
-}
-static bool joint_use_mfma(int n_r, int n_ho, int m, int T) {
-    return n_ho >= 1 && joint_mfma_eligible(n_r, n_ho, m * T + 1, T) && joint_mfma_wanted(n_ho, m * T);
-}
-// conditioning sets beyond one launch of joint_test_mfma_kernel (the 45 + 480 slots of the k = 0 draw of MPC steps >= 1 at
-// configs[4]): the test rows in two launches (JOINT_MFMA_TEST_TOP / _BOTTOM); needs a caller-owned factor cache with every row
-static bool joint_use_mfma_split(int n_r, int n_ho, int m, int T) {
-    static const char* env = getenv("GPMPC_JOINT_MFMA_SPLIT");         // 0: such draws stay on the vector pipe (A/B timing)
-    if (env && atoi(env) == 0) return false;
-    return joint_mfma_split_eligible(n_r, n_ho, m * T + 1, T) && joint_mfma_wanted(n_ho, m * T);
+
+// every knob of the joint draw: the environment read once per process (GPMPC_EIGH_GLOBAL_G, a test knob, on every call), then the
+// debug forces and the path pin
+static JointKnobs joint_knobs() {
+    static const JointKnobs env = [] {
+        JointKnobs k = {};
+        const char* from = getenv("GPMPC_JOINT_MFMA_FROM");         // when set, the whole rule (0: never)
+        k.mfma_from = from ? (atoi(from) > 0 ? atoi(from) : 0) : -1;
+        const char* abandon = getenv("GPMPC_JOINT_ABANDON");        // 0 / 1: abandoning forced off / on
+        k.abandon = abandon ? (atoi(abandon) != 0) : -1;
+        const char* real = getenv("GPMPC_JOINT_REAL_KERNEL");       // 0: joint_real_mfma_kernel off
+        k.real_kernel = real ? atoi(real) : 1;
+        const char* narrow = getenv("GPMPC_EIGH_NARROW");           // 0 / 1: the narrow eigh launch forced off / on
+        k.eigh_narrow = narrow ? atoi(narrow) : -1;
+        return k;
+    }();
+    JointKnobs k = env;
+    if (g_real_kernel_force >= 0) k.real_kernel = g_real_kernel_force;
+    if (g_eigh_narrow_force >= 0) k.eigh_narrow = g_eigh_narrow_force;
+    k.eigh_global_G = getenv("GPMPC_EIGH_GLOBAL_G") != nullptr;
+    k.path_pin = g_joint_path_pin;
+    return k;
 }
 
 static long eigh_grid(long nchains) {
-    static const char* env = getenv("GPMPC_EIGH_SLOTS_PER_CU");       // experiment knob (tools/eigh_sweep.sh)
-    const long per_cu = env ? atol(env) : 10;            // one wave per chain, ~8 resident per CU (LDS / VGPR bound)
-    const long cap = 256L * (per_cu > 0 ? per_cu : 10);
+    const long cap = 256L * 10;                         // one wave per chain, ~8 resident per CU (LDS / VGPR bound)
     return nchains < cap ? nchains : cap;
 }
 
@@ -1078,17 +1068,46 @@ static JointWs joint_ws_layout(int n_r, int n_ho, int m, int T, long nchains) {
         w.tc_rows = (n_ho + 1) & ~1;
         w.tc_cs = fc_row_stride(n_r, w.tc_rows);
         w.tc_stride = (long)w.tc_rows * (w.tc_cs + 1);
-        w.tc_slots = nchains < 1024 ? nchains : 1024;
+        w.tc_slots = nchains < JOINT_TC_SLOTS ? nchains : JOINT_TC_SLOTS;
         w.tc_off = (w.total + 1) & ~1L;
         w.total = w.tc_off + w.tc_slots * w.tc_stride;
     }
     w.xt_off = w.xt_slots = 0;
     if (joint_mfma_split_eligible(n_r, n_ho, m * (int)T + 1, T)) {                // (pin-independent, as above)
-        w.xt_slots = nchains < 3072 ? nchains : 3072;          // 416 KB per chain: 1.3 GB at most
+        w.xt_slots = nchains < JOINT_XT_SLOTS ? nchains : JOINT_XT_SLOTS;      // 416 KB per chain: 1.3 GB at most
         w.xt_off = (w.total + 1) & ~1L;
         w.total = w.xt_off + w.xt_slots * JOINT_MFMA_XBUF_DOUBLES;
     }
     return w;
+}
+
+static JointShape joint_shape(const gpmpc_gp_desc_t* gp, long Ns, int n_h, int n_ho, int m, int cache_rows, int n_cached, int pending,
+                              int root_mode, int last_rank) {
+    JointShape s;
+    s.T = gp->T;
+    s.D = gp->D;
+    s.n_r = observed_real_slots(gp);
+    s.N_r = gp->N_r;
+    s.nchains = Ns * gp->g_ny;
+    s.n_h = n_h;
+    s.n_ho = n_ho;
+    s.n_c = cache_rows > 0 ? n_cached : 0;
+    s.m = m;
+    s.cache_rows = cache_rows;
+    s.pending = pending;
+    s.root_mode = root_mode;
+    s.last_rank = last_rank;
+    return s;
+}
+
+static const char* const JOINT_MFMA_MODE_NAMES[] = {"TEST", "FACTOR", "TEST_TOP", "TEST_BOTTOM"};
+static const char* joint_phase_name(int phase) {
+    switch (phase) {
+        case JOINT_PHASE_ALL: return "ALL";
+        case JOINT_PHASE_FACTOR: return "FACTOR";
+        case JOINT_PHASE_HEAD: return "HEAD";
+        default: return "?";
+    }
 }
 
 }  // namespace gpmpc
@@ -1111,19 +1130,6 @@ int gpmpc_debug_read_eigh_work(unsigned long long* out /*[host] 4*/, int reset) 
     return GPMPC_OK;
 }
 
-// tests / A-B timing: 0 = joint_kernel's own tail, 1 = joint_tail_mfma_kernel, -1 = default (1); returns the previous value
-int gpmpc_debug_joint_tail_kernel(int mode) {
-    const int prev = g_tail_kernel_force;
-    g_tail_kernel_force = mode < 0 ? -1 : (mode ? 1 : 0);
-    return prev;
-}
-// tests / A-B timing: 0 = the matrix-pipe path's Cholesky of the Schur complement by joint_kernel's CHOL phase, 1 = by
-// joint_chol_mfma_kernel, -1 = default (1); returns the previous value
-int gpmpc_debug_joint_chol_kernel(int mode) {
-    const int prev = g_chol_kernel_force;
-    g_chol_kernel_force = mode < 0 ? -1 : (mode ? 1 : 0);
-    return prev;
-}
 // tests / A-B timing: joint_real_mfma_kernel (columns conditioned on the real data alone: the factor extension with nothing cached, the
 // draw without hallucinated slots) off (0) / on (1), -1 = default (on; GPMPC_JOINT_REAL_KERNEL=0 turns it off); returns the previous value
 int gpmpc_debug_joint_real_kernel(int mode) {
@@ -1172,6 +1178,52 @@ int gpmpc_debug_eigh_occupancy(int mT, size_t extra_lds) {
     return nb;
 }
 
+}  // extern "C"
+
+namespace gpmpc {
+
+// (defined here, behind gpmpc_debug_eigh_occupancy: the order in which the kernels are first instantiated is their order in the code
+// object, and the narrow eigh kernel measured 20-50 % slower at another placement)
+// joint_kernel for the chains [a.chain0, a.chain1) with `nrow` label rows per chain: one label row per thread and a workgroup just
+// wide enough for the rows (more chains per CU when they are short: iteration 0 of config 5 has 121 rows; iteration 0 of every later
+// MPC step conditions on the previous step's whole hallucinated set - the reference's reset-after-build quirk - i.e. 601 rows at
+// config 5: 1024 threads).  Long conditioning sets on the 256-thread workgroups take 32-column blocks at two waves per SIMD (256
+// VGPRs) - half the workspace re-reads; the draw is stream-bound and loses little with fewer chains per CU, but the wider blocks cost
+// more serial work per block, so only from JOINT_WIDE_FROM hallucinated slots on (k=3 scattered points 9.8 against 10.8 ms; k=2 7.2 / 7.0)
+template <int T>
+static void launch_joint_kernel_t(const JointArgs& a, int nrow, long grid, hipStream_t st) {
+    const long nch = a.chain1 - a.chain0;
+    const dim3 g((unsigned)(nch < grid ? nch : grid));
+    if (nrow <= 128) hipLaunchKernelGGL((joint_kernel<T, GPMPC_JOINT_NB, 1, 128, GPMPC_JOINT_WPE>), g, dim3(128), 0, st, a);
+    else if (nrow <= 256 && a.n_ho >= JOINT_WIDE_FROM) hipLaunchKernelGGL((joint_kernel<T, GPMPC_JOINT_WIDE_NB, 1, 256, 2>), g, dim3(256), 0, st, a);
+    else if (nrow <= 256) hipLaunchKernelGGL((joint_kernel<T, GPMPC_JOINT_NB, 1, 256, GPMPC_JOINT_WPE>), g, dim3(256), 0, st, a);
+    else if (nrow <= 512) hipLaunchKernelGGL((joint_kernel<T, 16, 1, 512, GPMPC_JOINT_WPE>), g, dim3(512), 0, st, a);
+    else if (nrow <= 1024) hipLaunchKernelGGL((joint_kernel<T, 16, 1, 1024, 4>), g, dim3(1024), 0, st, a);
+    else hipLaunchKernelGGL((joint_kernel<T, 16, 2, 1024, 4>), g, dim3(1024), 0, st, a);
+}
+static void launch_joint_kernel(const JointArgs& a, int nrow, long grid, hipStream_t st) {
+    if (a.gp.T == 1) launch_joint_kernel_t<1>(a, nrow, grid, st);
+    else launch_joint_kernel_t<3>(a, nrow, grid, st);
+}
+
+// joint_eigh_kernel: the narrow instantiation (EIGH_PASS_NARROW) or the full one, wider still beyond 128 test slots
+template <int T>
+static void launch_joint_eigh_t(const EighArgs& e, int mT, long grid, bool narrow, hipStream_t st) {
+    const size_t lds = (size_t)eigh_lds_doubles(mT, e.lds_cap) * sizeof(double);
+    const dim3 g((unsigned)grid), b(64);
+    if (mT > 128) hipLaunchKernelGGL((joint_eigh_kernel<T, 4, GPMPC_EIGH_WPE>), g, b, lds, st, e);
+    else if (narrow) hipLaunchKernelGGL((joint_eigh_kernel<T, 2, GPMPC_EIGH_NARROW_WPE>), g, b, lds, st, e);
+    else hipLaunchKernelGGL((joint_eigh_kernel<T, 2, GPMPC_EIGH_WPE>), g, b, lds, st, e);
+}
+static void launch_joint_eigh(const EighArgs& e, int T, int mT, long grid, bool narrow, hipStream_t st) {
+    if (T == 1) launch_joint_eigh_t<1>(e, mT, grid, narrow, st);
+    else launch_joint_eigh_t<3>(e, mT, grid, narrow, st);
+}
+
+}  // namespace gpmpc
+
+extern "C" {
+
 // bytes of the caller-owned factor cache of gpmpc_joint_sample for up to cache_rows hallucinated label rows per chain
 size_t gpmpc_joint_cache_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int32_t cache_rows) {
     if (check_gp(gp) != GPMPC_OK || cache_rows < 16 || (cache_rows & 1) || Ns < 1) return 0;
@@ -1213,6 +1265,7 @@ int gpmpc_joint_sample_pending(const gpmpc_gp_desc_t* gp, const void* plan, cons
     if (n_ho > 0 && (!X_h || !Y_h || !h_slots)) return fail(GPMPC_E_ARG, "gpmpc_joint_sample: hallucinated data missing");
     if (n_ho > n_h * gp->T) return fail(GPMPC_E_ARG, "gpmpc_joint_sample: n_ho > n_h*T");
     if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, "only D = 2 is instantiated");
+    if (gp->T != 1 && gp->T != 3) return fail(GPMPC_E_UNSUPPORTED, "joint: only T = 1 and T = 3 (D = 2) are instantiated");
     const int mT = m * gp->T;
     if (mT > 256) return fail(GPMPC_E_UNSUPPORTED, "joint: m*T > 256");
     if (n_ho + 1 + mT > 2048) return fail(GPMPC_E_UNSUPPORTED, "joint: more than 2048 label rows per chain");
@@ -1277,282 +1330,134 @@ int gpmpc_joint_sample_pending(const gpmpc_gp_desc_t* gp, const void* plan, cons
     a.xbuf = nullptr;
     hipStream_t st = (hipStream_t)stream;
     GPMPC_HIP_CHECK(hipMemsetAsync(a.any_fail, 0, 4 * sizeof(int), st));      // any_fail, deferred chains, max rank (joint_eigh_kernel)
+    // the largest eigh rank of the last call whose counter has arrived (pinned, read back behind every eigh launch)
+    static int* hint_host = nullptr;
+    const int last_rank = hint_host ? *(volatile int*)hint_host : 0;
+    const JointPlan p = plan_joint_draw(joint_shape(gp, Ns, n_h, n_ho, m, factor_cache ? cache_rows : 0, n_cached, pending, root_mode, last_rank),
+                                        joint_knobs());
+    g_joint_last_path = p.path;
     const long nchains = Ns * gp->g_ny;
-    // Abandoning pays when the launch needs at least two rounds of the chip (the chains of later rounds skip their root
-    // phase): measured on the car's closed loop, Ns = 1024: k = 0 (1.5 rounds) +5 %, k = 1..3 and the 480-slot k = 0
-    // (3-6 rounds) -1.5 ... -4.5 %; Ns = 4096: -3 ... -7 % at every k.  GPMPC_JOINT_ABANDON=0 / 1 forces it off / on.
-    auto abandon_for = [&](int nrow) -> int {
-        static const char* aenv = getenv("GPMPC_JOINT_ABANDON");
-        const int nt_ = (nrow <= 128) ? 128 : ((nrow <= 256) ? 256 : ((nrow <= 512) ? 512 : 1024));
-        const int wpe_ = (nrow > 128 && nrow <= 256 && n_ho >= 300) ? 2 : 4;
-        const double rounds = (double)nchains * nt_ / (256.0 * 256.0 * wpe_);
-        const bool on = aenv ? (atoi(aenv) != 0) : (rounds >= 2.0);
-        return (root_mode == GPMPC_ROOT_AUTO && mT > 1 && on) ? 1 : 0;
-    };
-    // one label row per thread and a workgroup just wide enough for the rows (more chains per CU when they are short:
-    // iteration 0 of config 5 has 121 rows; iteration 0 of every later MPC step conditions on the previous step's
-    // whole hallucinated set - the reference's reset-after-build quirk - i.e. 601 rows at config 5: 1024 threads)
-    static const char* penv = getenv("GPMPC_JOINT_LDS_PAD");           // experiment knob: dynamic LDS bytes per workgroup (caps the chains per CU)
-    const size_t lds_pad = penv ? (size_t)atol(penv) : 0;
-    // long conditioning sets on the 256-thread workgroups: 32-column blocks at two waves per SIMD (256 VGPRs) - half the
-    // workspace re-reads; the draw is stream-bound and loses little with fewer chains per CU, but the wider blocks cost more
-    // serial work per block, so only from ~300 hallucinated slots on (k=3 scattered points 9.8 against 10.8 ms; k=2 7.2 / 7.0)
-    static const char* wenv = getenv("GPMPC_JOINT_WIDE_FROM");        // experiment knob: hallucinated slots from which it is used
-    const bool wide = n_ho >= (wenv ? atoi(wenv) : 300);
-    // launches joint_kernel for the chains [aa.chain0, aa.chain1) with `nrow` label rows per chain
-    auto launch = [&](const JointArgs& aa, int nrow) {
-        const long nch = aa.chain1 - aa.chain0;
-        const dim3 g((unsigned)(nch < w.grid ? nch : w.grid));
-#define GPMPC_JOINT_LAUNCH(TT)                                                                              \
-    do {                                                                                                    \
-        if (nrow <= 128) hipLaunchKernelGGL((joint_kernel<TT, GPMPC_JOINT_NB, 1, 128, GPMPC_JOINT_WPE>), g, dim3(128), lds_pad, st, aa);      \
-        else if (nrow <= 256 && wide) hipLaunchKernelGGL((joint_kernel<TT, GPMPC_JOINT_WIDE_NB, 1, 256, 2>), g, dim3(256), lds_pad, st, aa); \
-        else if (nrow <= 256) hipLaunchKernelGGL((joint_kernel<TT, GPMPC_JOINT_NB, 1, 256, GPMPC_JOINT_WPE>), g, dim3(256), lds_pad, st, aa); \
-        else if (nrow <= 512) hipLaunchKernelGGL((joint_kernel<TT, 16, 1, 512, GPMPC_JOINT_WPE>), g, dim3(512), 0, st, aa); \
-        else if (nrow <= 1024) hipLaunchKernelGGL((joint_kernel<TT, 16, 1, 1024, 4>), g, dim3(1024), 0, st, aa);            \
-        else hipLaunchKernelGGL((joint_kernel<TT, 16, 2, 1024, 4>), g, dim3(1024), 0, st, aa);               \
-    } while (0)
-        if (gp->T == 1) GPMPC_JOINT_LAUNCH(1);
-        else GPMPC_JOINT_LAUNCH(3);
-#undef GPMPC_JOINT_LAUNCH
-    };
-    if (gp->T != 1 && gp->T != 3) return fail(GPMPC_E_UNSUPPORTED, "joint: only T = 1 and T = 3 (D = 2) are instantiated");
-    // the tail (root with the jitter chain, sample, post-processing) as joint_tail_mfma_kernel (joint_chol.hip, round 6) wherever it is
-    // instantiated: T = 3, 2 .. 128 test slots; GPMPC_JOINT_TAIL_KERNEL=0 / gpmpc_debug_joint_tail_kernel(0): joint_kernel's own tail
-    static const char* tenv = getenv("GPMPC_JOINT_TAIL_KERNEL");
-    const int tforce = g_tail_kernel_force >= 0 ? g_tail_kernel_force : (tenv ? atoi(tenv) : 1);
-    const bool tail_kernel = tforce != 0 && joint_tail_mfma_eligible(mT, gp->T);
-    // joint_tail_mfma_kernel abandons too (one flag read at the head of an attempt): it pays as soon as the launch has a second round of
-    // waves (one wave per chain and SIMD at six tiles and more, two below); GPMPC_JOINT_ABANDON=0 / 1 forces it off / on
-    static const char* taenv = getenv("GPMPC_JOINT_ABANDON");
-    const int tail_abandon = (root_mode == GPMPC_ROOT_AUTO && mT > 1 &&
-                              (taenv ? atoi(taenv) != 0 : nchains > (mT > 80 ? 1024 : 2048))) ? 1 : 0;
-    JointArgs sv_args = a;                             // whose Sv* the eigh launch reads (redirected only with the caller's own cache: one batch)
-    const bool split = !joint_use_mfma(a.gp.n_r, n_ho, m, gp->T) && joint_use_mfma_split(a.gp.n_r, n_ho, m, gp->T) &&
-                       a.fcache && n_ho <= a.fc_cap && (a.fc_cap % 2) == 0;
-    if (joint_use_mfma(a.gp.n_r, n_ho, m, gp->T) || split) {
-        // The matrix-pipe path: (i) the factor is extended by the rows of the new hallucinated slots - their entries against the
-        // old columns and the Schur complement on the matrix pipe (joint_test_mfma_kernel, JOINT_MFMA_FACTOR), the Schur
-        // complement's blocked Cholesky by joint_kernel (JOINT_PHASE_CHOL); where that is not instantiated (more than 128 new
-        // rows, or more new rows than test slots) joint_kernel's factor phase forms the rows on the vector pipe -, (ii)
-        // joint_test_mfma_kernel forms the test rows, the mean and S, (iii) the tail draws.  Without a caller-owned cache that
-        // can take this call's rows the factor rows go to a temporary cache inside the workspace, one batch of chains at a time.
-        g_joint_last_path = 2;
-        const bool own = a.fcache && n_ho <= a.fc_cap && (a.fc_cap % 2) == 0;
-        JointArgs b = a;
-        if (!own) {
-            b.fcache = (double*)ws + w.tc_off;
-            b.fc_cap = w.tc_rows;
-            b.fc_cs = w.tc_cs;
-            b.fc_stride = w.tc_stride;
-            b.n_c = 0;
-        }
-        const int n_new = n_ho - b.n_c;
-        static const char* fenv = getenv("GPMPC_JOINT_MFMA_FACTOR");      // 0: the factor phase stays on the vector pipe
-        // (with nothing cached - the second SQP iteration - the new rows only meet the real columns: joint_kernel's factor phase does
-        // rows and Cholesky in one launch, 1.98 against 2.15 ms per draw at configs[4], k = 1; from 120 cached slots on the matrix pipe
-        // wins: 3.2 against 3.9 ms at k = 2)
-        // (round 6: with the Schur complement's Cholesky on the matrix pipe too - joint_chol.hip - the factor extension wins with
-        // nothing cached as well: 1.91 against 2.03 ms at configs[4], k = 1; GPMPC_JOINT_MFMA_FACTOR_FIRST=0 keeps that draw's factor
-        // phase on the vector pipe)
-        static const char* f0env = getenv("GPMPC_JOINT_MFMA_FACTOR_FIRST");
-        const bool mfma_factor = n_new > 0 && n_new <= mT && (b.n_c > 0 || !(f0env && atoi(f0env) == 0)) &&
-                                 joint_mfma_eligible(a.gp.n_r, b.n_c, n_new, gp->T) && !(fenv && atoi(fenv) == 0);
-        // pending rows (see JointArgs): used when the caller says so and the shapes allow it; written by the one-launch test mode
-        // into the caller's cache when the rows fit
-        // (GPMPC_PENDING_USE is a permission: where the shapes do not allow it - or on the VALU path - the rows are recomputed)
-        const bool pend_use = (pending & GPMPC_PENDING_USE) && own && b.n_c > 0 && gp->T == 3 && joint_chol_mfma_eligible(n_new);
-        const bool pend_write = (pending & GPMPC_PENDING_WRITE) && own && !split && gp->T == 3 && n_ho + mT <= a.fc_cap &&
-                                joint_chol_mfma_eligible(mT);
-        static const char* renv = getenv("GPMPC_JOINT_REAL_KERNEL");
-        const int rforce = g_real_kernel_force >= 0 ? g_real_kernel_force : (renv ? atoi(renv) : 1);
-        const bool real_first = rforce != 0 && b.n_c == 0 && n_new == n_ho && joint_real_mfma_eligible(a.gp.n_r, a.gp.N_r, n_ho, n_h, gp->T, gp->D) &&
-                                joint_chol_mfma_eligible(n_new) && !(fenv && atoi(fenv) == 0);
-        const long step = split ? w.xt_slots : (own ? nchains : w.tc_slots);
-        for (long c0 = 0; c0 < nchains; c0 += step) {
-            b.chain0 = c0;
-            b.chain1 = (c0 + step < nchains) ? c0 + step : nchains;
-            b.fc_chain_base = own ? 0 : c0;
-            b.info_in = 0;
-            b.abandon_root = 0;
-            if (n_new > 0 && pend_use) {
-                // the caller vouches that the cache rows n_c .. n_ho - 1 hold the previous call's X^T and S (its test points are
-                // this call's new slots): the factor extension is the Cholesky of (S + noise) in place, nothing else
-                b.pend_use = 1;
-                if (int rc = joint_chol_mfma_launch(b, st)) return rc;
-                b.pend_use = 0;
-                GPMPC_HIP_CHECK(hipGetLastError());
-                b.info_in = 1;
-            } else if (n_new > 0 && real_first) {
-                // nothing cached - the second SQP iteration of an MPC step, right behind the reset - so the new slots only meet the real
-                // columns: one wave per chain forms X^T and the Schur complement in the cache (what a draw with pending rows leaves
-                // there), joint_chol_mfma_kernel factorises it in place (0.41 + 0.18 -> 0.1 + 0.18 ms at the configs[4] shard)
-                b.mfma_mode = JOINT_MFMA_FACTOR;
-                if (int rc = joint_real_mfma_launch(b, st)) return rc;
-                b.pend_use = 1;
-                if (int rc = joint_chol_mfma_launch(b, st)) return rc;
-                b.pend_use = 0;
-                b.info_in = 1;
-            } else if (n_new > 0) {
-                if (mfma_factor) {
-                    b.mfma_mode = JOINT_MFMA_FACTOR;
-                    if (int rc = joint_mfma_launch(b, st)) return rc;
-                    b.phase = JOINT_PHASE_CHOL;
-                } else {
-                    b.phase = JOINT_PHASE_FACTOR;
-                }
-                // the Schur complement's Cholesky: one wave per chain on the matrix pipe (joint_chol.hip, round 6: 0.45 -> ~0.1 ms
-                // per draw at the configs[4] shard); GPMPC_JOINT_CHOL_KERNEL=0 / gpmpc_debug_joint_chol_kernel(0): joint_kernel's CHOL phase
-                static const char* cenv = getenv("GPMPC_JOINT_CHOL_KERNEL");
-                const int cforce = g_chol_kernel_force >= 0 ? g_chol_kernel_force : (cenv ? atoi(cenv) : 1);
-                if (mfma_factor && cforce != 0 && joint_chol_mfma_eligible(n_new)) {
-                    if (int rc = joint_chol_mfma_launch(b, st)) return rc;
-                } else {
-                    launch(b, n_new);
-                }
-                GPMPC_HIP_CHECK(hipGetLastError());
-                b.info_in = 1;
+    JointArgs b = a;
+    if (p.temp_cache) {
+        b.fcache = (double*)ws + w.tc_off;
+        b.fc_cap = w.tc_rows;
+        b.fc_cs = w.tc_cs;
+        b.fc_stride = w.tc_stride;
+        b.n_c = 0;
+    }
+    // the covariance as the factor cache's pending block (caller's cache, one batch): chain c's block of the rows n_ho .. n_ho + m T - 1
+    double* const Sv_cache = b.fcache ? b.fcache + (long)n_ho * b.fc_cs + a.gp.n_r + n_ho : nullptr;
+    for (long c0 = 0; c0 < nchains; c0 += p.batch) {
+        b.chain0 = c0;
+        b.chain1 = (c0 + p.batch < nchains) ? c0 + p.batch : nchains;
+        b.fc_chain_base = p.temp_cache ? c0 : 0;
+        for (int i = 0; i < p.nsteps; ++i) {
+            const JointStep& s = p.steps[i];
+            b.mfma_mode = s.mfma_mode;
+            b.phase = s.phase;
+            b.pend_use = s.pend_use;
+            b.pend_write = s.pend_write;
+            b.abandon_root = s.abandon_root;
+            b.info_in = s.info_in;
+            b.Sv = s.sv_cache ? Sv_cache : a.Sv;
+            b.Sv_ld = s.sv_cache ? b.fc_cs : a.Sv_ld;
+            b.Sv_cs = s.sv_cache ? b.fc_stride : a.Sv_cs;
+            b.Sv_chain_base = s.sv_cache ? b.fc_chain_base : a.Sv_chain_base;
+            if (s.mfma_mode == JOINT_MFMA_TEST_TOP || s.mfma_mode == JOINT_MFMA_TEST_BOTTOM) b.xbuf = (double*)ws + w.xt_off;
+            switch (s.kernel) {
+                case JOINT_K_JOINT: launch_joint_kernel(b, s.nrow, w.grid, st); break;
+                case JOINT_K_TEST_MFMA: if (int rc = joint_mfma_launch(b, st)) return rc; break;
+                case JOINT_K_REAL_MFMA: if (int rc = joint_real_mfma_launch(b, st)) return rc; break;
+                case JOINT_K_CHOL_MFMA: if (int rc = joint_chol_mfma_launch(b, st)) return rc; break;
+                case JOINT_K_TAIL_MFMA: if (int rc = joint_tail_mfma_launch(b, st)) return rc; break;
             }
-            if (split) {
-                b.xbuf = (double*)ws + w.xt_off;
-                b.mfma_mode = JOINT_MFMA_TEST_TOP;
-                if (int rc = joint_mfma_launch(b, st)) return rc;
-                b.mfma_mode = JOINT_MFMA_TEST_BOTTOM;
-            } else {
-                b.mfma_mode = JOINT_MFMA_TEST;
-                b.pend_write = pend_write ? 1 : 0;
-                if (pend_write && tail_kernel) {       // S once: the pending block IS the covariance buffer of this draw's tail and eigh root
-                    b.Sv = b.fcache + (long)n_ho * b.fc_cs + a.gp.n_r + n_ho;
-                    b.Sv_ld = b.fc_cs;
-                    b.Sv_cs = b.fc_stride;
-                    b.Sv_chain_base = b.fc_chain_base;
-                    sv_args = b;
-                }
-            }
-            if (int rc = joint_mfma_launch(b, st)) return rc;
-            b.pend_write = 0;
-            if (tail_kernel) {
-                b.abandon_root = tail_abandon;
-                if (int rc = joint_tail_mfma_launch(b, st)) return rc;
-            } else {
-                b.phase = JOINT_PHASE_TAIL;
-                b.abandon_root = abandon_for(mT);
-                launch(b, mT);
-            }
-        }
-        g_joint_pending_written = pend_write ? 1 : 0;
-    } else {
-        // (Measured and dropped: for conditioning sets beyond joint_test_mfma_kernel's 416 slots - k = 0 of the MPC steps after the first,
-        // 45 + 480 slots at configs[4] - the factor extension alone on the matrix pipe and the test rows here with every
-        // hallucinated row cached: 13.3 ms against 11.2 - the test rows' stream is the critical path of this kernel either way.)
-        g_joint_last_path = 1;
-        const int nrow = n_ho + 1 + mT - a.n_c;        // rows that are computed (the cached ones have no thread)
-        static const char* renv = getenv("GPMPC_JOINT_REAL_KERNEL");
-        const int rforce = g_real_kernel_force >= 0 ? g_real_kernel_force : (renv ? atoi(renv) : 1);
-        if (n_ho == 0 && tail_kernel && rforce != 0 && g_joint_path_pin != 1 && joint_real_mfma_eligible(a.gp.n_r, a.gp.N_r, mT, m, gp->T, gp->D)) {
-            // no hallucinated slot (the first SQP iteration of the first MPC step): the test columns only meet the real data, whose
-            // inverse factor all chains of an output share - X = L_rr^-1 K_r*, mean and S one wave per chain on the matrix pipe
-            g_joint_last_path = 2;
-            a.mfma_mode = JOINT_MFMA_TEST;
-            if (int rc = joint_real_mfma_launch(a, st)) return rc;
-            a.info_in = 1;
-            a.abandon_root = tail_abandon;
-            if (int rc = joint_tail_mfma_launch(a, st)) return rc;
-        } else if (tail_kernel) {                             // head (factor rows, test rows, mean, S) here, the tail one wave per chain
-            a.phase = JOINT_PHASE_HEAD;
-            a.abandon_root = 0;
-            launch(a, nrow);
             GPMPC_HIP_CHECK(hipGetLastError());
-            a.info_in = 1;
-            a.abandon_root = tail_abandon;
-            if (int rc = joint_tail_mfma_launch(a, st)) return rc;
-        } else {
-            a.abandon_root = abandon_for(nrow);
-            launch(a, nrow);
         }
     }
+    g_joint_pending_written = p.pending_written;
+    if (p.eigh == JOINT_EIGH_NONE) return GPMPC_OK;
+    // eigendecomposition root for the whole batch when a chain failed all jitter retries (or on request); the kernel returns at once
+    // when the flag is clear
+    EighArgs e;
+    e.gp = a.gp;
+    e.Ns = Ns;
+    e.m = m;
+    e.z = z;
+    e.var_zero_thr = var_zero_thr;
+    e.beta = beta;
+    e.apply_clip = apply_clip;
+    e.mean = mean;
+    e.var = var;
+    e.y = y;
+    e.info = (int*)info;
+    e.Sall = p.eigh_sv_cache ? Sv_cache : a.Sv;
+    e.S_ld = p.eigh_sv_cache ? b.fc_cs : a.Sv_ld;
+    e.S_cs = p.eigh_sv_cache ? b.fc_stride : a.Sv_cs;
+    e.any_fail = a.any_fail;
+    e.force = (root_mode == GPMPC_ROOT_EIGH);
+    e.ws = (double*)ws + w.e_off;
+    e.ws_slot_stride = w.estride;
+    e.root = root;
+    const int np = (mT + 1) & ~1;
+    e.lds_cap = p.eigh_global_G ? 0 : (np < EIGH_LDS_RANK ? np : EIGH_LDS_RANK);
+    e.tol_mult = 16.0;
+    e.gg_off = (long)mT * mT;
+    e.rlog_off = e.gg_off + 2 * eigh_packed(np);
+    e.pass = EIGH_PASS_ALL;
+    e.defer_rank = 0;
+    int* flags = a.any_fail;                            // [0] any_fail, [1] deferred chains, [2] max rank of this call; zeroed above
+    e.defer_count = flags + 1;
+    e.rank_hint = flags + 2;
+    e.defer_list = (int*)((double*)ws + w.d_off);
+    if (!hint_host) {
+        GPMPC_HIP_CHECK(hipHostMalloc((void**)&hint_host, sizeof(int), hipHostMallocDefault));
+        *hint_host = 0;
+    }
+    if (p.eigh == JOINT_EIGH_NARROW_DEFERRED) {
+        EighArgs en = e;
+        en.pass = EIGH_PASS_NARROW;
+        en.lds_cap = EIGH_NARROW_RANK;
+        en.defer_rank = EIGH_NARROW_RANK;
+        en.gg_off = 0;                                  // (no chain of this launch takes the HBM/L2 form)
+        en.rlog_off = (long)mT * (EIGH_NARROW_RANK + EIGH_PB);
+        en.ws_slot_stride = eigh_narrow_slot_doubles((int)mT);
+        launch_joint_eigh(en, gp->T, mT, w.egrid_narrow, true, st);
+        GPMPC_HIP_CHECK(hipGetLastError());
+        e.pass = EIGH_PASS_DEFERRED;
+    }
+    launch_joint_eigh(e, gp->T, mT, w.egrid, false, st);
     GPMPC_HIP_CHECK(hipGetLastError());
-    // eigendecomposition root for the whole batch when a chain failed all jitter retries (or on request); the kernel
-    // returns at once when the flag is clear
-    if (mT > 1 && root_mode != GPMPC_ROOT_CHOLESKY) {
-        EighArgs e;
-        e.gp = a.gp;
-        e.Ns = Ns;
-        e.m = m;
-        e.z = z;
-        e.var_zero_thr = var_zero_thr;
-        e.beta = beta;
-        e.apply_clip = apply_clip;
-        e.mean = mean;
-        e.var = var;
-        e.y = y;
-        e.info = (int*)info;
-        e.Sall = sv_args.Sv;
-        e.S_ld = sv_args.Sv_ld;
-        e.S_cs = sv_args.Sv_cs;
-        e.any_fail = a.any_fail;
-        e.force = (root_mode == GPMPC_ROOT_EIGH);
-        e.ws = (double*)ws + w.e_off;
-        e.ws_slot_stride = w.estride;
-        e.root = root;
-        const bool global_G = (getenv("GPMPC_EIGH_GLOBAL_G") != nullptr);     // test knob: Gram matrix in HBM/L2
-        const int np = (mT + 1) & ~1;
-        e.lds_cap = global_G ? 0 : (np < EIGH_LDS_RANK ? np : EIGH_LDS_RANK);
-        e.tol_mult = 16.0;
-        e.gg_off = (long)mT * mT;
-        e.rlog_off = e.gg_off + 2 * eigh_packed(np);
-        e.pass = EIGH_PASS_ALL;
-        e.defer_rank = 0;
-        int* flags = a.any_fail;                        // [0] any_fail, [1] deferred chains, [2] max rank of this call; zeroed above
-        e.defer_count = flags + 1;
-        e.rank_hint = flags + 2;
-        e.defer_list = (int*)((double*)ws + w.d_off);
-        // Batches of low rank (the closed loop's points: 6..16 of 120) first run the NARROW form - LDS for ranks <= 32, 128
-        // registers: 16 chains resident per CU instead of 7 (the kernel is a chain of dependent LDS / L2 round trips per wave) - and
-        // the chains it defers (rank > 32) the full form, in a second launch over their list.  Which form a chain takes does not
-        // change its result.  The choice follows the largest rank of the LAST call whose counter has arrived (a heuristic for
-        // speed only): scattered points (ranks ~50) skip the narrow launch.
-        static int* hint_host = nullptr;
-        if (!hint_host) {
-            GPMPC_HIP_CHECK(hipHostMalloc((void**)&hint_host, sizeof(int), hipHostMallocDefault));
-            *hint_host = 0;
-        }
-        static const char* nenv = getenv("GPMPC_EIGH_NARROW");            // 0 / 1: force the choice (A/B timing)
-        const int forced = g_eigh_narrow_force >= 0 ? g_eigh_narrow_force : (nenv ? atoi(nenv) : -1);
-        const int last_rank = *(volatile int*)hint_host;
-        const bool narrow = !global_G && mT <= 128 && mT > EIGH_NARROW_RANK &&
-                            (forced >= 0 ? forced != 0 : last_rank <= EIGH_NARROW_RANK);
-        auto launch_eigh = [&](const EighArgs& ea, long grid, int wpe) {
-            const size_t lds = (size_t)eigh_lds_doubles(mT, ea.lds_cap) * sizeof(double);
-            const dim3 ge((unsigned)grid), be(64);
-            if (gp->T == 1) {
-                if (mT > 128) hipLaunchKernelGGL((joint_eigh_kernel<1, 4, GPMPC_EIGH_WPE>), ge, be, lds, st, ea);
-                else if (wpe == 4) hipLaunchKernelGGL((joint_eigh_kernel<1, 2, GPMPC_EIGH_NARROW_WPE>), ge, be, lds, st, ea);
-                else hipLaunchKernelGGL((joint_eigh_kernel<1, 2, GPMPC_EIGH_WPE>), ge, be, lds, st, ea);
-            } else {
-                if (mT > 128) hipLaunchKernelGGL((joint_eigh_kernel<3, 4, GPMPC_EIGH_WPE>), ge, be, lds, st, ea);
-                else if (wpe == 4) hipLaunchKernelGGL((joint_eigh_kernel<3, 2, GPMPC_EIGH_NARROW_WPE>), ge, be, lds, st, ea);
-                else hipLaunchKernelGGL((joint_eigh_kernel<3, 2, GPMPC_EIGH_WPE>), ge, be, lds, st, ea);
-            }
-        };
-        if (narrow) {
-            EighArgs en = e;
-            en.pass = EIGH_PASS_NARROW;
-            en.lds_cap = EIGH_NARROW_RANK;
-            en.defer_rank = EIGH_NARROW_RANK;
-            en.gg_off = 0;                              // (no chain of this launch takes the HBM/L2 form)
-            en.rlog_off = (long)mT * (EIGH_NARROW_RANK + EIGH_PB);
-            en.ws_slot_stride = eigh_narrow_slot_doubles((int)mT);
-            launch_eigh(en, w.egrid_narrow, 4);           // (4: "the narrow instantiation", whatever its occupancy)
-            GPMPC_HIP_CHECK(hipGetLastError());
-            e.pass = EIGH_PASS_DEFERRED;
-        }
-        launch_eigh(e, w.egrid, GPMPC_EIGH_WPE);
-        GPMPC_HIP_CHECK(hipGetLastError());
-        GPMPC_HIP_CHECK(hipMemcpyAsync(hint_host, e.rank_hint, sizeof(int), hipMemcpyDeviceToHost, st));
-        GPMPC_HIP_CHECK(hipGetLastError());
-    }
+    GPMPC_HIP_CHECK(hipMemcpyAsync(hint_host, e.rank_hint, sizeof(int), hipMemcpyDeviceToHost, st));
+    GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
+}
+
+// tests: the plan of a gpmpc_joint_sample_pending call (cache_rows 0: no caller cache; last_rank: the eigh rank hint) under the current
+// knobs, as one line: "path=P batches=B | kernel(modes) ... | eigh=none|full|narrow+deferred[,global_G] pending_written=0|1"
+int gpmpc_debug_joint_plan(const gpmpc_gp_desc_t* gp, int64_t Ns, int32_t n_h, int32_t n_ho, int32_t m, int32_t cache_rows,
+                           int32_t n_cached, int32_t pending, int32_t root_mode, int32_t last_rank, char* out, size_t out_len) {
+    if (int rc = check_gp(gp)) return rc;
+    if (!out || out_len < 1 || Ns < 1 || m < 1 || n_ho < 0 || n_h < 0 || cache_rows < 0 || n_cached < 0)
+        return fail(GPMPC_E_ARG, "gpmpc_debug_joint_plan: bad arguments");
+    const JointShape sh = joint_shape(gp, Ns, n_h, n_ho, m, cache_rows, n_cached, pending, root_mode, last_rank);
+    const JointPlan p = plan_joint_draw(sh, joint_knobs());
+    static const char* const kernels[] = {"joint_kernel", "joint_test_mfma", "joint_real_mfma", "joint_chol_mfma", "joint_tail_mfma"};
+    static const char* const eighs[] = {"none", "full", "narrow+deferred"};
+    std::string r = "path=" + std::to_string(p.path) + " batches=" + std::to_string((sh.nchains + p.batch - 1) / p.batch) + " |";
+    for (int i = 0; i < p.nsteps; ++i) {
+        const JointStep& s = p.steps[i];
+        std::string f;
+        if (s.kernel == JOINT_K_JOINT) f = std::string(joint_phase_name(s.phase)) + ",nrow=" + std::to_string(s.nrow);
+        else if (s.kernel == JOINT_K_TEST_MFMA || s.kernel == JOINT_K_REAL_MFMA) f = JOINT_MFMA_MODE_NAMES[s.mfma_mode];
+        if (s.pend_use) f += ",pend_use";
+        if (s.pend_write) f += ",pend_write";
+        if (s.abandon_root) f += ",abandon";
+        if (s.sv_cache) f += ",Sv=cache";
+        r += std::string(" ") + kernels[s.kernel] + "(" + (f[0] == ',' ? f.substr(1) : f) + ")";
+    }
+    r += std::string(" | eigh=") + eighs[p.eigh] + (p.eigh_global_G ? ",global_G" : "") + " pending_written=" + std::to_string(p.pending_written);
+    snprintf(out, out_len, "%s", r.c_str());
+    return r.size() < out_len ? GPMPC_OK : fail(GPMPC_E_ARG, "gpmpc_debug_joint_plan: buffer too small");
 }
 
 }  // extern "C"

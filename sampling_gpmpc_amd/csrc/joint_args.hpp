@@ -9,12 +9,14 @@ namespace gpmpc {
 enum : int {
     JOINT_PHASE_ALL = 0,      // one launch: factor rows, w row, test rows, mean, S, root, sample (the VALU path)
     JOINT_PHASE_FACTOR = 1,   // the hallucinated rows n_c .. n_ho - 1 of the factor only (into M and the factor cache)
-    JOINT_PHASE_TAIL = 2,     // root + sample only: S is in Sall, the mean in `mean` (written by joint_test_mfma_kernel)
+    JOINT_PHASE_TAIL = 2,     // root + sample only: S is in Sall, the mean in `mean` (written by joint_test_mfma_kernel); unreachable
     JOINT_PHASE_HEAD = 4,     // everything but the tail: factor rows, test rows, mean (into `mean`) and S (into Sall); the root and the
                               // sample follow in joint_tail_mfma_kernel (joint_chol.hip)
     JOINT_PHASE_CHOL = 3      // the new hallucinated rows against the NEW columns only: blocked Cholesky of the Schur complement
                               // joint_test_mfma_kernel (JOINT_MFMA_FACTOR) left in Sall (leading dimension n_ho - n_c); the rows'
-                              // entries against the old columns are already in the cache
+                              // entries against the old columns are already in the cache; unreachable
+                              // (TAIL and CHOL: the matrix-pipe path always has joint_tail_mfma_kernel / joint_chol_mfma_kernel - see
+                              // joint_plan.hpp; their code in joint_kernel stays because its register allocation sits at the cliff)
 };
 // JOINT_MFMA_TEST_TOP / _BOTTOM: the test rows of a conditioning set of more than JOINT_MFMA_SPLIT slots in two launches - TOP is
 // the test mode over the first JOINT_MFMA_SPLIT slots (a leading block of the factor is the factor of the leading block); it leaves

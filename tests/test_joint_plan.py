@@ -1,0 +1,115 @@
+"""CPU: the joint draw's launch plan (plan_joint_draw, csrc/joint_plan.hpp) through gpmpc_debug_joint_plan, for the closed loops'
+shapes and the paths the knobs select.  Each expected line is the kernel sequence the dispatcher launched for the same call before
+it was split into a plan and an executor (kernel trace of that build; one batch's steps, repeated `batches` times, then the eigh
+launches)."""
+import ctypes
+
+import pytest
+
+from sampling_gpmpc_amd import _lib
+
+# (g_ny, T, N_r): the car (45 real points, value + two derivatives), the pendulum (36 real points), the car's value-only model
+CAR, PEND, CAR_T1 = (3, 3, 45), (1, 3, 36), (3, 1, 45)
+
+# (desc, Ns, n_h, n_ho, m, cache_rows (0: no caller cache), n_cached, pending, root_mode, eigh rank hint, knob, expected line)
+PLANS = [
+    # car 1024 x 40, MPC step 0, k = 0
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma(abandon) | eigh=narrow+deferred pending_written=0'),
+    # k = 1
+    (CAR, 1024, 40, 120, 40, 512, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # k = 2
+    (CAR, 1024, 80, 240, 40, 512, 120, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # k = 3
+    (CAR, 1024, 120, 360, 40, 512, 240, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # MPC step 1, k = 0: 45 + 480 slots, TOP / BOTTOM
+    (CAR, 1024, 160, 480, 40, 512, 360, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST_TOP) joint_test_mfma(TEST_BOTTOM) joint_tail_mfma(abandon) | eigh=narrow+deferred pending_written=0'),
+    # car 4096 x 40, k = 0
+    (CAR, 4096, 0, 0, 40, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma(abandon) | eigh=narrow+deferred pending_written=0'),
+    # k = 1
+    (CAR, 4096, 40, 120, 40, 512, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # k = 2
+    (CAR, 4096, 80, 240, 40, 512, 120, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # k = 3
+    (CAR, 4096, 120, 360, 40, 512, 240, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # pendulum 1024 x 30, k = 0
+    (PEND, 1024, 0, 0, 30, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # k = 1: 90 slots, m T = 90 - the matrix pipe
+    (PEND, 1024, 30, 90, 30, 256, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # car H = 20, k = 1: 60 slots, narrow test block - the VALU path
+    (CAR, 1024, 20, 60, 20, 256, 0, 2, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=121) joint_tail_mfma(abandon) | eigh=narrow+deferred pending_written=0'),
+    # value-only model (T = 1): one launch
+    (CAR_T1, 1024, 0, 0, 40, 0, 0, 0, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(ALL,nrow=41) | eigh=narrow+deferred pending_written=0'),
+    # gpmpc_debug_eigh_narrow(0)
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 0, 100, 'narrow=0',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # gpmpc_debug_eigh_narrow(1)
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 0, 0, 'narrow=1',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma(abandon) | eigh=narrow+deferred pending_written=0'),
+    # eigh rank hint above the narrow cap
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 0, 100, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # gpmpc_debug_joint_real_kernel(0), k = 0
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 0, 100, 'real=0',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=121) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # gpmpc_debug_joint_real_kernel(0), k = 1
+    (CAR, 1024, 40, 120, 40, 384, 0, 2, 0, 100, 'real=0',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=full pending_written=1'),
+    # gpmpc_debug_joint_real_kernel(1), k = 1
+    (CAR, 1024, 40, 120, 40, 384, 0, 2, 0, 100, 'real=1',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(abandon,Sv=cache) | eigh=full pending_written=1'),
+    # GPMPC_ROOT_CHOLESKY: no eigh step
+    (CAR, 1024, 0, 0, 40, 0, 0, 0, 2, 100, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma() | eigh=none pending_written=0'),
+    # the VALU path pinned
+    (CAR, 1024, 40, 120, 40, 384, 0, 2, 0, 100, 'pin=1',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=241) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # no caller cache, nothing cached: three temporary-cache batches
+    (CAR, 1024, 40, 120, 40, 0, 0, 0, 0, 100, '',
+     'path=2 batches=3 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # no caller cache, more new rows than test slots: joint_kernel FACTOR first
+    (CAR, 1024, 80, 240, 40, 0, 0, 0, 0, 100, '',
+     'path=2 batches=3 | joint_kernel(FACTOR,nrow=240) joint_test_mfma(TEST) joint_tail_mfma(abandon) | eigh=full pending_written=0'),
+    # m T = 135 > 128: the VALU path in one launch
+    (CAR, 256, 45, 135, 45, 384, 0, 2, 0, 100, '',
+     'path=1 batches=1 | joint_kernel(ALL,nrow=271) | eigh=full pending_written=0'),
+]
+
+
+def _raw():
+    _lib.load()
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    raw.gpmpc_debug_joint_plan.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 8 + [ctypes.c_char_p, ctypes.c_size_t]
+    return raw
+
+
+@pytest.mark.parametrize("desc,Ns,n_h,n_ho,m,cache_rows,n_cached,pending,root_mode,rank,knob,expected", PLANS)
+def test_joint_plan(desc, Ns, n_h, n_ho, m, cache_rows, n_cached, pending, root_mode, rank, knob, expected):
+    raw = _raw()
+    g_ny, T, N_r = desc
+    d = _lib.make_gp_desc(g_ny, 2, T, N_r, False, [[2.0, 1.1]] * g_ny, [0.05] * g_ny, [2e-7] * T, 1e-20)
+    name, _, val = knob.partition("=")
+    setters = {"pin": (raw.gpmpc_joint_pin_path, 0), "narrow": (raw.gpmpc_debug_eigh_narrow, -1),
+               "real": (raw.gpmpc_debug_joint_real_kernel, -1)}
+    if name:
+        setters[name][0](int(val))
+    try:
+        buf = ctypes.create_string_buffer(512)
+        rc = raw.gpmpc_debug_joint_plan(ctypes.addressof(d), Ns, n_h, n_ho, m, cache_rows, n_cached, pending, root_mode, rank, buf, 512)
+    finally:
+        if name:
+            setters[name][0](setters[name][1])
+    assert rc == 0
+    assert buf.value.decode() == expected
