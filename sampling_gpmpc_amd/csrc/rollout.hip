@@ -14,7 +14,9 @@
 // The per-sample factor lives in LDS when it fits (FAC_LDS) and in an HBM workspace otherwise; both are laid out
 // column-major so that lane == row gives conflict-free LDS / coalesced HBM access.
 #include "gpmpc_host.hpp"
-#include "rollout_args.hpp"
+#include "rollout_plan.hpp"
+
+#include <algorithm>
 
 namespace gpmpc {
 
@@ -430,65 +432,108 @@ __global__ __launch_bounds__(64 * GPMPC_MAX_NY) void rollout_kernel(const Rollou
     if (threadIdx.x == 0) a.info[s] = s_info;
 }
 
-struct RolloutPlan {
-    int nh_max, rpl, lds_shared, lds_per_wave, linv_in_lds, max_points;
-    long chain_doubles;
-    bool fac_lds;
-    size_t lds_bytes;
-};
-
-static bool force_global_factor() {
-    const char* e = std::getenv("GPMPC_FORCE_GLOBAL_FACTOR");
-    return e && e[0] == '1';
-}
-
-static int plan_rollout(const gpmpc_gp_desc_t* gp, int nx, int mode, int hall_tasks, int H, RolloutPlan* rp,
-                        int n_h0 = 0, int n_v0 = 0, int state_slots = 0, int state_points = 0) {
-    const int n_r = observed_real_slots(gp);
-    const int T = gp->T;
-    int nh_max = (mode == GPMPC_MODE_RECONDITIONED) ? n_h0 * T + hall_tasks * (n_v0 + H - 1) : 0;
+// rollout_kernel's sizing: hallucinated slots per chain, LDS map, and whether the chain's factor stays in LDS
+RolloutLaunch rollout_generic_sizing(const RolloutShape& s, bool force_global) {
+    RolloutLaunch g = {};
+    const int n_r = s.n_r, T = s.T, H = s.H;
+    const int state_slots = s.state ? s.state_slots : 0;
+    g.kernel = GPMPC_KERNEL_GENERIC;
+    g.env_id = s.env_id;
+    g.T = T;
+    int nh_max = (s.mode == GPMPC_MODE_RECONDITIONED) ? s.n_h0 * T + s.hall_tasks * (s.n_v0 + H - 1) : 0;
     if (state_slots > 0) nh_max = state_slots;                    // the exported factor's leading dimension
     if (nh_max < 1) nh_max = 1;
     // LDS point list: with a kept / resumed state the points already in it are unknown on the host (up to state_points),
     // and every step of this call records its GP input whether or not the factor still has room for it
-    rp->max_points = (state_slots > 0) ? state_points + H : n_h0 + n_v0 + H;
-    rp->nh_max = nh_max;
-    rp->rpl = (nh_max + 63) / 64;
-    if (rp->rpl > 4) return fail(GPMPC_E_UNSUPPORTED, "rollout: more than 256 hallucinated label slots per chain");
-    if (rp->rpl == 3) rp->rpl = 4;
-    rp->chain_doubles = (long)n_r * nh_max + ((long)nh_max * (nh_max + 1)) / 2;
-    rp->lds_shared = nx * (H + 1) + rp->max_points * gp->D + 2 * GPMPC_MAX_NY;
-    rp->lds_shared = (rp->lds_shared + 1) & ~1;
+    g.max_points = (state_slots > 0) ? s.state_points + H : s.n_h0 + s.n_v0 + H;
+    g.nh_max = nh_max;
+    g.rpl = (nh_max + 63) / 64;
+    if (g.rpl > 4) {
+        g.status = GPMPC_E_UNSUPPORTED;
+        g.msg = "rollout: more than 256 hallucinated label slots per chain";
+        return g;
+    }
+    if (g.rpl == 3) g.rpl = 4;
+    g.ws_chain_stride = (long)n_r * nh_max + ((long)nh_max * (nh_max + 1)) / 2;
+    g.lds_shared = s.nx * (H + 1) + g.max_points * s.D + 2 * GPMPC_MAX_NY;
+    g.lds_shared = (g.lds_shared + 1) & ~1;
     // stage L_rr^-1 per wave when it leaves room for the rest (n_r <= ~60); otherwise it is read through L2
-    rp->linv_in_lds = ((size_t)gp->g_ny * n_r * n_r * sizeof(double) <= 64 * 1024) ? 1 : 0;
-    const int vec = 2 * T * n_r + 2 * nh_max + H * T + (rp->linv_in_lds ? n_r * n_r : 0) + n_r;
-    const long with_fac = vec + rp->chain_doubles;
-    const size_t bytes_fac = ((size_t)rp->lds_shared + (size_t)gp->g_ny * ((with_fac + 1) & ~1L)) * sizeof(double);
-    rp->fac_lds = (mode == GPMPC_MODE_RECONDITIONED) && bytes_fac <= (size_t)(160 * 1024 - 256) && !force_global_factor() &&
-                  state_slots == 0;                               // a kept factor state lives in the caller's buffer
-    rp->lds_per_wave = (int)(((rp->fac_lds ? with_fac : (long)vec) + 1) & ~1L);
-    rp->lds_bytes = ((size_t)rp->lds_shared + (size_t)gp->g_ny * rp->lds_per_wave) * sizeof(double);
-    if (rp->lds_bytes > (size_t)(160 * 1024 - 256)) return fail(GPMPC_E_UNSUPPORTED, "rollout: horizon too long for LDS vectors");
-    return GPMPC_OK;
+    g.linv_in_lds = ((size_t)s.g_ny * n_r * n_r * sizeof(double) <= 64 * 1024) ? 1 : 0;
+    const int vec = 2 * T * n_r + 2 * nh_max + H * T + (g.linv_in_lds ? n_r * n_r : 0) + n_r;
+    const long with_fac = vec + g.ws_chain_stride;
+    const size_t bytes_fac = ((size_t)g.lds_shared + (size_t)s.g_ny * ((with_fac + 1) & ~1L)) * sizeof(double);
+    g.fac_lds = (s.mode == GPMPC_MODE_RECONDITIONED) && bytes_fac <= (size_t)(160 * 1024 - 256) && !force_global &&
+                state_slots == 0;                                 // a kept factor state lives in the caller's buffer
+    g.lds_per_wave = (int)(((g.fac_lds ? with_fac : (long)vec) + 1) & ~1L);
+    g.lds_bytes = ((size_t)g.lds_shared + (size_t)s.g_ny * g.lds_per_wave) * sizeof(double);
+    if (g.lds_bytes > (size_t)(160 * 1024 - 256)) {
+        g.status = GPMPC_E_UNSUPPORTED;
+        g.msg = "rollout: horizon too long for LDS vectors";
+    }
+    g.grid = s.Ns;                                                // one workgroup per sample, one wave per output
+    g.block = 64 * s.g_ny;
+    // the factor lives in the workspace unless it stays in LDS or in a kept state
+    if (s.mode == GPMPC_MODE_RECONDITIONED && !g.fac_lds && !s.state)
+        g.ws_bytes = (size_t)s.Ns * s.g_ny * g.ws_chain_stride * sizeof(double);
+    return g;
 }
 
 template <int T, int RPL>
-static int launch_rollout(const RolloutArgs& args, const RolloutPlan& rp, int g_ny, hipStream_t stream) {
-    const dim3 grid((unsigned)args.Ns), block(64 * g_ny);
-    if (rp.fac_lds) {
+static int launch_rollout(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t stream) {
+    const dim3 grid((unsigned)p.grid), block(p.block);
+    if (p.fac_lds) {
         auto k = rollout_kernel<T, RPL, true>;
-        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rp.lds_bytes));
-        hipLaunchKernelGGL(k, grid, block, rp.lds_bytes, stream, args);
+        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+        hipLaunchKernelGGL(k, grid, block, p.lds_bytes, stream, args);
     } else {
         auto k = rollout_kernel<T, RPL, false>;
-        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rp.lds_bytes));
-        hipLaunchKernelGGL(k, grid, block, rp.lds_bytes, stream, args);
+        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+        hipLaunchKernelGGL(k, grid, block, p.lds_bytes, stream, args);
     }
     GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
 }
 
-int g_rollout_pin = GPMPC_KERNEL_AUTO;
+int rollout_generic_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    if (p.T == 1) {
+        if (p.rpl == 1) return launch_rollout<1, 1>(args, p, st);
+        if (p.rpl == 2) return launch_rollout<1, 2>(args, p, st);
+        return launch_rollout<1, 4>(args, p, st);
+    } else if (p.T == 3) {
+        if (p.rpl == 1) return launch_rollout<3, 1>(args, p, st);
+        if (p.rpl == 2) return launch_rollout<3, 2>(args, p, st);
+        return launch_rollout<3, 4>(args, p, st);
+    }
+    return fail(GPMPC_E_UNSUPPORTED, "rollout: only T = 1 and T = 3 (D = 2) are instantiated");
+}
+
+static int g_rollout_pin = GPMPC_KERNEL_AUTO;      // gpmpc_rollout_pin_kernel
+
+// a knob set to '1' / '0': 1 / -1, else 0
+static int knob(const char* name) {
+    const char* e = std::getenv(name);
+    return !e ? 0 : (e[0] == '1' ? 1 : (e[0] == '0' ? -1 : 0));
+}
+
+// every knob of the rollout's kernel choice, read on every call (the tests change them between calls); precedence: RolloutKnobs
+static RolloutKnobs rollout_knobs() {
+    RolloutKnobs k;
+    k.pin = g_rollout_pin;
+    k.one = knob("GPMPC_ROLLOUT_ONE");
+    k.tiles = knob("GPMPC_ROLLOUT_TILES");
+    k.disable_fast = knob("GPMPC_DISABLE_FAST_ROLLOUT") > 0;
+    k.disable_grid_root = knob("GPMPC_DISABLE_GRID_ROOT") > 0;
+    k.force_global_factor = knob("GPMPC_FORCE_GLOBAL_FACTOR") > 0;
+    return k;
+}
+
+// env NULL: not known (the workspace queries size for GPMPC_MAX_NX state components)
+static RolloutShape rollout_shape(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int64_t Ns, int H,
+                                  int n_h0 = 0, int n_v0 = 0, bool state = false, int state_slots = 0, int state_points = 0) {
+    return RolloutShape{gp->T, gp->D, gp->N_r, observed_real_slots(gp), gp->real_has_grad, gp->g_ny, gp->grid_n0, gp->grid_n1,
+                        env ? env->env_id : -1, env ? env->nx : GPMPC_MAX_NX, mode, (mode == GPMPC_MODE_INDEPENDENT) ? gp->T : hall_tasks,
+                        Ns, H, n_h0, n_v0, state, state ? state_slots : 0, state_points};
+}
 
 }  // namespace gpmpc
 
@@ -501,23 +546,53 @@ static int g_last_rollout_path = -1;     // 0 generic, 1 tuned re-conditioned (r
 int gpmpc_debug_last_rollout_path(void) { return g_last_rollout_path; }
 int gpmpc_rollout_last_kernel(void) { return g_last_rollout_path; }
 // the kernel an (unseeded) launch of this shape and size takes under the current pin / environment
-static int select_rollout_kernel(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H, int64_t Ns) {
-    if (rollout_one_eligible(gp, env, mode, hall_tasks, H, Ns)) return GPMPC_KERNEL_ONE;
-    if (rollout_tiles_eligible(gp, env, mode, hall_tasks, H, Ns)) return GPMPC_KERNEL_TILES;
-    if (rollout_fast_eligible(gp, env, mode, hall_tasks, H)) return GPMPC_KERNEL_FAST;
-    if (rollout_indep_eligible(gp, env, mode)) return GPMPC_KERNEL_INDEP;
-    return GPMPC_KERNEL_GENERIC;
-}
 int gpmpc_rollout_kernel_for(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int32_t mode, int32_t hall_tasks, int64_t Ns,
                              int32_t H) {
     if (check_gp(gp) != GPMPC_OK || check_env(gp, env) != GPMPC_OK) return GPMPC_KERNEL_AUTO;
-    if (mode == GPMPC_MODE_INDEPENDENT) hall_tasks = gp->T;
-    return select_rollout_kernel(gp, env, mode, hall_tasks, H, Ns);
+    return plan_rollout_launch(rollout_shape(gp, env, mode, hall_tasks, Ns, H), rollout_knobs()).kernel;
 }
 int gpmpc_rollout_pin_kernel(int32_t kernel) {
     const int prev = gpmpc::g_rollout_pin;
     gpmpc::g_rollout_pin = (kernel >= GPMPC_KERNEL_GENERIC && kernel <= GPMPC_KERNEL_ONE) ? kernel : GPMPC_KERNEL_AUTO;
     return prev;
+}
+
+// the plan of a gpmpc_rollout_seeded call of this shape (state_slots > 0: with a factor state) as one line
+int gpmpc_debug_rollout_plan(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int32_t mode, int32_t hall_tasks, int64_t Ns,
+                             int32_t H, int32_t n_h0, int32_t n_v0, int32_t state_slots, int32_t state_points, char* out, size_t out_len) {
+    if (int rc = check_gp(gp)) return rc;
+    if (int rc = check_env(gp, env)) return rc;
+    if (!out || out_len < 1 || Ns < 1 || H < 1 || n_h0 < 0 || n_v0 < 0 || state_slots < 0)
+        return fail(GPMPC_E_ARG, "gpmpc_debug_rollout_plan: bad arguments");
+    const RolloutLaunch p = plan_rollout_launch(
+        rollout_shape(gp, env, mode, hall_tasks, Ns, H, n_h0, n_v0, state_slots > 0, state_slots, state_points), rollout_knobs());
+    const char* env_name = (p.env_id == GPMPC_ENV_PENDULUM1D) ? "pendulum" : "car";
+    char k[128];
+    if (p.status != GPMPC_OK) {
+        snprintf(out, out_len, "error=%d %s", p.status, p.msg);
+        return GPMPC_OK;
+    }
+    switch (p.kernel) {
+        case GPMPC_KERNEL_ONE: snprintf(k, sizeof k, "rollout_one_kernel<N0=4,ENV=pendulum>"); break;
+        case GPMPC_KERNEL_TILES:
+            snprintf(k, sizeof k, "rollout_tiles_kernel<N0=%d,N1=9,ENV=%s,NT=%d,SEED=%d>", p.n0, env_name, p.nt, p.seed);
+            break;
+        case GPMPC_KERNEL_FAST:
+            snprintf(k, sizeof k, "rollout_fast_kernel<T=3,NR=%d,G_NY=%d,ENV=%s,LHH_LDS=%d,GRID=%d>", gp->N_r, gp->g_ny, env_name,
+                     p.lhh_lds, p.grid_root);
+            break;
+        case GPMPC_KERNEL_INDEP:
+            snprintf(k, sizeof k, "rollout_indep%s_kernel<ENV=%s,N0=%d,N1=%d,G_NY=%d>", p.grid_root ? "_grid" : "", env_name, gp->grid_n0,
+                     gp->grid_n1, gp->g_ny);
+            break;
+        default: snprintf(k, sizeof k, "rollout_kernel<T=%d,RPL=%d,FAC_LDS=%d>", p.T, p.rpl, p.fac_lds);
+    }
+    const int n = snprintf(out, out_len,
+                           "%s grid=%ld block=%d lds=%zu ws=%zu zero=%d | nh_max=%d lds_shared=%d lds_per_wave=%d linv_in_lds=%d "
+                           "ws_chain_stride=%ld max_points=%d",
+                           k, p.grid, p.block, p.lds_bytes, p.ws_bytes, p.zero_bytes > 0, p.nh_max, p.lds_shared, p.lds_per_wave,
+                           p.linv_in_lds, p.ws_chain_stride, p.max_points);
+    return (size_t)n < out_len ? GPMPC_OK : fail(GPMPC_E_ARG, "gpmpc_debug_rollout_plan: buffer too small");
 }
 
 int gpmpc_debug_read_phases(long long* out /*[host] 16*/) {
@@ -528,16 +603,15 @@ int gpmpc_debug_read_phases(long long* out /*[host] 16*/) {
 size_t gpmpc_rollout_workspace_bytes(const gpmpc_gp_desc_t* gp, int32_t mode, int32_t hall_tasks, int64_t Ns,
                                      int32_t H) {
     if (check_gp(gp) != GPMPC_OK) return 0;
-    RolloutPlan rp;
-    if (plan_rollout(gp, GPMPC_MAX_NX, mode, hall_tasks, H, &rp) != GPMPC_OK) return 0;
+    const RolloutShape s = rollout_shape(gp, nullptr, mode, hall_tasks, Ns, H);
+    const RolloutLaunch g = rollout_generic_sizing(s, false);
+    if (g.status != GPMPC_OK) return 0;
     if (mode != GPMPC_MODE_RECONDITIONED) return 256;
-    size_t need = align_up((size_t)Ns * gp->g_ny * rp.chain_doubles * sizeof(double), 256) + 2048;   // >= the tuned path's need (its zero page included)
+    size_t need = align_up((size_t)Ns * gp->g_ny * g.ws_chain_stride * sizeof(double), 256) + 2048;   // >= the tuned path's need (its zero page included)
     // the tiled throughput kernel keeps the whole tile matrix of a wave's four chains in the workspace (whichever env /
     // size it ends up serving: the query does not know the env, so the larger of the two layouts is reported)
-    if (gp->T == 3 && (hall_tasks == 3 || hall_tasks == 1) && 3 * (H - 1) <= 192 && H >= 2) {
-        const size_t tl = rollout_tiles_workspace_bytes(gp, Ns, H) + 256;
-        need = tl > need ? tl : need;
-    }
+    const RolloutLaunch t = rollout_tiles_sizing(s, g);
+    if (gp->T == 3 && (hall_tasks == 3 || hall_tasks == 1) && H >= 2 && t.nt) need = std::max(need, t.ws_bytes + 256);
     return need;
 }
 
@@ -545,16 +619,14 @@ size_t gpmpc_rollout_seeded_workspace_bytes(const gpmpc_gp_desc_t* gp, int32_t m
                                             int32_t H, int32_t n_h0, int32_t n_v0) {
     if (check_gp(gp) != GPMPC_OK || n_h0 < 0 || n_v0 < 0) return 0;
     if (mode != GPMPC_MODE_RECONDITIONED) return 256;
-    RolloutPlan rp;
-    if (plan_rollout(gp, GPMPC_MAX_NX, mode, hall_tasks, H, &rp, n_h0, n_v0) != GPMPC_OK) return 0;
-    size_t seeded = align_up((size_t)Ns * gp->g_ny * rp.chain_doubles * sizeof(double), 256) + 2048;
+    const RolloutShape s = rollout_shape(gp, nullptr, mode, hall_tasks, Ns, H, n_h0, n_v0);
+    const RolloutLaunch g = rollout_generic_sizing(s, false);
+    if (g.status != GPMPC_OK) return 0;
+    size_t seeded = align_up((size_t)Ns * gp->g_ny * g.ws_chain_stride * sizeof(double), 256) + 2048;
     // the tiled kernel, should the call be routed there (three row slots per point, value-only points included)
-    if (gp->T == 3 && 3 * (n_h0 + n_v0 + H - 1) <= 192) {
-        const size_t tl = rollout_tiles_workspace_bytes(gp, Ns, H, n_h0 + n_v0) + 256;
-        seeded = tl > seeded ? tl : seeded;
-    }
-    const size_t plain = gpmpc_rollout_workspace_bytes(gp, mode, hall_tasks, Ns, H);
-    return seeded > plain ? seeded : plain;
+    const RolloutLaunch t = rollout_tiles_sizing(s, g);
+    if (gp->T == 3 && t.nt) seeded = std::max(seeded, t.ws_bytes + 256);
+    return std::max(seeded, gpmpc_rollout_workspace_bytes(gp, mode, hall_tasks, Ns, H));
 }
 
 static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
@@ -571,7 +643,6 @@ static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, 
     if (mode != GPMPC_MODE_INDEPENDENT && mode != GPMPC_MODE_RECONDITIONED) return fail(GPMPC_E_ARG, "bad mode");
     if (mode == GPMPC_MODE_RECONDITIONED && !(hall_tasks == gp->T || hall_tasks == 1))
         return fail(GPMPC_E_ARG, "hall_tasks must be T or 1");
-    if (mode == GPMPC_MODE_INDEPENDENT) hall_tasks = gp->T;
     const bool seeded = (n_h0 > 0) || (n_v0 > 0) || state != nullptr;
     if (n_h0 < 0 || (n_h0 > 0 && (!X_h0 || !Y_h0))) return fail(GPMPC_E_ARG, "gpmpc_rollout_seeded: seed points missing");
     if (n_v0 < 0 || (n_v0 > 0 && (!X_v0 || !Y_v0))) return fail(GPMPC_E_ARG, "gpmpc_rollout_seeded: value-only seed points missing");
@@ -582,8 +653,13 @@ static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, 
         if (state_slots < n_h0 * gp->T + hall_tasks * (n_v0 + H) || state_points < n_h0 + n_v0 + H)
             return fail(GPMPC_E_ARG, "gpmpc_rollout_seeded: factor state too small for the seeds plus H appended points");
     }
-    RolloutPlan rp;
-    if (int rc = plan_rollout(gp, env->nx, mode, hall_tasks, H, &rp, n_h0, n_v0, state ? state_slots : 0, state_points)) return rc;
+    const RolloutShape sh = rollout_shape(gp, env, mode, hall_tasks, Ns, H, n_h0, n_v0, state != nullptr, state_slots, state_points);
+    const RolloutLaunch p = plan_rollout_launch(sh, rollout_knobs());
+    if (p.status != GPMPC_OK) return fail(p.status, p.msg);
+    hipStream_t st = (hipStream_t)stream;
+    if (p.ws_bytes && (!ws || ws_bytes < p.ws_bytes)) return fail(GPMPC_E_WORKSPACE, "gpmpc_rollout: workspace too small");
+    if (p.zero_bytes) GPMPC_HIP_CHECK(hipMemsetAsync(ws, 0, p.zero_bytes, st));      // the factor itself is not cleared
+    g_last_rollout_path = p.kernel;
 
     RolloutArgs args;
     args.gp = make_gp_params(gp);
@@ -591,7 +667,7 @@ static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, 
     args.plan = (const double*)plan;
     args.X_r = X_r;
     args.mode = mode;
-    args.hall_tasks = hall_tasks;
+    args.hall_tasks = sh.hall_tasks;
     args.var_zero_thr = var_zero_thr;
     args.beta = beta;
     args.Ns = Ns;
@@ -606,11 +682,11 @@ static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, 
     args.Xi = Xi;
     args.info = (int*)info;
     args.ws = (double*)ws;
-    args.ws_chain_stride = rp.chain_doubles;
-    args.nh_max = rp.nh_max;
-    args.lds_shared = rp.lds_shared;
-    args.lds_per_wave = rp.lds_per_wave;
-    args.linv_in_lds = rp.linv_in_lds;
+    args.ws_chain_stride = p.ws_chain_stride;
+    args.nh_max = p.nh_max;
+    args.lds_shared = p.lds_shared;
+    args.lds_per_wave = p.lds_per_wave;
+    args.linv_in_lds = p.linv_in_lds;
     args.X_h0 = X_h0;
     args.Y_h0 = Y_h0;
     args.n_h0 = n_h0;
@@ -621,35 +697,14 @@ static int rollout_impl(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, 
     args.state_points = state_points;
     args.state_stride = state ? state_sample_doubles(gp->g_ny, observed_real_slots(gp), state_slots, state_points, gp->D) : 0;
     args.resume = resume;
-    args.max_points = rp.max_points;
-    hipStream_t st = (hipStream_t)stream;
-    // seed points without a kept factor state are conditioning-only passes of the tiled kernel's step body; a kept / resumed
-    // state is the generic kernel's own factor layout
-    int kernel = GPMPC_KERNEL_GENERIC;
-    if (!seeded) kernel = select_rollout_kernel(gp, env, mode, hall_tasks, H, Ns);
-    else if (!state && rollout_tiles_eligible(gp, env, mode, hall_tasks, H, Ns, n_h0, n_v0)) kernel = GPMPC_KERNEL_TILES;
-    // the generic kernel's factor lives in the workspace (the tiled / fast kernels check their own needs in their launchers; the
-    // one-chain-per-wave MFMA kernel keeps the factor in registers and needs none)
-    if (kernel == GPMPC_KERNEL_GENERIC && mode == GPMPC_MODE_RECONDITIONED && !rp.fac_lds && !state) {
-        const size_t need = (size_t)Ns * gp->g_ny * rp.chain_doubles * sizeof(double);
-        if (!ws || ws_bytes < need) return fail(GPMPC_E_WORKSPACE, "gpmpc_rollout: workspace too small");
+    args.max_points = p.max_points;
+    switch (p.kernel) {
+        case GPMPC_KERNEL_ONE: return rollout_one_launch(args, p, st);
+        case GPMPC_KERNEL_TILES: return rollout_tiles_launch(args, p, st);
+        case GPMPC_KERNEL_FAST: return rollout_fast_launch(args, p, st);
+        case GPMPC_KERNEL_INDEP: return rollout_indep_launch(args, p, st);
+        default: return rollout_generic_launch(args, p, st);
     }
-    g_last_rollout_path = kernel;
-    if (kernel == GPMPC_KERNEL_ONE) return rollout_one_launch(gp, env, args, st);
-    if (kernel == GPMPC_KERNEL_TILES) return rollout_tiles_launch(gp, env, args, ws, ws_bytes, st);
-    if (kernel == GPMPC_KERNEL_FAST) return rollout_fast_launch(gp, env, args, ws, ws_bytes, st);
-    if (kernel == GPMPC_KERNEL_INDEP) return rollout_indep_launch(gp, env, args, st);
-    const int T = gp->T;
-    if (T == 1) {
-        if (rp.rpl == 1) return launch_rollout<1, 1>(args, rp, gp->g_ny, st);
-        if (rp.rpl == 2) return launch_rollout<1, 2>(args, rp, gp->g_ny, st);
-        return launch_rollout<1, 4>(args, rp, gp->g_ny, st);
-    } else if (T == 3) {
-        if (rp.rpl == 1) return launch_rollout<3, 1>(args, rp, gp->g_ny, st);
-        if (rp.rpl == 2) return launch_rollout<3, 2>(args, rp, gp->g_ny, st);
-        return launch_rollout<3, 4>(args, rp, gp->g_ny, st);
-    }
-    return fail(GPMPC_E_UNSUPPORTED, "rollout: only T = 1 and T = 3 (D = 2) are instantiated");
 }
 
 int gpmpc_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,

@@ -53,28 +53,4 @@ __host__ __device__ __forceinline__ long state_sample_doubles(int g_ny, int n_r,
 // packed lower-triangular, column-major: element (row, col) at col_ofs(col) + row - col, rows col..nh_max-1
 __host__ __device__ __forceinline__ long col_ofs(int p, int nh_max) { return (long)p * nh_max - ((long)p * (p - 1)) / 2; }
 
-// gpmpc_rollout_pin_kernel (rollout.hip): GPMPC_KERNEL_AUTO or the kernel every launch must take where its shape allows
-extern int g_rollout_pin;
-
-// tuned path (rollout_fast.hip)
-bool rollout_fast_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H);
-size_t rollout_fast_workspace_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int H);
-int rollout_fast_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, void* ws,
-                        size_t ws_bytes, hipStream_t st);
-
-// throughput path: four chains per wave, forward substitution on the FP64 matrix pipe (rollout_tiles.hip)
-bool rollout_tiles_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H, int64_t Ns,
-                            int n_h0 = 0, int n_v0 = 0);
-size_t rollout_tiles_workspace_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int H, int n_pre = 0);
-int rollout_tiles_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, void* ws, size_t ws_bytes,
-                         hipStream_t st);
-
-// latency path: one chain per wave, the chain's factor in AGPR panels, forward substitution on the FP64 matrix pipe (rollout_one.hip)
-bool rollout_one_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H, int64_t Ns);
-int rollout_one_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, hipStream_t st);
-
-// mode-I thread-per-sample path (rollout_indep.hip)
-bool rollout_indep_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode);
-int rollout_indep_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, hipStream_t st);
-
 }  // namespace gpmpc

@@ -26,7 +26,7 @@
 //   * appending a row is one coalesced 8-byte store per lane (lane p owns the new row's entry in column p);
 //   * the storage is zero-initialised, so not-yet-appended rows read as zero.
 #include "gpmpc_host.hpp"
-#include "rollout_args.hpp"
+#include "rollout_plan.hpp"
 
 #include <type_traits>
 
@@ -1023,113 +1023,71 @@ __global__ __launch_bounds__(GPMPC_FAST_MAXTHREADS, 1) void rollout_fast_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host side: eligibility + launch
+// host side: sizing + launch.  Instantiated for T = 3 with value-only real labels on the pendulum's 36-point and the car's
+// 45-point grid, every appended row observed with T tasks, 3 (H - 1) <= 128
 // ---------------------------------------------------------------------------------------------------------------
-struct FastPlan {
-    int spw, waves, lds_shared, lds_per_wave;
-    bool lhh_lds;
-    size_t lds_bytes;
-    long chain_doubles;
-};
-
-static bool fast_disabled() {
-    if (g_rollout_pin != GPMPC_KERNEL_AUTO) return g_rollout_pin != GPMPC_KERNEL_FAST;
-    const char* e = std::getenv("GPMPC_DISABLE_FAST_ROLLOUT");
-    return e && e[0] == '1';
-}
-
-bool rollout_fast_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H) {
-    if (fast_disabled()) return false;
-    if (mode != GPMPC_MODE_RECONDITIONED || gp->T != 3 || gp->D != 2 || hall_tasks != 3 || gp->real_has_grad) return false;
-    if (!(gp->N_r == 36 || gp->N_r == 45)) return false;
-    if (3 * (H - 1) > 128 || H < 2) return false;
-    if (env->env_id == GPMPC_ENV_PENDULUM1D) return gp->g_ny == 1 && gp->N_r == 36;
-    if (env->env_id == GPMPC_ENV_CAR_RESIDUAL) return gp->g_ny == 3 && gp->N_r == 45;
-    return false;
-}
-
-static bool fast_grid_root(const gpmpc_gp_desc_t* gp) {
-    const char* eg = std::getenv("GPMPC_DISABLE_GRID_ROOT");
-    return !(eg && eg[0] == '1') && gp->grid_n1 == 9 && gp->grid_n0 * 9 == gp->N_r &&
-           plan_has_grid_root(gp->grid_n0, gp->grid_n1, gp->real_has_grad);
-}
-
-static void fast_plan(const gpmpc_gp_desc_t* gp, int nx, int H, bool force_global, FastPlan* fp) {
-    const int NR = gp->N_r, T = 3, G = gp->g_ny;
-    (void)nx;
-    (void)H;
+RolloutLaunch rollout_fast_sizing(const RolloutShape& s, const RolloutLaunch& g, bool grid_root, bool force_global) {
+    RolloutLaunch p = g;
+    p.kernel = GPMPC_KERNEL_AUTO;
+    const int NR = s.N_r, T = 3, G = s.g_ny, H = s.H;
+    if (s.mode != GPMPC_MODE_RECONDITIONED || s.T != 3 || s.D != 2 || s.hall_tasks != 3 || s.real_has_grad) return p;
+    if (3 * (H - 1) > 128 || H < 2) return p;
+    if (!(s.env_id == GPMPC_ENV_PENDULUM1D && G == 1 && NR == 36) && !(s.env_id == GPMPC_ENV_CAR_RESIDUAL && G == 3 && NR == 45))
+        return p;
+    p.kernel = GPMPC_KERNEL_FAST;
+    // the grid root of the plan (separable real-data kernel row) when the real inputs are the reference's tensor grid
+    p.grid_root = grid_root && s.grid_n1 == 9 && s.grid_n0 * 9 == NR && plan_has_grid_root(s.grid_n0, s.grid_n1, s.real_has_grad);
     const int NRP = (NR + 1) & ~1;
     const int NRS = ((NRP / 2) & 1) ? NRP : NRP + 2;
     const int nh_max = 3 * (H - 1);
     const int nb1 = nh_max > 64 ? nh_max - 64 : 0;
-    fp->chain_doubles = lhh_doubles(nh_max, kRingLds);
     const long vec = (long)T * NRP + (long)nb1 * NRS;
     const size_t budget = 160 * 1024 - 64;
-    const int max_spw = (G == 1) ? 4 : 1;
-    const bool grid = fast_grid_root(gp);                         // the grid root keeps no L_rr^-1 in LDS
-    auto shared_doubles = [&](int spw) { return ((grid ? 0 : G * NR * NRS) + ((G > 1) ? spw * 2 * G : 0) + 1) & ~1; };
-    // L_hh stays in LDS only if that still leaves one wave on every SIMD (max_spw samples per workgroup): with fewer
+    const int spw = (G == 1) ? 4 : 1;                             // samples per workgroup
+    // the grid root keeps no L_rr^-1 in LDS
+    p.lds_shared = ((p.grid_root ? 0 : G * NR * NRS) + ((G > 1) ? spw * 2 * G : 0) + 1) & ~1;
+    // L_hh stays in LDS only if that still leaves one wave on every SIMD (spw samples per workgroup): with fewer
     // resident samples the HBM/L2-workspace variant at full occupancy is faster (tools/horizon_sweep.py, Ns=4096:
     // H=31 1.07 vs 1.25 ms, H=43 1.9 vs 5.3 ms; at H<=30, where 4 samples fit, LDS wins 0.82 vs 0.95 ms)
-    fp->lhh_lds = false;
-    fp->spw = max_spw;
-    if (!force_global) {
-        const long per = vec + fp->chain_doubles;
-        const size_t bytes = ((size_t)shared_doubles(max_spw) + (size_t)max_spw * G * ((per + 1) & ~1L)) * sizeof(double);
-        fp->lhh_lds = bytes <= budget;
+    const long per_lds = vec + lhh_doubles(nh_max, kRingLds);
+    p.lhh_lds = !force_global && ((size_t)p.lds_shared + (size_t)spw * G * ((per_lds + 1) & ~1L)) * sizeof(double) <= budget;
+    p.ws_chain_stride = lhh_doubles(nh_max, p.lhh_lds ? kRingLds : kRingGlobal);
+    p.ws_bytes = p.zero_bytes = 0;
+    if (!p.lhh_lds) {
+        p.zero_bytes = kZeroPage * sizeof(double);                // the zero page (1 KB) ahead of the factors
+        p.ws_bytes = p.zero_bytes + (size_t)s.Ns * G * (size_t)p.ws_chain_stride * sizeof(double);
     }
-    if (!fp->lhh_lds) fp->chain_doubles = lhh_doubles(nh_max, kRingGlobal);
-    fp->waves = fp->spw * G;
-    fp->lds_shared = shared_doubles(fp->spw);
-    const long per = vec + (fp->lhh_lds ? fp->chain_doubles : 48);          // 48: diagonal-segment scratch (dgs)
-    fp->lds_per_wave = (int)((per + 1) & ~1L);
-    fp->lds_bytes = ((size_t)fp->lds_shared + (size_t)fp->waves * fp->lds_per_wave) * sizeof(double);
-}
-
-size_t rollout_fast_workspace_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int H) {
-    return ((size_t)kZeroPage + (size_t)Ns * gp->g_ny * (size_t)lhh_doubles(3 * (H - 1), kRingGlobal)) * sizeof(double);
+    p.grid = (s.Ns + spw - 1) / spw;
+    p.block = 64 * spw * G;
+    p.nh_max = nh_max;
+    p.lds_per_wave = (int)((vec + (p.lhh_lds ? p.ws_chain_stride : 48) + 1) & ~1L);      // 48: diagonal-segment scratch (dgs)
+    p.lds_bytes = ((size_t)p.lds_shared + (size_t)spw * G * p.lds_per_wave) * sizeof(double);
+    p.linv_in_lds = 1;
+    return p;
 }
 
 template <int NR, int G_NY, int ENV, bool GRID>
-static int launch_fast(RolloutArgs& args, const FastPlan& fp, hipStream_t st) {
-    const long nblk = (args.Ns + fp.spw - 1) / fp.spw;
-    const dim3 grid((unsigned)nblk), block(64 * fp.waves);
-    if (fp.lhh_lds) {
+static int launch_fast(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    const dim3 grid((unsigned)p.grid), block(p.block);
+    if (p.lhh_lds) {
         auto k = rollout_fast_kernel<3, NR, G_NY, ENV, true, GRID>;
-        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes));
-        hipLaunchKernelGGL(k, grid, block, fp.lds_bytes, st, args);
+        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+        hipLaunchKernelGGL(k, grid, block, p.lds_bytes, st, args);
     } else {
         auto k = rollout_fast_kernel<3, NR, G_NY, ENV, false, GRID>;
-        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes));
-        hipLaunchKernelGGL(k, grid, block, fp.lds_bytes, st, args);
+        GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+        hipLaunchKernelGGL(k, grid, block, p.lds_bytes, st, args);
     }
     GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
 }
 
-int rollout_fast_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, void* ws,
-                        size_t ws_bytes, hipStream_t st) {
-    const char* e = std::getenv("GPMPC_FORCE_GLOBAL_FACTOR");
-    const bool force_global = e && e[0] == '1';
-    FastPlan fp;
-    fast_plan(gp, env->nx, args.H, force_global, &fp);
-    args.nh_max = 3 * (args.H - 1);
-    args.lds_shared = fp.lds_shared;
-    args.lds_per_wave = fp.lds_per_wave;
-    args.linv_in_lds = 1;
-    args.ws_chain_stride = fp.chain_doubles;
-    if (!fp.lhh_lds) {
-        if (!ws || ws_bytes < rollout_fast_workspace_bytes(gp, args.Ns, args.H))
-            return fail(GPMPC_E_WORKSPACE, "gpmpc_rollout: workspace too small");
-        GPMPC_HIP_CHECK(hipMemsetAsync(ws, 0, kZeroPage * sizeof(double), st));      // the zero page (1 KB); the factor itself is not cleared
-    }
-    // the grid root of the plan (separable real-data kernel row) when the real inputs are the reference's tensor grid
-    const bool grid = fast_grid_root(gp);
-    if (env->env_id == GPMPC_ENV_PENDULUM1D)
-        return grid ? launch_fast<36, 1, GPMPC_ENV_PENDULUM1D, true>(args, fp, st)
-                    : launch_fast<36, 1, GPMPC_ENV_PENDULUM1D, false>(args, fp, st);
-    return grid ? launch_fast<45, 3, GPMPC_ENV_CAR_RESIDUAL, true>(args, fp, st)
-                : launch_fast<45, 3, GPMPC_ENV_CAR_RESIDUAL, false>(args, fp, st);
+int rollout_fast_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    if (p.env_id == GPMPC_ENV_PENDULUM1D)
+        return p.grid_root ? launch_fast<36, 1, GPMPC_ENV_PENDULUM1D, true>(args, p, st)
+                           : launch_fast<36, 1, GPMPC_ENV_PENDULUM1D, false>(args, p, st);
+    return p.grid_root ? launch_fast<45, 3, GPMPC_ENV_CAR_RESIDUAL, true>(args, p, st)
+                       : launch_fast<45, 3, GPMPC_ENV_CAR_RESIDUAL, false>(args, p, st);
 }
 
 }  // namespace gpmpc

@@ -12,7 +12,7 @@
 //   * mu = acc . w_r, S = os - acc . acc, y = mu + sqrt(S) z (1x1 root: plain sqrt, App. A.7), floor, clip, env step.
 // Algorithmic work per trajectory-step (car): 3 * (1035 + 90) FMA + 42 exp; 112 B of unavoidable HBM traffic.
 #include "gpmpc_host.hpp"
-#include "rollout_args.hpp"
+#include "rollout_plan.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -482,30 +482,33 @@ __global__ __launch_bounds__(64 * G_NY) void rollout_indep_grid_kernel(const Rol
 }
 
 
-bool rollout_indep_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode) {
-    if (g_rollout_pin == GPMPC_KERNEL_GENERIC) return false;    // (the other pins name mode-R kernels: mode I is unaffected)
-    const char* e = std::getenv("GPMPC_DISABLE_FAST_ROLLOUT");
-    if (e && e[0] == '1') return false;
-    if (mode != GPMPC_MODE_INDEPENDENT || gp->T != 1 || gp->D != 2 || gp->real_has_grad) return false;
-    if (env->env_id == GPMPC_ENV_CAR_RESIDUAL) return gp->g_ny == 3 && gp->grid_n0 == 5 && gp->grid_n1 == 9;
-    if (env->env_id == GPMPC_ENV_PENDULUM1D) return gp->g_ny == 1 && gp->grid_n0 == 4 && gp->grid_n1 == 9;
-    return false;
+// instantiated for the shipped grids (car 5 x 9, pendulum1D 4 x 9) with the value-only model (T = 1): one sample per lane, the
+// grid root of the plan unless disabled (GPMPC_DISABLE_GRID_ROOT=1 keeps the triangular L_rr^-1 form, used by the tests to compare
+// the two); the layout fields are the generic kernel's
+RolloutLaunch rollout_indep_sizing(const RolloutShape& s, const RolloutLaunch& g, bool grid_root) {
+    RolloutLaunch p = g;
+    p.kernel = GPMPC_KERNEL_AUTO;
+    if (s.mode != GPMPC_MODE_INDEPENDENT || s.T != 1 || s.D != 2 || s.real_has_grad) return p;
+    if (!(s.env_id == GPMPC_ENV_CAR_RESIDUAL && s.g_ny == 3 && s.grid_n0 == 5 && s.grid_n1 == 9) &&
+        !(s.env_id == GPMPC_ENV_PENDULUM1D && s.g_ny == 1 && s.grid_n0 == 4 && s.grid_n1 == 9))
+        return p;
+    p.kernel = GPMPC_KERNEL_INDEP;
+    p.grid_root = grid_root && plan_has_grid_root(s.grid_n0, s.grid_n1, s.real_has_grad);
+    p.grid = p.grid_root ? (s.Ns + 63) / 64 : (s.Ns + 255) / 256;
+    p.block = p.grid_root ? 64 * s.g_ny : 256;
+    p.lds_bytes = 0;
+    return p;
 }
 
-int rollout_indep_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, hipStream_t st) {
-    // the grid root of the plan unless disabled (GPMPC_DISABLE_GRID_ROOT=1 keeps the triangular L_rr^-1 form, used by
-    // the tests to compare the two)
-    const char* eg = std::getenv("GPMPC_DISABLE_GRID_ROOT");
-    const bool grid_root = !(eg && eg[0] == '1') && plan_has_grid_root(gp->grid_n0, gp->grid_n1, gp->real_has_grad);
-    if (grid_root) {
-        const dim3 grid((unsigned)((args.Ns + 63) / 64));
-        if (env->env_id == GPMPC_ENV_CAR_RESIDUAL)
-            hipLaunchKernelGGL((rollout_indep_grid_kernel<GPMPC_ENV_CAR_RESIDUAL, 5, 9, 3>), grid, dim3(64 * 3), 0, st, args);
+int rollout_indep_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    const dim3 grid((unsigned)p.grid), block(p.block);
+    if (p.grid_root) {
+        if (p.env_id == GPMPC_ENV_CAR_RESIDUAL)
+            hipLaunchKernelGGL((rollout_indep_grid_kernel<GPMPC_ENV_CAR_RESIDUAL, 5, 9, 3>), grid, block, 0, st, args);
         else
-            hipLaunchKernelGGL((rollout_indep_grid_kernel<GPMPC_ENV_PENDULUM1D, 4, 9, 1>), grid, dim3(64), 0, st, args);
+            hipLaunchKernelGGL((rollout_indep_grid_kernel<GPMPC_ENV_PENDULUM1D, 4, 9, 1>), grid, block, 0, st, args);
     } else {
-        const dim3 grid((unsigned)((args.Ns + 255) / 256)), block(256);
-        if (env->env_id == GPMPC_ENV_CAR_RESIDUAL)
+        if (p.env_id == GPMPC_ENV_CAR_RESIDUAL)
             hipLaunchKernelGGL((rollout_indep_kernel<GPMPC_ENV_CAR_RESIDUAL, 5, 9, 3>), grid, block, 0, st, args);
         else
             hipLaunchKernelGGL((rollout_indep_kernel<GPMPC_ENV_PENDULUM1D, 4, 9, 1>), grid, block, 0, st, args);

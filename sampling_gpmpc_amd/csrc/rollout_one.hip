@@ -37,7 +37,7 @@
 // times the masked writes; tools/experiments/rollout_one_superrow/.)
 // Reference: the loop of benchmarking/simulate_true_reachable_set.py:179-258 / src/agent.py:362-415 (one launch here).
 #include "gpmpc_host.hpp"
-#include "rollout_args.hpp"
+#include "rollout_plan.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -594,40 +594,27 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int one_mode() {                                          // 0 auto, 1 forced, -1 disabled
-    if (g_rollout_pin != GPMPC_KERNEL_AUTO) return (g_rollout_pin == GPMPC_KERNEL_ONE) ? 1 : -1;
-    const char* e = std::getenv("GPMPC_ROLLOUT_ONE");
-    if (!e) return 0;
-    return (e[0] == '1') ? 1 : ((e[0] == '0') ? -1 : 0);
+// instantiated for the pendulum1D 4 x 9 grid with value-only real labels, every appended row observed with T = 3 tasks; the
+// factor lives in registers (no workspace), the other layout fields are the generic kernel's
+RolloutLaunch rollout_one_sizing(const RolloutShape& s, const RolloutLaunch& g) {
+    RolloutLaunch p = g;
+    p.kernel = GPMPC_KERNEL_AUTO;
+    if (s.mode != GPMPC_MODE_RECONDITIONED || s.T != 3 || s.D != 2 || s.hall_tasks != 3 || s.real_has_grad) return p;
+    if (!plan_has_grid_root(s.grid_n0, s.grid_n1, s.real_has_grad)) return p;
+    if (s.env_id != GPMPC_ENV_PENDULUM1D || s.g_ny != 1 || s.grid_n0 != 4 || s.grid_n1 != 9) return p;
+    if (s.H < 2 || 3 * (s.H - 1) > kOneMaxRows) return p;          // 22 tile rows of panels fit the AGPR file
+    p.kernel = GPMPC_KERNEL_ONE;
+    p.grid = s.Ns;
+    p.block = 64;
+    p.lds_bytes = (size_t)OneLds::TOTAL * sizeof(double);
+    p.ws_bytes = 0;
+    return p;
 }
 
-bool rollout_one_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H, int64_t Ns) {
-    const int md = one_mode();
-    if (md < 0) return false;
-    const char* e = std::getenv("GPMPC_DISABLE_FAST_ROLLOUT");
-    if (e && e[0] == '1') return false;
-    const char* eg = std::getenv("GPMPC_DISABLE_GRID_ROOT");
-    if (eg && eg[0] == '1') return false;
-    const char* ef = std::getenv("GPMPC_FORCE_GLOBAL_FACTOR");
-    if (ef && ef[0] == '1') return false;
-    const char* et = std::getenv("GPMPC_ROLLOUT_TILES");                      // the tiled kernel forced (tests, A/B timing)
-    if (md == 0 && et && et[0] == '1') return false;
-    if (mode != GPMPC_MODE_RECONDITIONED || gp->T != 3 || gp->D != 2 || hall_tasks != 3 || gp->real_has_grad) return false;
-    if (!plan_has_grid_root(gp->grid_n0, gp->grid_n1, gp->real_has_grad)) return false;
-    if (env->env_id != GPMPC_ENV_PENDULUM1D || gp->g_ny != 1 || gp->grid_n0 != 4 || gp->grid_n1 != 9) return false;
-    if (H < 2 || 3 * (H - 1) > kOneMaxRows) return false;           // 22 tile rows of panels fit the AGPR file
-    if (md > 0) return true;
-    // one chain per wave, one wave per SIMD: up to two rounds of the chip (2048 chains) it beats four chains per wave
-    return Ns <= 2048;
-}
-
-int rollout_one_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, hipStream_t st) {
-    (void)gp;
-    (void)env;
-    const size_t lds = (size_t)OneLds::TOTAL * sizeof(double);
+int rollout_one_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
     auto k = rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D>;
-    GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3((unsigned)args.Ns), dim3(64), lds, st, args);
+    GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL(k, dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, args);
     GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
 }

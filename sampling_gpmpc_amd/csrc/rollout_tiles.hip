@@ -30,7 +30,7 @@
 //     (a point keeps Qa^T{ea, ea q0} and Qb^T{eb, eb q1}: 28 doubles in LDS instead of three 45-vectors), per-chain
 //     operands broadcast with v_fmac_f64_dpp row_newbcast.  A 1.5 KB LDS scratch converts between the two lane maps.
 #include "gpmpc_host.hpp"
-#include "rollout_args.hpp"
+#include "rollout_plan.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -1113,105 +1113,76 @@ __global__ __launch_bounds__(64, 1) void rollout_tiles_kernel(const RolloutArgs 
 // and one size up each (5 x 9 / 6 x 9), with 32 tile rows (128 label rows per chain: H <= 43) or 48 (192: H <= 65, the
 // shipped car H = 50 included); anything else stays with the one-chain-per-wave kernels.
 // ---------------------------------------------------------------------------------------------------------------
-static int tiles_mode() {                                        // 0 auto, 1 forced, -1 disabled
-    if (g_rollout_pin != GPMPC_KERNEL_AUTO) return (g_rollout_pin == GPMPC_KERNEL_TILES) ? 1 : -1;
-    const char* e = std::getenv("GPMPC_ROLLOUT_TILES");
-    if (!e) return 0;
-    return (e[0] == '1') ? 1 : ((e[0] == '0') ? -1 : 0);
-}
-
-// tile rows for H steps behind n_pre conditioning-only points (three row slots per point, value-only points included)
-static int tiles_nt(int H, int n_pre = 0) {
-    const int n = 3 * (n_pre + H - 1);
-    return (n <= 128) ? 32 : ((n <= 160) ? 40 : ((n <= 192) ? 48 : 0));
-}
-
 template <int N0, int N1>
 static size_t tiles_lds_bytes(int g_ny, int H, int n_pre) {
     const int gl = (g_ny == 1) ? 4 : 3;
     return (size_t)gl * TilesLds<N0, N1>::per_chain(n_pre + H - 1 > 1 ? n_pre + H - 1 : 1) * sizeof(double);
 }
 
-static size_t tiles_lds_for(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int H, int n_pre) {       // 0: shape not instantiated
-    const int n0 = gp->grid_n0, n1 = gp->grid_n1;
-    if (env->env_id == GPMPC_ENV_PENDULUM1D && gp->g_ny == 1 && n1 == 9) {
-        if (n0 == 4) return tiles_lds_bytes<4, 9>(1, H, n_pre);
-        if (n0 == 5) return tiles_lds_bytes<5, 9>(1, H, n_pre);
+static size_t tiles_lds_for(const RolloutShape& s, int n_pre) {       // 0: shape not instantiated
+    const int n0 = s.grid_n0, n1 = s.grid_n1;
+    if (s.env_id == GPMPC_ENV_PENDULUM1D && s.g_ny == 1 && n1 == 9) {
+        if (n0 == 4) return tiles_lds_bytes<4, 9>(1, s.H, n_pre);
+        if (n0 == 5) return tiles_lds_bytes<5, 9>(1, s.H, n_pre);
     }
-    if (env->env_id == GPMPC_ENV_CAR_RESIDUAL && gp->g_ny == 3 && n1 == 9) {
-        if (n0 == 5) return tiles_lds_bytes<5, 9>(3, H, n_pre);
-        if (n0 == 6) return tiles_lds_bytes<6, 9>(3, H, n_pre);
+    if (s.env_id == GPMPC_ENV_CAR_RESIDUAL && s.g_ny == 3 && n1 == 9) {
+        if (n0 == 5) return tiles_lds_bytes<5, 9>(3, s.H, n_pre);
+        if (n0 == 6) return tiles_lds_bytes<6, 9>(3, s.H, n_pre);
     }
     return 0;
 }
 
 // n_h0 / n_v0 > 0: a seeded call (gpmpc_rollout_seeded without a kept factor state) - the seed points are conditioning-only
-// passes of the same step body; hall_tasks == 1: value-only points keep three row slots (see the kernel)
-bool rollout_tiles_eligible(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int mode, int hall_tasks, int H, int64_t Ns,
-                            int n_h0, int n_v0) {
-    const int md = tiles_mode();
-    const int n_pre = n_h0 + n_v0;
-    if (md < 0) return false;
-    const char* e = std::getenv("GPMPC_DISABLE_FAST_ROLLOUT");
-    if (e && e[0] == '1') return false;
-    const char* eg = std::getenv("GPMPC_DISABLE_GRID_ROOT");
-    if (eg && eg[0] == '1') return false;
-    if (mode != GPMPC_MODE_RECONDITIONED || gp->T != 3 || gp->D != 2 || gp->real_has_grad) return false;
-    if (!(hall_tasks == 3 || hall_tasks == 1)) return false;
-    if (!plan_has_grid_root(gp->grid_n0, gp->grid_n1, gp->real_has_grad)) return false;
-    if ((H < 2 && n_pre == 0) || H < 1 || tiles_nt(H, n_pre) == 0) return false;
-    if (tiles_nt(H, n_pre) > 32 && !((env->env_id == GPMPC_ENV_PENDULUM1D && gp->grid_n0 == 4) || (env->env_id == GPMPC_ENV_CAR_RESIDUAL && gp->grid_n0 == 5)))
-        return false;
-    const size_t lds = tiles_lds_for(gp, env, H, n_pre);
-    if (lds == 0 || lds > 160 * 1024 - 64) return false;
-    if (md > 0) return true;
-    // A wave carries four chains and takes ~1.6-1.9x as long as a wave of the one-chain-per-wave kernel: the tuned kernel
-    // wins while it needs ONE round of the chip (pendulum: 1024 chains, one per SIMD; car: 256 samples, one three-wave
-    // workgroup per CU) and loses from its second round on (tools/debug/tiles_threshold.py, sustained clocks: pendulum
-    // Ns = 1024 0.109 vs 0.170 ms, 1536 0.214 vs 0.181, 3072 0.323 vs 0.208; car Ns = 256 0.216 vs 0.306, 384 0.425 vs
-    // 0.324, 768 0.639 vs 0.380).  Shapes the tuned kernel does not take (other grids, 3 (H - 1) > 128) fall to the generic
-    // kernel, 4-20x slower: there the tiled kernel is taken from 256 chains on.
-    const int64_t chains = Ns * gp->g_ny;
-    const bool tuned_alt = n_pre == 0 && rollout_fast_eligible(gp, env, mode, hall_tasks, H);
-    return tuned_alt ? (chains > (gp->g_ny == 1 ? 1024 : 768)) : (chains >= 256);
-}
-
-size_t rollout_tiles_workspace_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int H, int n_pre) {
-    const int nt = tiles_nt(H, n_pre) ? tiles_nt(H, n_pre) : 32;
-    const int64_t waves = (gp->g_ny == 1) ? (Ns + 3) / 4 : Ns;
-    return (size_t)waves * tri(nt) * 64 * sizeof(double);
+// passes of the same step body; hall_tasks == 1: value-only points keep three row slots (see the kernel).  The workspace holds
+// the tile matrix of every wave; nt and ws_bytes are reported for any shape of at most 192 label rows (the workspace queries do
+// not know the env).  The other layout fields are the generic kernel's
+RolloutLaunch rollout_tiles_sizing(const RolloutShape& s, const RolloutLaunch& g) {
+    RolloutLaunch p = g;
+    p.kernel = GPMPC_KERNEL_AUTO;
+    const int n_pre = s.n_h0 + s.n_v0, n = 3 * (n_pre + s.H - 1);      // three row slots per point
+    p.nt = (n <= 128) ? 32 : ((n <= 160) ? 40 : ((n <= 192) ? 48 : 0));
+    if (p.nt == 0) return p;
+    p.grid = (s.g_ny == 1) ? (s.Ns + 3) / 4 : s.Ns;                    // waves: four pendulum chains / one car sample each
+    p.block = 64;
+    p.ws_chain_stride = (long)tri(p.nt) * 64;                          // doubles per wave
+    p.ws_bytes = (size_t)p.grid * p.ws_chain_stride * sizeof(double);
+    p.zero_bytes = 0;
+    if (s.mode != GPMPC_MODE_RECONDITIONED || s.T != 3 || s.D != 2 || s.real_has_grad) return p;
+    if (!(s.hall_tasks == 3 || s.hall_tasks == 1)) return p;
+    if (!plan_has_grid_root(s.grid_n0, s.grid_n1, s.real_has_grad)) return p;
+    if ((s.H < 2 && n_pre == 0) || s.H < 1) return p;
+    if (p.nt > 32 && !((s.env_id == GPMPC_ENV_PENDULUM1D && s.grid_n0 == 4) || (s.env_id == GPMPC_ENV_CAR_RESIDUAL && s.grid_n0 == 5)))
+        return p;
+    p.lds_bytes = tiles_lds_for(s, n_pre);
+    if (p.lds_bytes == 0 || p.lds_bytes > 160 * 1024 - 64) return p;
+    p.kernel = GPMPC_KERNEL_TILES;
+    p.n0 = s.grid_n0;
+    p.seed = n_pre > 0 || s.hall_tasks == 1;
+    return p;
 }
 
 template <int N0, int N1, int ENV, int NT>
-static int launch_tiles(RolloutArgs& args, int g_ny, hipStream_t st) {
-    const size_t lds = tiles_lds_bytes<N0, N1>(g_ny, args.H, args.n_h0 + args.n_v0);
-    const long nblk = (g_ny == 1) ? (args.Ns + 3) / 4 : args.Ns;
-    const bool seed = (args.n_h0 + args.n_v0 > 0) || args.hall_tasks == 1;
-    auto k = seed ? rollout_tiles_kernel<N0, N1, ENV, NT, true> : rollout_tiles_kernel<N0, N1, ENV, NT, false>;
-    GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(64), lds, st, args);
+static int launch_tiles(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    auto k = p.seed ? rollout_tiles_kernel<N0, N1, ENV, NT, true> : rollout_tiles_kernel<N0, N1, ENV, NT, false>;
+    GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL(k, dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, args);
     GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
 }
 
-int rollout_tiles_launch(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, RolloutArgs& args, void* ws, size_t ws_bytes,
-                         hipStream_t st) {
-    if (!ws || ws_bytes < rollout_tiles_workspace_bytes(gp, args.Ns, args.H, args.n_h0 + args.n_v0))
-        return fail(GPMPC_E_WORKSPACE, "gpmpc_rollout: workspace too small");
-    const int nt = tiles_nt(args.H, args.n_h0 + args.n_v0), n0 = gp->grid_n0;
-    args.ws = (double*)ws;
-    args.ws_chain_stride = (long)tri(nt) * 64;                   // doubles per wave
+int rollout_tiles_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
+    const int nt = p.nt, n0 = p.n0;
     // the shipped grids with every tile-row count, the one-size-up grids with 32 tile rows
-    if (env->env_id == GPMPC_ENV_PENDULUM1D) {
-        if (n0 == 4 && nt == 32) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 32>(args, 1, st);
-        if (n0 == 4 && nt == 40) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 40>(args, 1, st);
-        if (n0 == 4 && nt == 48) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 48>(args, 1, st);
-        if (n0 == 5 && nt == 32) return launch_tiles<5, 9, GPMPC_ENV_PENDULUM1D, 32>(args, 1, st);
+    if (p.env_id == GPMPC_ENV_PENDULUM1D) {
+        if (n0 == 4 && nt == 32) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 32>(args, p, st);
+        if (n0 == 4 && nt == 40) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 40>(args, p, st);
+        if (n0 == 4 && nt == 48) return launch_tiles<4, 9, GPMPC_ENV_PENDULUM1D, 48>(args, p, st);
+        if (n0 == 5 && nt == 32) return launch_tiles<5, 9, GPMPC_ENV_PENDULUM1D, 32>(args, p, st);
     } else {
-        if (n0 == 5 && nt == 32) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 32>(args, 3, st);
-        if (n0 == 5 && nt == 40) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 40>(args, 3, st);
-        if (n0 == 5 && nt == 48) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 48>(args, 3, st);
-        if (n0 == 6 && nt == 32) return launch_tiles<6, 9, GPMPC_ENV_CAR_RESIDUAL, 32>(args, 3, st);
+        if (n0 == 5 && nt == 32) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 32>(args, p, st);
+        if (n0 == 5 && nt == 40) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 40>(args, p, st);
+        if (n0 == 5 && nt == 48) return launch_tiles<5, 9, GPMPC_ENV_CAR_RESIDUAL, 48>(args, p, st);
+        if (n0 == 6 && nt == 32) return launch_tiles<6, 9, GPMPC_ENV_CAR_RESIDUAL, 32>(args, p, st);
     }
     return fail(GPMPC_E_UNSUPPORTED, "rollout_tiles: shape not instantiated");
 }

@@ -1,5 +1,5 @@
 """LDS-resident vs HBM/L2-resident factor of the tuned rollout kernel over the horizon (GPMPC_FORCE_GLOBAL_FACTOR=1
-selects the latter); decides the heuristic in rollout_fast.hip:fast_plan."""
+selects the latter); decides the heuristic in rollout_fast.hip:rollout_fast_sizing."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bench_configs as bc
