@@ -32,6 +32,15 @@
 //     (one_solve<K>: the next tile row's independent MFMAs stand in the wait states of the current one), rare paths (root
 //     retry, sampling clip, variance-is-zero, the wrap-group diagonal) are out of line, and every instruction off the step's
 //     spine counts (~6 cycles per VALU, ~17 per MFMA).
+//   * the step loop is ROTATED: the kernel entries of step t + 1 are issued inside step t.  Prologue: entries of step 0.  Body:
+//     (i) fence, LDS reads, one_solve<K>, Gram; (ii) the FIRST pivot of the two 3 x 3 roots, y[0] from it and with y[0] the
+//     next state, input, trajectory record and exponent; (iii) + (iv) pivots 2 and 3 with the next step's exponential as a
+//     third stream of their levels, the ds_bpermute requests, then the draws and the clip test; (v) the grid-root DPP
+//     products, the right-hand sides and v_r into the LDS converters; (vi) the append, which covers the latency of those
+//     ds_writes.  y[0] is final unless the root retry, the variance-is-zero replacement or the clip of slot 0 replaces
+//     it: then - and only then - (ii) and the exponential run again from the final value in the cold block.  The converters
+//     are untouched by the append and their layout does not depend on the epoch, so the hand-over crosses epoch changes.
+//     (profiles/one_rotated_phases.md; the entries need no register across the append, LDS carries them.)
 //
 // (A first version grouped FOUR TILE ROWS per MFMA with the solution tiles replicated in all blocks: 1.5x the MFMAs, three
 // times the masked writes; tools/experiments/rollout_one_superrow/.)
@@ -199,13 +208,94 @@ __device__ __forceinline__ double one_pick3(int i, double v0, double v1, double 
     return (i == 0) ? v0 : t;
 }
 
+// chol3_pair_lean (gpmpc_device.hpp) cut behind its FIRST pivot: the sample's y[0] = sqrt(S_00) z_0 + mu_0 - all the next
+// state needs - is known after one_chol_pivot1.  one_chol_rest runs pivots 2 and 3 with the NEXT step's exponential
+// (one_exp_neg, same operations in the same order) as a third stream of its levels: the Cholesky chains are ~8 cycles per
+// dependent instruction of a lone wave, the exponential's instructions stand in those gaps.  Per matrix the operations and
+// their order are those of chol3_pair_lean => bit-identical factors.
+struct OneCholPair {
+    double d0[2], y0[2], r0[2];
+};
+#ifdef GPMPC_ONE_NO_REST_FENCES                                   // experiment: leave the order of the levels to hipcc
+#define GPMPC_ONE_FENCE()
+#else
+#define GPMPC_ONE_FENCE() __builtin_amdgcn_sched_barrier(0)
+#endif
+#define GPMPC_ONE_LVL(stmt, third)                              \
+    _Pragma("unroll") for (int m_ = 0; m_ < 2; ++m_) { stmt; }  \
+    third;                                                      \
+    GPMPC_ONE_FENCE()
+__device__ __forceinline__ void one_chol_pivot1(double a00, double b00, OneCholPair& p) {
+    double h[2], t[2], e[2];
+    p.d0[0] = a00, p.d0[1] = b00;
+    __builtin_amdgcn_sched_barrier(0);
+    GPMPC_ROW2L(p.y0[m_] = __builtin_amdgcn_rsq(p.d0[m_]); h[m_] = 0.5 * p.d0[m_]);
+    GPMPC_ROW2L(t[m_] = h[m_] * p.y0[m_]);
+    GPMPC_ROW2L(e[m_] = fma(-t[m_], p.y0[m_], 0.5));
+    GPMPC_ROW2L(p.y0[m_] = fma(p.y0[m_], e[m_], p.y0[m_]));
+    GPMPC_ROW2L(p.r0[m_] = p.d0[m_] * p.y0[m_]);
+}
+__device__ __forceinline__ void one_chol_rest(const double (&A)[3][3], const double (&B)[3][3], const OneCholPair& p, double x,
+                                              const OneExpConsts& k, double (&LA)[3][3], double (&LB)[3][3], double (&invA)[3],
+                                              double (&invB)[3], bool& okA, bool& okB, double& ex) {
+    double s10[2] = {A[1][0], B[1][0]}, s20[2] = {A[2][0], B[2][0]}, s21[2] = {A[2][1], B[2][1]};
+    double s11[2] = {A[1][1], B[1][1]}, s22[2] = {A[2][2], B[2][2]};
+    double d1[2], d2[2], y1[2], y2[2], h[2], t[2], e[2], l10[2], l20[2], l21[2], n21[2], p2[2], r1[2], r2[2];
+    // (the exponential's Estrin terms in the order that keeps the fewest of them alive: 7 doubles at most)
+    double n, r, rr, a0, a1, a2, a4;
+    int ni;
+    GPMPC_ONE_FENCE();
+    GPMPC_ONE_LVL(l10[m_] = s10[m_] * p.y0[m_]; l20[m_] = s20[m_] * p.y0[m_], n = x * k.log2e);
+    GPMPC_ONE_LVL(d1[m_] = fma(-l10[m_], l10[m_], s11[m_]); n21[m_] = fma(-l20[m_], l10[m_], s21[m_]), n = rint(n));
+    GPMPC_ONE_LVL(y1[m_] = __builtin_amdgcn_rsq(d1[m_]); h[m_] = 0.5 * d1[m_]; p2[m_] = fma(-l20[m_], l20[m_], s22[m_]),
+                  r = fma(n, k.nln2h, x));
+    GPMPC_ONE_LVL(t[m_] = h[m_] * y1[m_], r = fma(n, k.nln2l, r); ni = (int)n);
+    GPMPC_ONE_LVL(e[m_] = fma(-t[m_], y1[m_], 0.5), rr = r * r; a0 = 1.0 + r; a1 = fma(k.c3, r, k.c2));
+    GPMPC_ONE_LVL(y1[m_] = fma(y1[m_], e[m_], y1[m_]), a0 = fma(a1, rr, a0); a4 = fma(k.c9, r, k.c8); a1 = fma(k.c11, r, k.c10));
+    GPMPC_ONE_LVL(l21[m_] = n21[m_] * y1[m_]; r1[m_] = d1[m_] * y1[m_], a4 = fma(a1, rr, a4); a2 = fma(k.c5, r, k.c4));
+    GPMPC_ONE_LVL(d2[m_] = fma(-l21[m_], l21[m_], p2[m_]), a1 = fma(k.c7, r, k.c6));
+    GPMPC_ONE_LVL(y2[m_] = __builtin_amdgcn_rsq(d2[m_]); h[m_] = 0.5 * d2[m_], a2 = fma(a1, rr, a2); rr = rr * rr);
+    GPMPC_ONE_LVL(t[m_] = h[m_] * y2[m_], a2 = fma(a4, rr, a2));
+    GPMPC_ONE_LVL(e[m_] = fma(-t[m_], y2[m_], 0.5), a0 = fma(a2, rr, a0));
+    GPMPC_ONE_LVL(y2[m_] = fma(y2[m_], e[m_], y2[m_]), ex = ldexp(a0, ni));
+    GPMPC_ONE_LVL(r2[m_] = d2[m_] * y2[m_], (void)0);
+    asm volatile("" ::"v"(p.r0[0]), "v"(r1[0]), "v"(r2[0]), "v"(p.r0[1]), "v"(r1[1]), "v"(r2[1]));
+    okA = (p.d0[0] > 0.0) && (d1[0] > 0.0) && (d2[0] > 0.0);
+    okB = (p.d0[1] > 0.0) && (d1[1] > 0.0) && (d2[1] > 0.0);
+    LA[0][0] = p.r0[0], LA[1][0] = l10[0], LA[2][0] = l20[0], LA[1][1] = r1[0], LA[2][1] = l21[0], LA[2][2] = r2[0];
+    LB[0][0] = p.r0[1], LB[1][0] = l10[1], LB[2][0] = l20[1], LB[1][1] = r1[1], LB[2][1] = l21[1], LB[2][2] = r2[1];
+    LA[0][1] = LA[0][2] = LA[1][2] = 0.0;
+    LB[0][1] = LB[0][2] = LB[1][2] = 0.0;
+    invA[0] = p.y0[0], invA[1] = y1[0], invA[2] = y2[0];
+    invB[0] = p.y0[1], invB[1] = y1[1], invB[2] = y2[1];
+}
+
+typedef const __attribute__((address_space(4))) RolloutArgs* OneArgsPtr;
+// (opaque to the optimiser: a load through the result stays where it is written)
+__device__ __forceinline__ OneArgsPtr one_cold_args(OneArgsPtr p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
+__device__ __forceinline__ long one_cold_sample(int s) {
+    asm volatile("" : "+s"(s));
+    return s;
+}
+
+// p != nullptr, compared where it is asked (one scalar compare per step): hoisted out of the step loop the answer
+// occupies an SGPR pair for the whole kernel
+__device__ __forceinline__ bool one_wanted(double* p) {
+    asm volatile("" : "+s"(p));
+    return p != nullptr;
+}
 struct OneLds {
     static constexpr int VR = 0;                                  // [4 NKT][RS]  v_r rows (natural-map source)
     static constexpr int HS = ((4 * kOneNKT * kOneRS + 1) & ~1);  // [96][RS]     right-hand sides of the appended rows
     static constexpr int TOTAL = HS + 96 * kOneRS;
 };
 
-template <int N0, int ENV>
+// LEAN: no optional outputs (Y, Xi) and the variance-is-zero replacement off - what RolloutRunner and the benchmark launch;
+// the three launch-uniform tests and their branches leave the step's spine
+template <int N0, int ENV, bool LEAN>
 __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a) {
     static_assert(ENV == GPMPC_ENV_PENDULUM1D && N0 == 4, "instantiated for the pendulum1D 4 x 9 grid");
     constexpr int D = 2, T = 3, N1 = 9, NR = N0 * N1, NX = 2;
@@ -218,6 +308,11 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #endif
 
     const GpParams& gp = a.gp;
+    // what only the cold paths and the epilogue need (the retry's jitter, the output pointers) is read through this pointer
+    // where it is used, and the sample index is kept as ONE 32-bit scalar: held in SGPRs across the step loop these would
+    // be spilled - the loop leaves no scalar register free
+    const OneArgsPtr ak0 = (OneArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    const int s32 = blockIdx.x;
     const int lane = threadIdx.x;
     const int kq = lane >> 4, bm = (lane >> 2) & 3, jq = lane & 3;
     const long s = blockIdx.x;
@@ -278,48 +373,63 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     if (blockIdx.x == 0 && threadIdx.x == 0) g_one_phase_cycles[8] = opht_ - opk0_;
 #endif
 
-    auto step = [&](auto Kc) {
-        constexpr int K = decltype(Kc)::value;                    // group of the incomplete tile (unified tile 9 + (n_h >> 2))
-        constexpr int R0 = 4 * K - NKT;                           // first tile row of the group (may be negative: real-data tiles)
-        const int i0 = n_h & 3, ycol = (i0 + 3) & 3, npts = t;
-        const int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
-        // ---- input, GP input ---------------------------------------------------------------------------------------
-        double u, xi[D];
+    // ---- the kernel entries of a step, in the three pieces the rotated loop issues them in --------------------------------
+    // (a) input and GP input of step tn from the state xs, the trajectory record, the exponent of the lane's kernel factor:
+    //     ONE exponential per lane - the grid axis factor (lanes < N0 + N1) or the appended point jpt
+    auto ent_a = [&](int tn, bool store, const double (&xs)[NX], double& un) -> double {
+        double xi[D];
         {
-            const double uf = readlane_f64(uq, t);
+            const double uf = readlane_f64(uq, tn);
             if (a.env.use_feedback) {
                 double acc = 0.0;
 #pragma unroll
-                for (int j = 0; j < NX; ++j) acc += (a.env.x_goal[j] - x[j]) * a.env.K[0][j];
-                u = -acc + uf;
+                for (int j = 0; j < NX; ++j) acc += (a.env.x_goal[j] - xs[j]) * a.env.K[0][j];
+                un = -acc + uf;
             } else {
-                u = uf;
+                un = uf;
             }
-            xi[0] = x[0];
-            xi[1] = u;
+            xi[0] = xs[0];
+            xi[1] = un;
         }
 #pragma unroll
-        for (int d = 0; d < NX; ++d) xq[d] = (lane == t) ? x[d] : xq[d];
-        if (lane == 0 && a.Xi) {
+        for (int d = 0; d < NX; ++d) xq[d] = (lane == tn) ? xs[d] : xq[d];
+        if (!LEAN && lane == 0 && one_wanted(Xi_s) && store) {
 #pragma unroll
-            for (int d = 0; d < D; ++d) Xi_s[t * D + d] = xi[d];
+            for (int d = 0; d < D; ++d) Xi_s[tn * D + d] = xi[d];
         }
-
-        // ---- kernel factors: ONE exponential per lane - the grid axis factor (lanes < N0 + N1) or the appended point jpt -----
-        double ea, gq, kk, q0, q1;
+        const double gr = g_x - (g_ax0 ? xi[0] : xi[1]), gq = gr * g_il2;
+        const double d0 = xh[0] - xi[0], d1 = xh[1] - xi[1], q0 = d0 * il0, q1 = d1 * il1;
+        return (lane < kPt0) ? -0.5 * gr * gq : -0.5 * (d0 * q0 + d1 * q1);
+    };
+    // (b) the factor of the tn existing points, and the axis factors to all DPP rows (requested here, used in (c))
+    // (gq, q0, q1 are two instructions each from the GP input (xi0, xi1): computed again where they are used rather than
+    // carried across the roots - this kernel has no register to spare)
+    auto ent_b = [&](int tn, double ea, double xi0, double xi1, double& kk, double& Rq0, double& Rq1) {
+        const double gr = g_x - (g_ax0 ? xi0 : xi1), gq = gr * g_il2;
+        kk = (jpt >= 0 && jpt < tn) ? os * ea : 0.0;
+        Rq0 = one_bpermute(ea, bp_addr);
+        Rq1 = one_bpermute(ea * gq, bp_addr);
+    };
+    // (c) the right-hand sides of the nh appended rows and v_r = W k_r into the lane-map converters
+    auto ent_c = [&](int nh, double kk, double xi0, double xi1, double Rq0, double Rq1) {
+        const double q0 = (xh[0] - xi0) * il0, q1 = (xh[1] - xi1) * il1;
+        const int i0 = nh & 3, ycol = (i0 + 3) & 3;
+        const int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
+        // (the DPP products first: their operands - the ds_bpermute results - arrived long ago, while a wait behind the
+        // ds_writes below would also wait for those)
+        // ---- v_r = W k_r through the grid root (rollout_fast.hip, step 2): lane = real point ------------------------------
+        double vr[T];
         {
-            const double gr = g_x - (g_ax0 ? xi[0] : xi[1]);
-            gq = gr * g_il2;
-            const double d0 = xh[0] - xi[0], d1 = xh[1] - xi[1];
-            q0 = d0 * il0;
-            q1 = d1 * il1;
-            ea = one_exp_neg((lane < kPt0) ? -0.5 * gr * gq : -0.5 * (d0 * q0 + d1 * q1), ek);
-            kk = (jpt >= 0 && jpt < npts) ? os * ea : 0.0;
+            double PA0 = 0.0, PA1 = 0.0, PB0 = 0.0, PB1 = 0.0;
+            one_axis4(PA0, PA1, Rq0, Rq1, qa);                    // lanes 0 .. 3 of the row: axis 0
+            one_axis9(PB0, PB1, Rq0, Rq1, qb);                    // lanes 4 .. 12: axis 1
+            const double s0 = dsc * PB0;
+            vr[0] = s0 * PA0;
+            vr[1] = s0 * PA1;
+            vr[2] = dsc * PA0 * PB1;
         }
-        // the axis factors to all DPP rows (requested now, used after the appended rows' entries)
-        const double R0_ = one_bpermute(ea, bp_addr), R1_ = one_bpermute(ea * gq, bp_addr);
         // ---- right-hand sides of the appended rows: lane = point, cov(task a of the point, task b of the test point) ----
-        if (n_h > 0 && jpt >= 0 && jpt < 32) {
+        if (nh > 0 && jpt >= 0 && jpt < 32) {
             // k (A_a B_b + [a == b > 0] / l_a^2) with A = (1, -q0, -q1), B = (1, q0, q1)
             const double kA[T] = {kk, -kk * q0, -kk * q1}, kd[T] = {0.0, kk * il0, kk * il1};
 #pragma unroll
@@ -331,17 +441,6 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 dst[ycol] = yt[aa];                               // (zero until the lane's point exists)
             }
         }
-        // ---- v_r = W k_r through the grid root (rollout_fast.hip, step 2): lane = real point ------------------------------
-        double vr[T];
-        {
-            double PA0 = 0.0, PA1 = 0.0, PB0 = 0.0, PB1 = 0.0;
-            one_axis4(PA0, PA1, R0_, R1_, qa);                    // lanes 0 .. 3 of the row: axis 0
-            one_axis9(PB0, PB1, R0_, R1_, qb);                    // lanes 4 .. 12: axis 1
-            const double s0 = dsc * PB0;
-            vr[0] = s0 * PA0;
-            vr[1] = s0 * PA1;
-            vr[2] = dsc * PA0 * PB1;
-        }
         if (lane < NR) {                                          // rows of v_r, task column c at (i0 + c) & 3, whitened label beside
             double* dst = VRb + lane * kOneRS;
             dst[cb0] = vr[0];
@@ -349,6 +448,27 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
             dst[cb2] = vr[2];
             dst[ycol] = w_lane;
         }
+    };
+
+    // ---- prologue: the entries of step 0 (no appended rows yet) ------------------------------------------------------------
+    double ucur;                                                  // the input of the step whose entries are in LDS
+    {
+        double kk, Rq0, Rq1;
+        const double ea = one_exp_neg(ent_a(0, true, x, ucur), ek);
+        ent_b(0, ea, x[0], ucur, kk, Rq0, Rq1);
+        ent_c(0, kk, x[0], ucur, Rq0, Rq1);
+    }
+#ifdef GPMPC_PHASE_TIMERS
+    opht_ = __builtin_readcyclecounter();
+#endif
+
+    auto step = [&](auto Kc) {
+        constexpr int K = decltype(Kc)::value;                    // group of the incomplete tile (unified tile 9 + (n_h >> 2))
+        constexpr int R0 = 4 * K - NKT;                           // first tile row of the group (may be negative: real-data tiles)
+        const int i0 = n_h & 3, ycol = (i0 + 3) & 3, npts = t;
+        const int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
+        const bool more = t + 1 < H;
+        // ---- (i) this step's entries are in LDS (written by the prologue or behind the previous step's sample) -------------
         one_sync_lds();
         // the solution, one natural register per group: the real-data tiles now, the appended tiles as they are solved
         double Vu[K + 1], RN[K + 1];
@@ -377,90 +497,129 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         OPH(2);
 
         // ---- S' = sum_g Vu[g]^T Vu[g] (each block sums its own tiles), summed over the blocks; entry [k][j] in lane 16 k + j ---
-        double mu[T], S[T][T];
-        {
-            const double Stot = one_block_sum(S0 + S1);
-            ODBG(6, Stot);
-            const int cb[T] = {cb0, cb1, cb2};
+        double mu[T], S[T][T], var[T], zt[T];
+        const double Stot = one_block_sum(S0 + S1);
+        ODBG(6, Stot);
+        const int cb[T] = {cb0, cb1, cb2};
+        auto extract = [&](auto bc) {
+            constexpr int bq = decltype(bc)::value;
 #pragma unroll
-            for (int bq = 0; bq < T; ++bq) {
-                mu[bq] = readlane_f64(Stot, 16 * cb[bq] + ycol);
-#pragma unroll
-                for (int c = 0; c <= bq; ++c) {
-                    const double kss = (bq == c) ? ((bq == 0) ? os : ((bq == 1) ? os * il0 : os * il1)) : 0.0;
-                    const double val = kss - readlane_f64(Stot, 16 * cb[bq] + cb[c]);
-                    S[bq][c] = val;
-                    S[c][bq] = val;
-                }
+            for (int c = 0; c <= bq; ++c) {
+                const double kss = (bq == c) ? ((bq == 0) ? os : ((bq == 1) ? os * il0 : os * il1)) : 0.0;
+                const double val = kss - readlane_f64(Stot, 16 * cb[bq] + cb[c]);
+                S[bq][c] = val;
+                S[c][bq] = val;
             }
-        }
+            // variance floor (as sample_gp, src/agent.py:629-708)
+            var[bq] = fmax(S[bq][bq], gp.var_floor);
+        };
+        // (the mean and the base sample of a slot are fetched where its draw is formed: SGPRs are as scarce as VGPRs here)
+        auto fetch = [&](auto bc) {
+            constexpr int bq = decltype(bc)::value;
+            mu[bq] = readlane_f64(Stot, 16 * cb[bq] + ycol);
+            zt[bq] = readlane_f64(zq[bq], t);
+        };
+        extract(std::integral_constant<int, 0>{});
+        fetch(std::integral_constant<int, 0>{});
         OPH(3);
-        // ---- variance floor, roots, sample (as sample_gp, src/agent.py:629-708) -------------------------------------------
-        double var[T];
-#pragma unroll
-        for (int bq = 0; bq < T; ++bq) var[bq] = fmax(S[bq][bq], gp.var_floor);
+        // ---- (ii) the first pivot of the two roots, y[0] from it, and with y[0] everything step t + 1 starts from -------------
+        OneCholPair ch;
+        one_chol_pivot1(S[0][0] + gp.noise[0], S[0][0], ch);
+        double y0s;                                               // y[0] unless a rare path below replaces it
+        {
+            double acc = 0.0;
+            acc = fma(ch.r0[1], zt[0], acc);
+            y0s = acc + mu[0];
+        }
+        double x0n, un, kk, Rq0, Rq1;
+        x0n = x[0] + x[1] * a.env.dt;
+        {
+            const bool mine = jpt == npts;                        // the lane of the point this step appends: its GP input
+            xh[0] = mine ? x[0] : xh[0];
+            xh[1] = mine ? ucur : xh[1];
+        }
+        double earg;
+        {
+            const double xs[NX] = {x0n, x[1] + y0s};
+            earg = ent_a(t + 1, more, xs, un);
+        }
+        extract(std::integral_constant<int, 1>{});
+        extract(std::integral_constant<int, 2>{});
         if (fmin(fmin(S[0][0], S[1][1]), S[2][2]) < gp.var_floor) info_acc |= GPMPC_INFO_VAR_CLAMPED;
         // the variance-is-zero replacement (src/agent.py:646-660) is off (threshold < 0) in the shipped configurations: uniform branch
         bool all_zero = false;
-        if (a.var_zero_thr >= 0.0) all_zero = (var[0] <= a.var_zero_thr) && (var[1] <= a.var_zero_thr) && (var[2] <= a.var_zero_thr);
+        if (!LEAN && a.var_zero_thr >= 0.0) all_zero = (var[0] <= a.var_zero_thr) && (var[1] <= a.var_zero_thr) && (var[2] <= a.var_zero_thr);
+        // ---- (iii) + (iv) pivots 2 and 3 with the next step's exponential as a third stream of their levels ------------------
         double Rt[T][T], C[T][T], cinv[T];
-        bool c_ok;
+        bool c_ok, r_ok;
         {
-            double Sn[T][T], rinv[T];
+            double Sn[T][T], rinv[T], ea;
 #pragma unroll
             for (int bq = 0; bq < T; ++bq)
 #pragma unroll
                 for (int c = 0; c < T; ++c) Sn[bq][c] = S[bq][c] + ((bq == c) ? gp.noise[bq] : 0.0);
-            bool r_ok;
-            chol3_pair_lean(Sn, S, C, Rt, cinv, rinv, c_ok, r_ok);
-            if (__builtin_expect(!r_ok, 0)) info_acc |= root_small_fast_retry<T>(S, gp.jitter, Rt);
+            one_chol_rest(Sn, S, ch, earg, ek, C, Rt, cinv, rinv, c_ok, r_ok, ea);
+            ent_b(t + 1, ea, x0n, un, kk, Rq0, Rq1);
         }
-        double zt[T];
-#pragma unroll
-        for (int c = 0; c < T; ++c) zt[c] = readlane_f64(zq[c], t);
+        fetch(std::integral_constant<int, 1>{});
+        fetch(std::integral_constant<int, 2>{});
         double y[T];
-        bool clip = false;                                        // ONE branch for the three slots: a taken branch of a lone
-#pragma unroll                                                    // wave costs an instruction fetch (~30 cycles), the clip is rare
-        for (int bq = 0; bq < T; ++bq) {
-            double acc = 0.0;
-#pragma unroll
-            for (int c = 0; c <= bq; ++c) acc = fma(Rt[bq][c], zt[c], acc);
-            const double yb = acc + mu[bq];
-            const double dlt = yb - mu[bq];
-            clip = clip || (dlt * dlt > a.beta * a.beta * var[bq]);
-            y[bq] = yb;
-        }
-        if (__builtin_expect(all_zero, 0)) {                      // (uniform; only with a threshold >= 0) the mean, nothing to clip
-#pragma unroll
-            for (int bq = 0; bq < T; ++bq) y[bq] = mu[bq];
+        bool clip;                                                // ONE branch for the three slots and every rare path: a taken
+        auto draw = [&]() {                                       // branch of a lone wave costs an instruction fetch (~30 cycles)
             clip = false;
-        }
-        if (__builtin_expect(clip, 0)) {
 #pragma unroll
             for (int bq = 0; bq < T; ++bq) {
-                const double dlt = y[bq] - mu[bq];
-                if (dlt * dlt > a.beta * a.beta * var[bq]) {
-                    const double sd = a.beta * sqrt(var[bq]);
-                    y[bq] = fmin(fmax(y[bq], mu[bq] - sd), mu[bq] + sd);
+                double acc = 0.0;
+#pragma unroll
+                for (int c = 0; c <= bq; ++c) acc = fma(Rt[bq][c], zt[c], acc);
+                const double yb = acc + mu[bq];
+                const double dlt = yb - mu[bq];
+                clip = clip || (dlt * dlt > a.beta * a.beta * var[bq]);
+                y[bq] = yb;
+            }
+        };
+        if (__builtin_expect(!r_ok, 0)) info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
+        draw();
+        if (__builtin_expect(clip || all_zero || !r_ok, 0)) {
+            if (all_zero) {                                       // (uniform; only with a threshold >= 0) the mean, nothing to clip
+#pragma unroll
+                for (int bq = 0; bq < T; ++bq) y[bq] = mu[bq];
+                clip = false;
+            }
+            if (clip) {
+#pragma unroll
+                for (int bq = 0; bq < T; ++bq) {
+                    const double dlt = y[bq] - mu[bq];
+                    if (dlt * dlt > a.beta * a.beta * var[bq]) {
+                        const double sd = a.beta * sqrt(var[bq]);
+                        y[bq] = fmin(fmax(y[bq], mu[bq] - sd), mu[bq] + sd);
+                    }
                 }
             }
+            // repair: y[0] itself changed - the next state, input, exponential and axis factors again, from the final value
+            if (y[0] != y0s) {
+                const double xs[NX] = {x0n, x[1] + y[0]};
+                const double ea = one_exp_neg(ent_a(t + 1, more, xs, un), ek);
+                ent_b(t + 1, ea, x0n, un, kk, Rq0, Rq1);
+            }
         }
-        if (lane == 0 && a.Y) {
+        if (!LEAN && lane == 0 && one_wanted(Y_s)) {
 #pragma unroll
             for (int bq = 0; bq < T; ++bq) Y_s[t * T + bq] = y[bq];
         }
         OPH(4);
 
-        // ---- append the point (A.9): three rows of the factor = lanes of the panels ----------------------------------------
-        if (t + 1 < H) {
+        if (more) {
             if (!c_ok) info_acc |= GPMPC_INFO_TRAIN_CHOL_FAIL;
             {
                 const bool mine = jpt == npts;
-                xh[0] = mine ? xi[0] : xh[0];
-                xh[1] = mine ? xi[1] : xh[1];
 #pragma unroll
                 for (int bq = 0; bq < T; ++bq) yt[bq] = mine ? y[bq] : yt[bq];   // the label column is whitened by the same MFMAs (w_r rides in Vu)
             }
+            // ---- (v) the rest of step t + 1's entries: their LDS writes land while the append runs ---------------------------
+            ent_c(n_h + T, kk, x0n, un, Rq0, Rq1);
+            OPH(0);
+            // ---- (vi) append the point (A.9): three rows of the factor = lanes of the panels -------------------------------
             const int tn = n_h >> 2;                              // the incomplete tile row; its unified tile is 4 K + bt
             const int bt = (NKT + tn) & 3;
             const int lo = n_h - 4 * R0;                          // first new row inside group K's 16 rows
@@ -488,9 +647,11 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
             // (no instruction) tells the compiler afterwards that the panels of the candidate rows may have changed.
             auto row_masks = [&](int r, int b, unsigned long long& mBase, unsigned long long& mLast) {
                 const int rowg = 4 * r + jq;
+                int bmv = bm;
+                asm volatile("" : "+v"(bmv));
                 const bool nw = (rowg >= n_h) && (rowg < n_h + 3);
                 mBase = __ballot(nw);
-                mLast = __ballot(nw && bm < b);
+                mLast = __ballot(nw && bmv < b);
             };
             // (a binary decision over the <= 4 candidate rows: a compare chain takes a branch per row in front of the right one)
             one_pick_row<(R0 > 0 ? R0 : 0), (R0 + 4 < kOneNTR ? R0 + 4 : kOneNTR)>(tn, [&](auto rc) {
@@ -530,7 +691,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
             {
                 // natural map of L^T: row index of L = 4 bm + jq (= rA), column index = 4 bm + kq, both inside the group
                 const bool newK = (rA >= lo) && (rA < lo + 3);
-                const int rkD = 4 * bm + kq - lo;
+                int kqv = kq;                                     // (opaque: hipcc reduces rkD <= rA - lo to the loop-invariant
+                asm volatile("" : "+v"(kqv));                     // kq <= jq and keeps that lane mask in an SGPR pair it has to spill)
+                const int rkD = 4 * bm + kqv - lo;
                 const double mixD = new_entry(rA - lo, rkD, Vu[K]);
                 ud = newK ? mixD : ud;
                 const bool newRowK = (rkD >= 0) && (rkD < 3);            // the lane's L-column index is a new row
@@ -563,11 +726,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         OPH(6);
 
         // ---- state hand-over ---------------------------------------------------------------------------------------------
-        {
-            const double x0n = x[0] + x[1] * a.env.dt;
-            x[1] = x[1] + y[0];
-            x[0] = x0n;
-        }
+        x[1] = x[1] + y[0];
+        x[0] = x0n;
+        ucur = un;
         t += 1;
         OPH(7);
     };
@@ -580,11 +741,18 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
     });
 
-    if (lane <= H) {
+    // (the output pointers and the sample index are fetched again here: held in SGPRs across the step loop they would be
+    // spilled - the loop leaves no scalar register free)
+    {
+        const OneArgsPtr ak = one_cold_args(ak0);
+        const long se = one_cold_sample(s32);
+        double* const X_traj = ak->X_traj;
+        if (lane <= H) {
 #pragma unroll
-        for (int d = 0; d < NX; ++d) a.X_traj[(s * NX + d) * (H + 1) + lane] = (lane == H) ? x[d] : xq[d];
+            for (int d = 0; d < NX; ++d) X_traj[(se * NX + d) * (H + 1) + lane] = (lane == H) ? x[d] : xq[d];
+        }
+        if (lane == 0) ak->info[se] = info_acc;
     }
-    if (lane == 0) a.info[s] = info_acc;
     OPH_STORE;
 #ifdef GPMPC_PHASE_TIMERS
     if (blockIdx.x == 0 && threadIdx.x == 0) g_one_phase_cycles[9] = __builtin_readcyclecounter() - opk0_;   // whole kernel
@@ -612,7 +780,8 @@ RolloutLaunch rollout_one_sizing(const RolloutShape& s, const RolloutLaunch& g) 
 }
 
 int rollout_one_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
-    auto k = rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D>;
+    const bool lean = args.Y == nullptr && args.Xi == nullptr && !(args.var_zero_thr >= 0.0);
+    auto k = lean ? rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, true> : rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, false>;
     GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
     hipLaunchKernelGGL(k, dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, args);
     GPMPC_HIP_CHECK(hipGetLastError());
