@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GPMPC_ABI_VERSION 9
+#define GPMPC_ABI_VERSION 10
 
 #define GPMPC_MAX_NY 4   /* GP outputs            (reference agent.g_dim.ny : 1 pendulum1D, 3 car)          */
 #define GPMPC_MAX_D  4   /* GP input dimension    (g_nx + g_nu : 2 in all shipped configs)                 */
@@ -404,6 +404,47 @@ int     gpmpc_or_reduce_words(const int32_t* v, int64_t n, int32_t* out, void* s
  */
 int     gpmpc_base_samples(uint64_t seed, int32_t n_mpc, int32_t n_itrs, int64_t offset, int64_t Ns, int32_t V, double beta,
                            double* out, int32_t* attempts, void* stream);
+
+/*
+ * gpmpc_convex_hulls (ABI 10) - the convex hulls of n_sets independent 2-D point sets of n_points points each, in one call:
+ * the per-time-step reachable sets of a sampled tube.
+ * Replaces: reference benchmarking/generate_convex_hull.py:88-104 (scipy.spatial.ConvexHull on the host, once per step; also
+ * extra/reachable_set_coverage.py:77-88, which takes the ratio of two hull areas).
+ *
+ * Addressing: point i of set s is (px[s*stride_set + i*stride_point], py[same]), strides in doubles.  The tube in the
+ * reference layout X (Ns, nx, H+1) is read in place with stride_point = nx*(H+1), stride_set = 1, px = X + d0*(H+1),
+ * py = X + d1*(H+1); a packed (n_sets, n, 2) vertex buffer with stride_point = 2, stride_set = 2*n, py = px + 1.
+ *
+ * Semantics
+ *   - strict hull: no vertex lies on the segment between its neighbours, points of equal value collapse to one vertex;
+ *   - vertices counter-clockwise, starting at the lexicographically smallest (x, y); every vertex is bit-equal to an input point;
+ *   - src[s][j] (optional) = the lowest input index whose coordinates equal vertex j;
+ *   - one distinct point -> 1 vertex, all points collinear -> the 2 end points, area 0 in both cases;
+ *   - points with a non-finite coordinate are ignored (failed chains leave NaN in X_traj, and NaN is the padding of the packed
+ *     vertex buffers: ragged hulls are merged without a count array);
+ *   - the result is the same bits on every run and for every chunking; the orientation test is ordinary FP64,
+ *     fma(ax-cx, by-cy, -((ay-cy)*(bx-cx))), so points closer to an edge than its round-off (a few ulp of the squared
+ *     coordinate range) may fall on either side.
+ *   verts   [dev] (n_sets, max_vertices, 2)   out, unused slots NaN
+ *   n_verts [dev] (n_sets) int32              out, the true vertex count (also when it exceeds max_vertices)
+ *   area    [dev] (n_sets)                    out, shoelace formula over the output order (about the first vertex)
+ *   src     [dev] (n_sets, max_vertices) int32 out or NULL, unused slots -1
+ *   info    [dev] (n_sets) uint32             out, GPMPC_HULL_* bits
+ * Limits: n_points < 2^31; any number of sets up to 4096 points per set, at most 65535 sets above that; max_vertices >= 3 and
+ * no upper limit - neither the survivors of the chunk passes nor the hull itself are capped, more than 4096 candidate points
+ * are wrapped from global memory instead of LDS.  Above 4096 points per set the workspace holds two (n_sets, n_points) vertex
+ * lists of 20 B per slot (worst case: every point a vertex; only survivors are ever written).
+ * All launches go to `stream`; there is no host round trip.  GPMPC_E_ARG (before any device work): NULL pointer other than
+ * src, n_points < 1, n_sets < 1, max_vertices < 3, ws_bytes < gpmpc_hull_workspace_bytes().
+ */
+#define GPMPC_HULL_OVERFLOW    0x1u  /* more than max_vertices vertices: verts / src of this set unspecified, call returns 0 */
+#define GPMPC_HULL_NONFINITE   0x2u  /* at least one point of the set was ignored                                           */
+#define GPMPC_HULL_EMPTY       0x4u  /* no finite point: n_verts 0                                                           */
+#define GPMPC_HULL_DEGENERATE  0x8u  /* 2 vertices or fewer                                                                   */
+size_t  gpmpc_hull_workspace_bytes(int n_points, int n_sets, int max_vertices);
+int     gpmpc_convex_hulls(const double* px, const double* py, long long stride_point, long long stride_set, int n_points,
+                           int n_sets, int max_vertices, double* verts, int* n_verts, double* area, int* src /* may be NULL */,
+                           unsigned* info, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

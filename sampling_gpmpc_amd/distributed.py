@@ -320,3 +320,27 @@ def gather_jacobians(arrays, Ns: int, group=None, dst: int = 0):
         out.append(np.ascontiguousarray(full[..., c0:c0 + w]))
         c0 += w
     return tuple(out)
+
+
+def all_gather_hulls(local, group=None):
+    """Per-step hulls of a sample-sharded tube without moving the tube: every rank takes the hulls of its shard
+    (``hulls.convex_hulls``), one ``all_gather_into_tensor`` moves the fixed-size ``(n_sets, max_vertices, 2)`` vertex buffers
+    (164 KB per rank at H = 40 and 256 vertices, against the 43 MB shard), and every rank merges them:
+    hull(A u B) = hull(hull A u hull B).  ``local`` is the rank's ``HullSet``.  Nothing here waits on the host: a set that had
+    overflowed on any rank comes out marked HULL_OVERFLOW on every rank (``raise_on_overflow()`` on the result)."""
+    from .hulls import HullSet, merge_hulls
+    world = dist.get_world_size(group)
+    n_sets, mv = local.n_sets, local.max_vertices
+    # the info word rides in one extra slot of the buffer (small integers are exact in float64): still one collective
+    v = torch.empty(n_sets, mv + 1, 2, dtype=local.verts.dtype, device=local.verts.device)
+    v[:, :mv] = local.verts
+    v[:, mv, 0] = local.info.to(v.dtype)
+    v[:, mv, 1] = 0.0
+    gathered = torch.empty((world,) + tuple(v.shape), dtype=v.dtype, device=v.device)
+    dist.all_gather_into_tensor(gathered, v, group=group)
+    parts = []
+    for r in range(world):                               # counts from the NaN padding; the ranks' areas are not gathered
+        pv = gathered[r, :, :mv]
+        parts.append(HullSet(pv, (~torch.isnan(pv[:, :, 0])).sum(dim=1).to(local.n_verts.dtype),
+                             torch.full_like(local.area, float("nan")), gathered[r, :, mv, 0].to(local.info.dtype)))
+    return merge_hulls(parts, max_vertices=mv)

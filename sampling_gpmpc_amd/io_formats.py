@@ -13,6 +13,9 @@ that its post-processing scripts can consume GPU results:
 * ``X_traj_list_<k>.pkl`` - reference ``benchmarking/simulate_true_reachable_set.py:263-273``: a list of ``H+1``
   tensors ``(N, g_ny, 1, nx+nu)`` (state in ``[..., :nx]``, applied input in ``[..., nx:]``, the state replicated over the
   ``g_ny`` batch axis), consumed by ``extra/cdc_plt.py:155-176``.
+* ``data_convex_hull_<tag>.pkl`` - reference ``benchmarking/generate_convex_hull.py:102-104``: a pickled list with one
+  ``(n_v, 2)`` float64 array of hull vertices per time step 1..H (what ``HullSet.to_list()`` returns), read by the
+  reference's plotting scripts (``extra/cdc_plt.py``, ``extra/plot_car_reachable_sets.py``).
 
 The reference pickles with ``dill`` (imported as ``pickle``); plain numpy arrays / torch CPU tensors pickled with either
 module are mutually readable, so ``dill`` is used when importable and the standard library otherwise.
@@ -119,5 +122,24 @@ def save_x_traj_list(save_dir: str, k: int, X_traj, U, g_ny: int) -> str:
 
 
 def load_x_traj_list(path: str):
+    with open(path, "rb") as f:
+        return _pickle.load(f)
+
+
+def convex_hull_path(save_dir: str, tag) -> str:
+    return os.path.join(save_dir, f"data_convex_hull_{tag}.pkl")
+
+
+def save_convex_hull(save_dir: str, hull_list, tag) -> str:
+    """Write the per-step hull vertex list as generate_convex_hull.py:102-104 does (there the tag is ``N200``)."""
+    hl = [np.ascontiguousarray(h, dtype=np.float64).reshape(-1, 2) for h in hull_list]
+    os.makedirs(save_dir, exist_ok=True)
+    path = convex_hull_path(save_dir, tag)
+    with open(path, "wb") as f:
+        _pickle.dump(hl, f)
+    return path
+
+
+def load_convex_hull(path: str):
     with open(path, "rb") as f:
         return _pickle.load(f)
