@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GPMPC_ABI_VERSION 10
+#define GPMPC_ABI_VERSION 11
 
 #define GPMPC_MAX_NY 4   /* GP outputs            (reference agent.g_dim.ny : 1 pendulum1D, 3 car)          */
 #define GPMPC_MAX_D  4   /* GP input dimension    (g_nx + g_nu : 2 in all shipped configs)                 */
@@ -445,6 +445,60 @@ size_t  gpmpc_hull_workspace_bytes(int n_points, int n_sets, int max_vertices);
 int     gpmpc_convex_hulls(const double* px, const double* py, long long stride_point, long long stride_set, int n_points,
                            int n_sets, int max_vertices, double* verts, int* n_verts, double* area, int* src /* may be NULL */,
                            unsigned* info, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * gpmpc_hull_query (ABI 11) - query points against the hulls gpmpc_convex_hulls wrote: signed distance to the boundary of
+ * the point's own set, containment counts per set, worst margin and first set outside per point.
+ * Replaces: the host side of the reference's containment questions - benchmarking/generate_convex_hull.py:107-126 (the true
+ * trajectory drawn over the hulls), extra/reachable_set_coverage.py:75-92 (the sampled set against the true one, X_traj_list of
+ * simulate_true_reachable_set.py), and the offline check that the hull of few samples lies inside the hull of many.
+ *
+ * Input: verts (n_sets, max_vertices, 2) counter-clockwise with NaN padding and n_verts (n_sets), exactly as
+ * gpmpc_convex_hulls leaves them, and the query points with that entry point's addressing: point i of set s is
+ * (qx[s*stride_set + i*stride_point], qy[same]), strides in doubles - a tube (Nq, nx, H+1) is queried in place in any two state
+ * dimensions, a packed (n_sets, n, 2) buffer likewise.  Point i of set s is tested against hull s only.
+ *
+ * Semantics
+ *   - margin(i, s) = +-dist, dist the Euclidean distance from the point to the nearest edge segment of hull s (segment j runs
+ *     from vertex j to vertex j+1, the last one back to vertex 0; the closest point's parameter is clamped to [0, 1] and is 0
+ *     at the edge's first end point, so a hull's own vertices have |margin| == 0.0 exactly);
+ *   - the sign is + when the hull has at least 3 vertices and orient(v_j, v_j+1, p) >= 0 for every edge j - the orientation
+ *     expression gpmpc_convex_hulls built the hull with, fma(ax-cx, by-cy, -((ay-cy)*(bx-cx))), same operand order - else -;
+ *   - the point is INSIDE iff margin >= -tol (closed set: dist == 0 is inside whatever the round-off of the sign says);
+ *   - 1 vertex: minus the distance to it (+-0 at the point); 2 vertices: minus the distance to the segment; 0 vertices
+ *     (GPMPC_HULL_EMPTY): -inf, and the set carries GPMPC_HULLQ_EMPTY_HULL;
+ *   - n_verts < 0 or > max_vertices (an overflowed hull, vertices unspecified): the set's margins are NaN, its counts 0, its
+ *     min_margin NaN, argmin -1, and it carries GPMPC_HULLQ_BAD_HULL; the per-point outputs ignore the set;
+ *   - a query point with a non-finite coordinate (failed chains leave NaN): its margin is NaN, it is counted in neither
+ *     n_inside nor n_finite, every reduction ignores it, and the set carries GPMPC_HULLQ_NONFINITE.
+ * Outputs - each may be NULL (not wanted), at least one must be given:
+ *   margin     [dev] (n_points, n_sets)        set index fastest: the tube's own order
+ *   n_inside   [dev] (n_sets) int32            points with margin >= -tol
+ *   n_finite   [dev] (n_sets) int32            points with a margin that is not NaN
+ *   min_margin [dev] (n_sets)                  minimum over those points (-inf for an empty hull), NaN if there is none
+ *   argmin     [dev] (n_sets) int32            the lowest point index attaining it, -1 if none
+ *   info       [dev] (n_sets) uint32           GPMPC_HULLQ_* bits
+ *   worst      [dev] (n_points)                minimum over the sets of the point's margins that are not NaN, NaN if none
+ *   first_out  [dev] (n_points) int32          the smallest s with margin < -tol, -1 if never
+ * The reductions are taken from the very values that are (or would be) written to margin - they equal what a host reduction of
+ * the returned matrix gives - and are the same bits with or without margin, on every run and for every geometry: each is a
+ * count, an OR, or a minimum whose ties (+0 and -0 compare equal) go to the lowest index.  No atomics are used; the per-set
+ * results go through one 24-byte record per (64-point tile, set) in the workspace and a finishing kernel.
+ * Limits: n_points < 2^31; no cap on n_sets or max_vertices (the edges of the first 32 vertices of a set are kept on chip, the
+ * rest are read from verts); edges shorter than about 1e-154 or coordinates above about 1e154 (|e|^2 under- or overflows) are
+ * measured to their first end point only; distances carry the round-off of ordinary FP64, a few ulp of the coordinate range.
+ * All launches go to `stream`; there is no host round trip.  GPMPC_E_ARG (before any device work): NULL verts, n_verts, qx or
+ * qy; all outputs NULL; n_points < 1, n_sets < 1, max_vertices < 1; tol < 0 or NaN; ws_bytes <
+ * gpmpc_hull_query_workspace_bytes() (ws itself may only be NULL when no per-set output is wanted).
+ */
+#define GPMPC_HULLQ_BAD_HULL    0x1u  /* n_verts outside [0, max_vertices]: the set was not queried                          */
+#define GPMPC_HULLQ_NONFINITE   0x2u  /* at least one query point of the set was ignored                                      */
+#define GPMPC_HULLQ_EMPTY_HULL  0x4u  /* the hull has no vertex: every margin of the set is -inf                              */
+size_t  gpmpc_hull_query_workspace_bytes(int n_points, int n_sets, int max_vertices);
+int     gpmpc_hull_query(const double* verts, const int* n_verts, int n_sets, int max_vertices, const double* qx,
+                         const double* qy, long long stride_point, long long stride_set, int n_points, double tol,
+                         double* margin, int* n_inside, int* n_finite, double* min_margin, int* argmin, unsigned* info,
+                         double* worst, int* first_out, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

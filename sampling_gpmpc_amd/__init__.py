@@ -6,7 +6,9 @@ from .agent import Agent, random_vector_within_bounds                   # noqa: 
 from .environments import make_env, Pendulum, CarKinematicsModel        # noqa: F401
 from .reachable_set import get_reachable_set_ball                       # noqa: F401
 from . import _lib                                                      # noqa: F401
-from .hulls import HullSet, HullAccumulator, convex_hulls, merge_hulls, hull_area_ratio  # noqa: F401
+from .hulls import (HullSet, HullAccumulator, convex_hulls, merge_hulls, hull_area_ratio,  # noqa: F401
+                    HullQuery, hull_query, tube_coverage)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
-           "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio"]
+           "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
+           "HullQuery", "hull_query", "tube_coverage"]

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgpmpc_hip.so")
 
 MAX_NY, MAX_D, MAX_T, MAX_NX, MAX_NU = 4, 4, 5, 8, 4
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 ENV_PENDULUM1D, ENV_CAR_RESIDUAL = 0, 1
 MODE_INDEPENDENT, MODE_RECONDITIONED = 0, 1
@@ -30,6 +30,8 @@ INFO_EIGH_NOCONV = 0x0100
 INFO_STATE_FULL = 0x0200
 # gpmpc_convex_hulls: per-set info word
 HULL_OVERFLOW, HULL_NONFINITE, HULL_EMPTY, HULL_DEGENERATE = 0x1, 0x2, 0x4, 0x8
+# gpmpc_hull_query: per-set info word
+HULLQ_BAD_HULL, HULLQ_NONFINITE, HULLQ_EMPTY_HULL = 0x1, 0x2, 0x4
 
 ROOT_AUTO, ROOT_EIGH, ROOT_CHOLESKY = 0, 1, 2
 # gpmpc_rollout_pin_kernel / gpmpc_rollout_last_kernel (include/gpmpc_hip.h)
@@ -91,6 +93,9 @@ SYMBOLS = {
     "gpmpc_hull_workspace_bytes": (_SZ, [C.c_int, C.c_int, C.c_int]),
     "gpmpc_convex_hulls": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P,
                                      _P, _SZ, _P]),
+    "gpmpc_hull_query_workspace_bytes": (_SZ, [C.c_int, C.c_int, C.c_int]),
+    "gpmpc_hull_query": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_longlong, C.c_longlong, C.c_int, _D,
+                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

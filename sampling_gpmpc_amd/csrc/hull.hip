@@ -25,6 +25,7 @@
 // of two equal points the lower source index wins (the `src` rule).  The march starts at the lexicographic minimum and runs
 // counter-clockwise until it is back there; it is cut off after as many steps as there are points.
 #include "gpmpc_host.hpp"
+#include "hull_geom.hpp"   // finite2, orient
 
 #include <cmath>
 #include <cstdlib>
@@ -54,13 +55,6 @@ struct HullIn {
     const int* count;       // NULL: n points in every set
     int n;
 };
-
-__device__ __forceinline__ bool finite2(double x, double y) { return fabs(x) < INFINITY && fabs(y) < INFINITY; }
-
-__device__ __forceinline__ double orient(double cx, double cy, double ax, double ay, double bx, double by) {
-    const double dax = ax - cx, day = ay - cy, dbx = bx - cx, dby = by - cy;
-    return fma(dax, dby, -(day * dbx));
-}
 
 struct PickLexMin {
     __device__ __forceinline__ Cand operator()(const Cand& a, const Cand& b) const {

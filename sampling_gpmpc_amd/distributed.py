@@ -344,3 +344,39 @@ def all_gather_hulls(local, group=None):
         parts.append(HullSet(pv, (~torch.isnan(pv[:, :, 0])).sum(dim=1).to(local.n_verts.dtype),
                              torch.full_like(local.area, float("nan")), gathered[r, :, mv, 0].to(local.info.dtype)))
     return merge_hulls(parts, max_vertices=mv)
+
+
+def all_reduce_hull_query(q, group=None):
+    """The per-set results of a ``hulls.hull_query`` of a sample-sharded query tube against replicated hulls (those of
+    ``all_gather_hulls``), over the whole tube: ``n_inside`` and ``n_finite`` are summed, ``min_margin`` is the minimum, ``info``
+    is ORed, and ``argmin`` becomes the GLOBAL sample index - the shard's first index is the number of points on the ranks
+    below it, which is ``shard_range``'s for its contiguous shards - with the lowest index among equal minima, as on one
+    device.  The per-point outputs (``margin``, ``worst``, ``first_out``) stay local.  Returns a new ``HullQuery``; works on
+    the tensors' own device (CPU tensors under gloo).  Three small collectives, no host wait."""
+    import dataclasses
+    if q.n_inside is None:
+        raise ValueError("all_reduce_hull_query needs the per-set outputs (hull_query(..., per_set=True))")
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    n_sets, dev = q.n_inside.shape[0], q.n_inside.device
+    # one SUM carries the counts, the info bits (a sum > 0 is the OR: RCCL has no bitwise reduction) and every shard's size
+    bits = torch.stack([(q.info.to(torch.int64) >> b) & 1 for b in range(8)]).reshape(-1)          # HULLQ_* uses 3
+    sizes = torch.zeros(world, dtype=torch.int64, device=dev)
+    sizes[rank] = int(q.n_points)
+    packed = torch.cat([q.n_inside.to(torch.int64), q.n_finite.to(torch.int64), bits, sizes])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    n_inside, n_finite = packed[:n_sets].to(q.n_inside.dtype), packed[n_sets:2 * n_sets].to(q.n_finite.dtype)
+    got = (packed[2 * n_sets:10 * n_sets].reshape(8, n_sets) > 0).to(torch.int64)
+    info = sum(got[b] << b for b in range(8)).to(q.info.dtype)
+    lo = packed[10 * n_sets:][:rank].sum()
+    # a shard without a finite point (NaN) takes no part in the minimum
+    m = torch.where(torch.isnan(q.min_margin), torch.full_like(q.min_margin, float("inf")), q.min_margin)
+    dist.all_reduce(m, op=dist.ReduceOp.MIN, group=group)
+    # every rank whose own minimum equals the global one proposes its global index, the lowest wins
+    big = torch.iinfo(torch.int64).max
+    local = q.argmin.to(torch.int64)
+    idx = torch.where((local >= 0) & (q.min_margin == m), local + lo, torch.full_like(local, big))
+    dist.all_reduce(idx, op=dist.ReduceOp.MIN, group=group)
+    none = idx == big
+    return dataclasses.replace(q, n_points=int(q.n_points), n_inside=n_inside, n_finite=n_finite,
+                               min_margin=torch.where(none, torch.full_like(m, float("nan")), m),
+                               argmin=torch.where(none, torch.full_like(idx, -1), idx).to(q.argmin.dtype), info=info)

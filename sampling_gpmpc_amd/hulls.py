@@ -6,6 +6,11 @@ areas).  The hulls are taken by ``gpmpc_convex_hulls`` (csrc/hull.hip) straight 
 ``(Ns, nx, H+1)`` - no copy, no transposition - and what leaves the device is ``(H+1, max_vertices, 2)`` instead of the tube.
 Semantics (strict hull, counter-clockwise from the lexicographic minimum, degenerate and non-finite input) are those of the
 entry point, include/gpmpc_hip.h.  There is no CPU fallback.
+
+The containment questions the hulls exist for (``generate_convex_hull.py:107-126`` draws the true trajectory over them,
+``extra/reachable_set_coverage.py:75-92`` compares the sampled set with the true one) are answered on the device as well:
+``hull_query`` tests a tube or a packed point buffer against the hulls through ``gpmpc_hull_query`` (csrc/hull_query.hip),
+``tube_coverage`` and ``HullSet.contains`` are built on it.
 """
 from __future__ import annotations
 
@@ -17,7 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import HULL_DEGENERATE, HULL_EMPTY, HULL_NONFINITE, HULL_OVERFLOW, GpmpcError  # noqa: F401
+from ._lib import (HULL_DEGENERATE, HULL_EMPTY, HULL_NONFINITE, HULL_OVERFLOW, HULLQ_BAD_HULL, HULLQ_EMPTY_HULL,  # noqa: F401
+                   HULLQ_NONFINITE, GpmpcError)
 
 
 @dataclass
@@ -58,6 +64,19 @@ class HullSet:
     def areas(self) -> np.ndarray:
         return _lib.to_host(self.area)
 
+    def contains(self, other: "HullSet", tol: float = 0.0) -> "HullQuery":
+        """The vertices of ``other`` against these hulls, set by set: ``other``'s set s lies inside this one's iff
+        ``n_inside[s] == n_finite[s]`` (a convex set contains a hull iff it contains its vertices).  The point index of the
+        result is ``other``'s vertex slot; its NaN padding is ignored like any non-finite point, and HULLQ_NONFINITE of the
+        result says whether ``other`` itself had ignored a point of its input (as ``merge_hulls`` folds it).  A set that had
+        overflowed in ``other`` is compared by the vertices that fitted."""
+        if other.n_sets != self.n_sets:
+            raise GpmpcError(f"contains: {other.n_sets} sets against {self.n_sets}")
+        q = hull_query(self, other.verts, layout="packed", tol=tol)
+        carried = ((other.info & HULL_NONFINITE) != 0).to(q.info.dtype) * HULLQ_NONFINITE
+        q.info = (q.info & ~HULLQ_NONFINITE) | carried
+        return q
+
 
 def _check_points(X: torch.Tensor) -> None:
     if not torch.is_tensor(X) or X.dim() != 3:
@@ -67,12 +86,8 @@ def _check_points(X: torch.Tensor) -> None:
         raise GpmpcError("convex_hulls takes float64 points")
 
 
-def convex_hulls(X: torch.Tensor, dims: Sequence[int] = (0, 1), max_vertices: int = 256, with_src: bool = False,
-                 layout: str = "auto") -> HullSet:
-    """Convex hulls of every time step of a tube ``X (Ns, nx, H+1)`` in the state dimensions ``dims``, or of every set of a packed
-    buffer ``X (n_sets, n, 2)`` (NaN rows are padding).  ``layout`` is "tube", "packed" or "auto": auto takes a last axis of
-    length 2 for a packed buffer, so a tube of horizon 1, ``(Ns, nx, 2)``, must be passed with ``layout="tube"``.  ``X`` is read
-    through its strides: any view is taken as it is."""
+def _addressing(X: torch.Tensor, dims: Sequence[int], layout: str):
+    """-> (px, py, stride_point, stride_set, n_points, n_sets) of the entry points' addressing for a tube or a packed buffer."""
     _check_points(X)
     if layout == "auto":
         layout = "packed" if X.shape[2] == 2 else "tube"
@@ -92,6 +107,16 @@ def convex_hulls(X: torch.Tensor, dims: Sequence[int] = (0, 1), max_vertices: in
         stride_point, stride_set = X.stride(1), X.stride(0)
     else:
         raise GpmpcError(f"unknown layout {layout!r}")
+    return px, py, stride_point, stride_set, int(n_points), int(n_sets)
+
+
+def convex_hulls(X: torch.Tensor, dims: Sequence[int] = (0, 1), max_vertices: int = 256, with_src: bool = False,
+                 layout: str = "auto") -> HullSet:
+    """Convex hulls of every time step of a tube ``X (Ns, nx, H+1)`` in the state dimensions ``dims``, or of every set of a packed
+    buffer ``X (n_sets, n, 2)`` (NaN rows are padding).  ``layout`` is "tube", "packed" or "auto": auto takes a last axis of
+    length 2 for a packed buffer, so a tube of horizon 1, ``(Ns, nx, 2)``, must be passed with ``layout="tube"``.  ``X`` is read
+    through its strides: any view is taken as it is."""
+    px, py, stride_point, stride_set, n_points, n_sets = _addressing(X, dims, layout)
     lib = _lib.load()
     dev = X.device
     mv = int(max_vertices)
@@ -108,6 +133,75 @@ def convex_hulls(X: torch.Tensor, dims: Sequence[int] = (0, 1), max_vertices: in
                                           _lib.dptr(out.info), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()),
                    "gpmpc_convex_hulls")
     return out
+
+
+@dataclass
+class HullQuery:
+    """Device tensors of one ``hull_query`` call (``None`` where the output was not asked for): ``margin (n_points, n_sets)``
+    signed distance to the hull's boundary (+ inside, NaN for a non-finite point or an overflowed hull); per set ``n_inside``,
+    ``n_finite``, ``min_margin``, ``argmin`` (lowest point index attaining it, -1: none) and ``info`` (``HULLQ_*`` bits); per
+    point ``worst`` (minimum over the sets) and ``first_out`` (first set with ``margin < -tol``, -1: never).  ``n_points`` is
+    the number of query points per set, ``tol`` the tolerance the counts were taken with."""
+    tol: float
+    n_points: int
+    margin: Optional[torch.Tensor] = None
+    n_inside: Optional[torch.Tensor] = None
+    n_finite: Optional[torch.Tensor] = None
+    min_margin: Optional[torch.Tensor] = None
+    argmin: Optional[torch.Tensor] = None
+    info: Optional[torch.Tensor] = None
+    worst: Optional[torch.Tensor] = None
+    first_out: Optional[torch.Tensor] = None
+
+
+def hull_query(h: HullSet, X: torch.Tensor, dims: Sequence[int] = (0, 1), layout: str = "auto", tol: float = 0.0,
+               margins: bool = True, per_set: bool = True, per_point: bool = True) -> HullQuery:
+    """Every point of a tube ``X (Nq, nx, H+1)`` (state dimensions ``dims``) or of a packed buffer ``X (n_sets, n, 2)`` against
+    the hull of its own step / set in ``h``.  ``layout`` and the stride handling are those of ``convex_hulls``; semantics of
+    the margin and of ``tol`` are the entry point's (include/gpmpc_hip.h).  ``margins`` / ``per_set`` / ``per_point`` choose the
+    outputs; the reductions are the same bits whether or not the matrix is asked for.  No host synchronisation."""
+    px, py, stride_point, stride_set, n_points, n_sets = _addressing(X, dims, layout)
+    if n_sets != h.n_sets:
+        raise GpmpcError(f"hull_query: the points have {n_sets} sets, the hulls {h.n_sets}")
+    if not (margins or per_set or per_point):
+        raise GpmpcError("hull_query: no output asked for")
+    _lib.require_hip_device(h.verts.device)
+    if h.verts.device != X.device:
+        raise GpmpcError("hull_query: hulls and points are on different devices")
+    tol = float(tol)
+    lib = _lib.load()
+    dev = X.device
+    mv = h.max_vertices
+    ws_bytes = int(lib.gpmpc_hull_query_workspace_bytes(n_points, n_sets, mv))
+    with torch.cuda.device(dev):
+        def new(shape, dtype, want):
+            return torch.empty(shape, dtype=dtype, device=dev) if want else None
+        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        q = HullQuery(tol=tol, n_points=n_points, margin=new((n_points, n_sets), torch.float64, margins),
+                      n_inside=new(n_sets, torch.int32, per_set), n_finite=new(n_sets, torch.int32, per_set),
+                      min_margin=new(n_sets, torch.float64, per_set), argmin=new(n_sets, torch.int32, per_set),
+                      info=new(n_sets, torch.int32, per_set), worst=new(n_points, torch.float64, per_point),
+                      first_out=new(n_points, torch.int32, per_point))
+        verts, n_verts = h.verts.contiguous(), h.n_verts.contiguous()
+        _lib.check(lib.gpmpc_hull_query(_lib.dptr(verts), _lib.dptr(n_verts), n_sets, mv, px, py, stride_point, stride_set,
+                                        n_points, tol, _lib.dptr(q.margin), _lib.dptr(q.n_inside), _lib.dptr(q.n_finite),
+                                        _lib.dptr(q.min_margin), _lib.dptr(q.argmin), _lib.dptr(q.info), _lib.dptr(q.worst),
+                                        _lib.dptr(q.first_out), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()),
+                   "gpmpc_hull_query")
+    return q
+
+
+def tube_coverage(h: HullSet, X_true: torch.Tensor, dims: Sequence[int] = (0, 1), tol: float = 0.0):
+    """How much of a tube of true trajectories ``X_true (N, nx, H+1)`` the sampled reachable sets ``h`` contain (the question
+    of reference extra/reachable_set_coverage.py:75-92): ``(per_step_fraction (H+1,), whole_trajectory_fraction)``, fractions
+    of the finite points of a step / of the trajectories with at least one finite point; a trajectory counts whole when none
+    of its finite steps lies outside (``first_out == -1``).  NaN where there is nothing finite.  One host read at the end."""
+    q = hull_query(h, X_true, dims=dims, layout="tube", tol=tol, margins=False)
+    per_step = q.n_inside.to(torch.float64) / q.n_finite.to(torch.float64)          # 0 / 0 = NaN
+    alive = ~torch.isnan(q.worst)
+    whole = ((q.first_out < 0) & alive).sum().to(torch.float64) / alive.sum().to(torch.float64)
+    out = _lib.to_host(torch.cat([per_step, whole.reshape(1)]))
+    return out[:-1].copy(), float(out[-1])
 
 
 def merge_hulls(hulls: Sequence[HullSet], max_vertices: Optional[int] = None, with_src: bool = False) -> HullSet:
