@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GPMPC_ABI_VERSION 11
+#define GPMPC_ABI_VERSION 12
 
 #define GPMPC_MAX_NY 4   /* GP outputs            (reference agent.g_dim.ny : 1 pendulum1D, 3 car)          */
 #define GPMPC_MAX_D  4   /* GP input dimension    (g_nx + g_nu : 2 in all shipped configs)                 */
@@ -499,6 +499,51 @@ int     gpmpc_hull_query(const double* verts, const int* n_verts, int n_sets, in
                          const double* qy, long long stride_point, long long stride_set, int n_points, double tol,
                          double* margin, int* n_inside, int* n_finite, double* min_margin, int* argmin, unsigned* info,
                          double* worst, int* first_out, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * gpmpc_sup_deviation (ABI 12) - the sup-norm deviation of Ns joint posterior samples on a grid of n points, per sample and as
+ * counts within eps: the small-ball probability of the GP posterior, from which the reference chooses the number of dynamics
+ * samples (N = log(delta) / log(1 - exp(-2 C_D) p_ball)).
+ * Replaces: reference extra/compute_num_samples/helper.py:116-245 (one output), helper.py:247-365 (all outputs jointly, with the
+ * BatchMultitaskGPModelWithDerivatives_fromParams(use_grad=False) model), helper.py:368-469 and helper.py:473-594 (the quantile
+ * forms, the second with per-output scale factors, helper.py:576-579), extra/compute_num_samples/small_ball_probability.py:106-130
+ * and extra/compute_num_samples/num_of_samples_car.py:77-89 - 10^5 .. 10^7 draws of model_call.sample(), samples - mean, abs, max,
+ * compare, each a pass over (Ns, g_ny n) doubles.  Here the draws never exist in memory: 8 bytes per sample leave the device, or
+ * a handful of counters.
+ *
+ * The stream: sample s has the global id offset + s; entry e = o*n + i of its base vector is EXACTLY entry e of vector s that
+ * gpmpc_base_samples(seed, 1, 1, offset, Ns, V = g_ny*n, beta = +inf, ...) writes (attempt 0, nothing rejected: the reference's
+ * small-ball draws are unbounded normals).  A sample's result depends on (seed, global id, root, scale) alone - not on Ns, on how
+ * a run is cut into calls, or on the number of devices that share it.
+ * Per sample: d_{o,i} = sum_j R_o[i][j] z_{o,j};  dev_o = scale_o * max_i |d_{o,i}|;  dev = max_o dev_o.
+ *
+ *   root         [dev]  (g_ny, n, n) row-major, ANY matrix with R R^T = Sigma_o (Cholesky factor, or the eigendecomposition root
+ *                       of gpmpc_joint_sample with its zero leading columns)
+ *   scale        [host] (g_ny) or NULL (= 1), each >= 0
+ *   eps          [host] (n_eps), n_eps 0..16, each >= 0
+ *   maxdev       [dev]  (Ns)            out or NULL: dev
+ *   maxdev_out   [dev]  (Ns, g_ny)      out or NULL: dev_o
+ *   n_within     [dev]  (n_eps) int64   out or NULL: samples with dev <= eps[k] (closed ball, helper.py:237)
+ *   n_within_out [dev]  (g_ny, n_eps) int64 out or NULL: samples with dev_o <= eps[k]
+ *   n_nonfinite  [dev]  (1) int64       out or NULL: samples whose dev is NaN or infinite
+ * Semantics
+ *   - a NaN d_{o,i} makes dev_o and dev NaN (the maxima do not drop it); such a sample is counted in n_nonfinite and in no
+ *     n_within; an infinite dev is counted in n_nonfinite as well;
+ *   - the counts equal what a host reduction of the values written to maxdev / maxdev_out gives, and are the same bits with or
+ *     without those outputs, on every run and for every launch geometry: they are integer sums, taken through one record per wave
+ *     in the workspace and a finishing kernel, without atomics;
+ *   - the dot products run on v_mfma_f64_16x16x4_f64 in a fixed K order: values differ from another summation order by the usual
+ *     bound of a length-n dot product.
+ * Limits: 1 <= g_ny <= GPMPC_MAX_NY, 1 <= n <= 128 (GPMPC_E_UNSUPPORTED above), Ns >= 1, offset >= 0.
+ * All launches go to `stream`; no hidden allocation, no host round trip.  GPMPC_E_ARG (before any device work): NULL root; every
+ * output NULL; g_ny, n, Ns or offset out of range; n_eps outside 0..16; n_eps > 0 with NULL eps; a negative or NaN eps / scale;
+ * n_within or n_within_out with n_eps == 0; ws_bytes < gpmpc_sup_deviation_workspace_bytes() (ws itself may only be NULL when no
+ * count is wanted).
+ */
+size_t  gpmpc_sup_deviation_workspace_bytes(int32_t g_ny, int32_t n, int64_t Ns, int32_t n_eps);
+int     gpmpc_sup_deviation(int32_t g_ny, int32_t n, const double* root, const double* scale, uint64_t seed, int64_t offset,
+                            int64_t Ns, const double* eps, int32_t n_eps, double* maxdev, double* maxdev_out, int64_t* n_within,
+                            int64_t* n_within_out, int64_t* n_nonfinite, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,10 @@ from .reachable_set import get_reachable_set_ball                       # noqa: 
 from . import _lib                                                      # noqa: F401
 from .hulls import (HullSet, HullAccumulator, convex_hulls, merge_hulls, hull_area_ratio,  # noqa: F401
                     HullQuery, hull_query, tube_coverage)
+from .small_ball import (SmallBall, reference_grid, posterior_on_grid, sup_deviation, small_ball_probability,  # noqa: F401
+                         sup_deviation_quantile, required_samples)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
-           "HullQuery", "hull_query", "tube_coverage"]
+           "HullQuery", "hull_query", "tube_coverage", "SmallBall", "reference_grid", "posterior_on_grid", "sup_deviation",
+           "small_ball_probability", "sup_deviation_quantile", "required_samples"]

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgpmpc_hip.so")
 
 MAX_NY, MAX_D, MAX_T, MAX_NX, MAX_NU = 4, 4, 5, 8, 4
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 ENV_PENDULUM1D, ENV_CAR_RESIDUAL = 0, 1
 MODE_INDEPENDENT, MODE_RECONDITIONED = 0, 1
@@ -96,6 +96,9 @@ SYMBOLS = {
     "gpmpc_hull_query_workspace_bytes": (_SZ, [C.c_int, C.c_int, C.c_int]),
     "gpmpc_hull_query": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.c_longlong, C.c_longlong, C.c_int, _D,
                                    _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gpmpc_sup_deviation_workspace_bytes": (_SZ, [_I32, _I32, _I64, _I32]),
+    "gpmpc_sup_deviation": (C.c_int, [_I32, _I32, _P, C.POINTER(C.c_double), C.c_uint64, _I64, _I64, C.POINTER(C.c_double), _I32,
+                                      _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

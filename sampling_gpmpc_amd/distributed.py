@@ -380,3 +380,26 @@ def all_reduce_hull_query(q, group=None):
     return dataclasses.replace(q, n_points=int(q.n_points), n_inside=n_inside, n_finite=n_finite,
                                min_margin=torch.where(none, torch.full_like(m, float("nan")), m),
                                argmin=torch.where(none, torch.full_like(idx, -1), idx).to(q.argmin.dtype), info=info)
+
+
+def all_reduce_small_ball(result, group=None):
+    """The counts of a ``small_ball.sup_deviation`` run whose samples are spread over the ranks, each rank having drawn its own
+    ``offset`` slice of the global sample ids (the stream makes the union the run one device would have made): ``n_within``,
+    ``n_within_out``, ``n_nonfinite`` and ``Ns`` are summed.  Every rank must have asked for the same outputs and thresholds.  The
+    per-sample outputs (``maxdev``, ``maxdev_out``) stay local.  Returns a new ``SmallBall``; works on the tensors' own device
+    (CPU tensors under gloo).  One collective, no host wait beyond reading the summed ``Ns``."""
+    import dataclasses
+    parts = [t for t in (result.n_within, result.n_within_out, result.n_nonfinite) if t is not None]
+    if not parts:
+        raise ValueError("all_reduce_small_ball needs a count output")
+    dev = parts[0].device
+    packed = torch.cat([torch.tensor([int(result.Ns)], dtype=torch.int64, device=dev)] + [t.reshape(-1).to(torch.int64) for t in parts])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    _lib.host_wait(packed)
+    out, at = {}, 1
+    for name in ("n_within", "n_within_out", "n_nonfinite"):
+        t = getattr(result, name)
+        if t is not None:
+            out[name] = packed[at:at + t.numel()].reshape(t.shape).to(t.dtype)
+            at += t.numel()
+    return dataclasses.replace(result, Ns=int(packed[0].item()), **out)
