@@ -55,6 +55,8 @@ extern "C" {
 #define GPMPC_INFO_ROOT_EIGH         0x0080 /* y was drawn with the eigendecomposition root (A.7 step 4)    */
 #define GPMPC_INFO_EIGH_NOCONV       0x0100 /* the Jacobi eigensolver hit its sweep limit (result still used) */
 #define GPMPC_INFO_STATE_FULL        0x0200 /* gpmpc_rollout_seeded: the factor state had no room for a new point  */
+#define GPMPC_INFO_BAD_HYPER         0x0400 /* gpmpc_marginal_likelihood: a candidate entry is non-finite, ell or outputscale <= 0,
+                                             * or a noise variance < 0: every output of that problem is NaN               */
 
 /* root_mode of gpmpc_joint_sample */
 #define GPMPC_ROOT_AUTO      0   /* gpytorch: Cholesky with the jitter chain; if ANY chain of the batch fails all  */
@@ -544,6 +546,46 @@ size_t  gpmpc_sup_deviation_workspace_bytes(int32_t g_ny, int32_t n, int64_t Ns,
 int     gpmpc_sup_deviation(int32_t g_ny, int32_t n, const double* root, const double* scale, uint64_t seed, int64_t offset,
                             int64_t Ns, const double* eps, int32_t n_eps, double* maxdev, double* maxdev_out, int64_t* n_within,
                             int64_t* n_within_out, int64_t* n_nonfinite, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * gpmpc_marginal_likelihood - the exact marginal likelihood of the real data under B candidate hyperparameter sets, with its
+ * gradient: B * g_ny independent dense problems in one launch, one workgroup each.  An additive entry point: the ABI version
+ * stays 12 (nothing that existed changes; a binding that does not know the symbol keeps working).
+ * Replaces: the objective and its backward pass in the reference's fitting scripts, extra/mle_pendulum1D.py:124-155,
+ * extra/mle_car.py:80-113 and extra/mle_pendulum.py - a gpytorch ExactGP with ScaleKernel(RBFKernelGrad), ConstantMeanGrad and a
+ * MultitaskGaussianLikelihood, 50-200 Adam steps on -ExactMarginalLogLikelihood, one output and one starting point at a time - and
+ * yields the two numbers of extra/compute_num_samples/helper.py:39-85 (y^T (K + lambda I)^-1 y and, through log det, beta_data).
+ *
+ *   gp      the SHAPE only: g_ny, D, T, N_r, real_has_grad.  ell, outputscale, noise, jitter, var_floor are ignored.
+ *   X_r     [dev] (N_r, D)
+ *   Y_r     [dev] (g_ny, N_r, T)
+ *   theta   [dev] (B, g_ny, P), P = D + 1 + T + 1: one candidate of one output is
+ *                 [ell_0 .. ell_{D-1}, outputscale, nz_0 .. nz_{T-1}, c]; nz_t is the TOTAL noise variance of task t (what
+ *                 gpmpc_gp_desc_t.noise holds), c the constant prior mean of the value task (gradient tasks: mean 0)
+ *   nll     [dev] (B, g_ny)      out
+ *   grad    [dev] (B, g_ny, P)   out or NULL: d nll / d theta with respect to the NATURAL values ell, outputscale, nz, c
+ *   quad    [dev] (B, g_ny)      out or NULL
+ *   logdet  [dev] (B, g_ny)      out or NULL
+ *   info    [dev] (B, g_ny) int32 out: 0, GPMPC_INFO_BAD_HYPER or GPMPC_INFO_TRAIN_CHOL_FAIL
+ * Label rows are chosen as the plan chooses them: real_has_grad = 0: task 0 of every point; real_has_grad = 1: all T tasks,
+ * point-major and task-minor; n = N_r * (real_has_grad ? T : 1).  With r = y - m, K = K_rbf(theta) + diag(nz), alpha = K^-1 r:
+ *   quad = r^T K^-1 r;  logdet = log det K;  nll = quad/2 + logdet/2 + (n/2) log(2 pi);
+ *   grad_p = 1/2 sum_ij (K^-1 - alpha alpha^T)_ij dK_ij/dtheta_p (kernel and noise parameters);  grad_c = -sum_{value rows} alpha_i.
+ * The components of nz_t for tasks that contribute no row are exactly 0.0.
+ * Status: a candidate with a non-finite entry, ell_d <= 0, outputscale <= 0 or nz_t < 0 gets NaN in every output and
+ * GPMPC_INFO_BAD_HYPER; a non-positive pivot gives NaN outputs and GPMPC_INFO_TRAIN_CHOL_FAIL.  There is NO jitter retry:
+ * gpytorch's training path would add jitter and go on, here a population fit simply loses that candidate.  Every other problem of
+ * the launch is unaffected either way.
+ * Reproducibility: a problem's results are the same bits whatever B is, wherever the candidate sits in the batch and on every
+ * run (fixed summation orders, no atomics): candidates can be sharded over calls and devices with no further code.
+ * Limits: D = 2 (T = 1 or 3; GPMPC_E_UNSUPPORTED otherwise); 1 <= n <= 140, what an LDS-resident n x n FP64 matrix plus the
+ * kernel's vectors allows in 160 KiB (GPMPC_E_UNSUPPORTED above): the car's 45 points with all tasks are 135 rows, the
+ * pendulum's 36 points 108.  The 363-row set of mle_car.py (11 x 11 points, all tasks) is out of scope.
+ * No workspace, no host round trip, everything goes to `stream`.  GPMPC_E_ARG (before any device work): NULL gp, X_r, Y_r, theta,
+ * nll or info; B < 1; a bad descriptor.
+ */
+int     gpmpc_marginal_likelihood(const gpmpc_gp_desc_t* gp, const double* X_r, const double* Y_r, int64_t B, const double* theta,
+                                  double* nll, double* grad, double* quad, double* logdet, int32_t* info, void* stream);
 
 #ifdef __cplusplus
 }

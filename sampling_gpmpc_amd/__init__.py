@@ -10,8 +10,12 @@ from .hulls import (HullSet, HullAccumulator, convex_hulls, merge_hulls, hull_ar
                     HullQuery, hull_query, tube_coverage)
 from .small_ball import (SmallBall, reference_grid, posterior_on_grid, sup_deviation, small_ball_probability,  # noqa: F401
                          sup_deviation_quantile, required_samples)
+from .mle import (MarginalLikelihood, FitResult, marginal_likelihood, pack_theta, unpack_theta, theta_from_params,  # noqa: F401
+                  theta_to_params, fit_hyperparameters, restarts, rkhs_norm_and_beta)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
            "HullQuery", "hull_query", "tube_coverage", "SmallBall", "reference_grid", "posterior_on_grid", "sup_deviation",
-           "small_ball_probability", "sup_deviation_quantile", "required_samples"]
+           "small_ball_probability", "sup_deviation_quantile", "required_samples", "MarginalLikelihood", "FitResult",
+           "marginal_likelihood", "pack_theta", "unpack_theta", "theta_from_params", "theta_to_params", "fit_hyperparameters",
+           "restarts", "rkhs_norm_and_beta"]
