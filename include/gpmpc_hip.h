@@ -57,6 +57,8 @@ extern "C" {
 #define GPMPC_INFO_STATE_FULL        0x0200 /* gpmpc_rollout_seeded: the factor state had no room for a new point  */
 #define GPMPC_INFO_BAD_HYPER         0x0400 /* gpmpc_marginal_likelihood: a candidate entry is non-finite, ell or outputscale <= 0,
                                              * or a noise variance < 0: every output of that problem is NaN               */
+#define GPMPC_INFO_NONFINITE         0x0800 /* gpmpc_moment_rollout: an input of the candidate or a value computed for it was
+                                             * not finite: its outputs are NaN from that step on                           */
 
 /* root_mode of gpmpc_joint_sample */
 #define GPMPC_ROOT_AUTO      0   /* gpytorch: Cholesky with the jitter chain; if ANY chain of the batch fails all  */
@@ -586,6 +588,62 @@ int     gpmpc_sup_deviation(int32_t g_ny, int32_t n, const double* root, const d
  */
 int     gpmpc_marginal_likelihood(const gpmpc_gp_desc_t* gp, const double* X_r, const double* Y_r, int64_t B, const double* theta,
                                   double* nll, double* grad, double* quad, double* logdet, int32_t* info, void* stream);
+
+/*
+ * gpmpc_moment_rollout - the linearisation-based ("cautious" GP-MPC) prediction of B candidates over H steps in one launch: the
+ * posterior mean of the real-data GP propagated through the dynamics, and a state covariance propagated by the Jacobian of that
+ * map.  One candidate per lane.  An additive entry point: the ABI version stays 12.
+ * Replaces: reference benchmarking/linearization_based_predictions.py:29-31,136-185 (P_propagation; per step an autograd Jacobian
+ * of the posterior mean, model(x).mean / .variance of the model train_hallucinated_dynGP(0) builds, :100,157-161, and the
+ * covariance step), the same ingredients in benchmarking/robust_tube_based_GPMPC_koller.py:83-104,277-287 (there with the
+ * feedback gain k_fb) and in extra/zoro_code.py:34-74 (gp_sensitivities, P_propagation_with_y) - one nominal trajectory at a time
+ * on the host; here every MPC step of a closed loop, every candidate input sequence of a sampling-based planner or a grid of
+ * initial states is one call.
+ *
+ * For candidate b and t = 0..H-1, from mu_0 = x0[b] and P_0 = P0[b] (zero when P0 is NULL):
+ *   1. u_t   = U[b,t], or with env.use_feedback  u_ff + K (mu_t - x_goal)  as gpmpc_rollout applies it;
+ *   2. xi_t  = the GP input of (mu_t, u_t): pendulum1D (theta, u), car (phi, delta);
+ *   3. per output o, conditioned on the REAL data only through the plan's L_rr^-1 and alpha_r:
+ *        m_o   = k_o(xi)^T alpha_o
+ *        s_o   = max(outputscale_o - |L_o^-1 k_o(xi)|^2, var_floor): the latent variance, no likelihood noise (model(x).variance
+ *                of the reference); raising it to the floor sets GPMPC_INFO_VAR_CLAMPED
+ *        dm_o  = d m_o / d xi (D entries) = the posterior mean of the derivative slots at xi: the derivative rows of the test
+ *                point against the labels; with real_has_grad the labels are N_r * T rows (value and gradient, point-major)
+ *                and both the value row and the derivative rows of the test point meet all of them;
+ *   4. mu_{t+1} = env_step(mu_t, u_t, m)  (the map of gpmpc_rollout);
+ *   5. A_t = the Jacobian of x -> env_step(x, fb(x), m(xi(x, fb(x)))) at mu_t: the known part, d B_d / d x . m (car: column v
+ *      receives m), B_d dm scattered to the columns the GP input selects, and with feedback the path d / d u . K.  Without
+ *      feedback this is the reference's mean_dy[0, :, 0, 0:nx], with feedback Koller's use of k_fb;
+ *   6. P_{t+1} = A_t P_t A_t^T + G_t diag(s) G_t^T,  G_t = B_d(mu_t): pendulum1D [0, 1]^T, car v I_{4x3}.  One triangle is computed
+ *      and mirrored: P is exactly symmetric (of P0 the lower triangle is read).  The dependence of s on x is ignored, as in the
+ *      reference.
+ *   x0   [dev] (B, nx) if x0_per_candidate else (nx)
+ *   U    [dev] (B, H, nu) if u_per_candidate else (H, nu)     (may be NULL when H == 0)
+ *   P0   [dev] (B, nx, nx) or NULL
+ *   M    [dev] (B, nx, H+1)      out: mu_t in the tube layout of gpmpc_rollout's X_traj (gpmpc_convex_hulls / gpmpc_hull_query
+ *                                take it as it is)
+ *   P    [dev] (B, H+1, nx, nx)  out
+ *   S    [dev] (B, H, g_ny)      out or NULL: s_o of every step
+ *   A    [dev] (B, H, nx, nx)    out or NULL: A_t
+ *   info [dev] (B) int32         out: OR of GPMPC_INFO_VAR_CLAMPED and GPMPC_INFO_NONFINITE over the steps
+ * Non-finite values: a candidate whose x0 or P0 has a non-finite entry has NaN in every output; when U[b,t] or anything computed
+ * in step t (u_t, m, s, dm, A_t, mu_{t+1}, P_{t+1}) is not finite, S and A of the steps >= t and M and P of the steps > t are NaN
+ * (the steps before keep their values).  Either way the candidate carries GPMPC_INFO_NONFINITE; no other candidate is touched.
+ * Reproducibility: a candidate's results are the same bits whatever B is and wherever it stands in the batch (one kernel path,
+ * fixed summation order, nothing shared between lanes but read-only tables).
+ * Limits (the contract): D = 2, T = 1 or 3, the two environments (pendulum1D nx 2, nu 1, g_ny 1; car nx 4, nu 2, g_ny 3), any
+ * X_r (the tensor grid is not needed and not used), at most 64 label rows: N_r <= 64 value-only, N_r * T <= 64 with
+ * real_has_grad (the shipped sets are 36 and 45 value-only rows); B < 2^31.  GPMPC_E_UNSUPPORTED beyond, before any device work.
+ * B == 0: nothing is launched, and the array pointers are not looked at (an empty array need not have an address; the
+ * descriptors and sizes are still checked); H == 0: only step 0 of M and P is written.  No workspace, no host round trip,
+ * everything goes to `stream`.  GPMPC_E_ARG (before any device work): NULL gp or env; with B > 0 NULL plan, X_r, x0, U (H > 0), M,
+ * P or info; B < 0 or H < 0; a bad gp descriptor; env.nx / env.nu / g_ny that do not belong to env.env_id.
+ */
+int     gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                             int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                             int32_t u_per_candidate, const double* P0 /* NULL or (B, nx, nx) */, double* M /* (B, nx, H+1) */,
+                             double* P /* (B, H+1, nx, nx) */, double* S /* (B, H, g_ny) or NULL */,
+                             double* A /* (B, H, nx, nx) or NULL */, int32_t* info /* (B) */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,7 @@ INFO_ROOT_EIGH = 0x0080
 INFO_EIGH_NOCONV = 0x0100
 INFO_STATE_FULL = 0x0200
 INFO_BAD_HYPER = 0x0400                                 # gpmpc_marginal_likelihood
+INFO_NONFINITE = 0x0800                                 # gpmpc_moment_rollout
 # gpmpc_convex_hulls: per-set info word
 HULL_OVERFLOW, HULL_NONFINITE, HULL_EMPTY, HULL_DEGENERATE = 0x1, 0x2, 0x4, 0x8
 # gpmpc_hull_query: per-set info word
@@ -101,6 +102,8 @@ SYMBOLS = {
     "gpmpc_sup_deviation": (C.c_int, [_I32, _I32, _P, C.POINTER(C.c_double), C.c_uint64, _I64, _I64, C.POINTER(C.c_double), _I32,
                                       _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gpmpc_marginal_likelihood": (C.c_int, [C.POINTER(GpDesc), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_moment_rollout": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _I64, _I32, _P, _I32, _P, _I32, _P,
+                                       _P, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,180 @@
+"""Host side of the linearised mean / covariance propagation (no GPU needed): the C-ABI's export and argument checks, the two CPU
+references against each other and against the recorded tolerance table, reference A against the oracle, and the variance-floor
+fixture."""
+import ctypes as C
+import os
+
+import pytest
+import torch
+
+from sampling_gpmpc_amd import _lib
+from tests import moments_reference as ref
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAME = "gpmpc_moment_rollout"
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def test_symbol_is_exported_and_bound_and_the_abi_stays_12(lib):
+    assert NAME in _lib.SYMBOLS
+    fn = getattr(lib, NAME)
+    res, args = _lib.SYMBOLS[NAME]
+    assert fn.restype == res == C.c_int and fn.argtypes == args
+    P, I32 = C.c_void_p, C.c_int32
+    assert args == [C.POINTER(_lib.GpDesc), C.POINTER(_lib.EnvDesc), P, P, C.c_int64, I32, P, I32, P, I32, P, P, P, P, P, P, P]
+    assert _lib.INFO_NONFINITE == 0x0800
+    assert lib.gpmpc_abi_version() == _lib.ABI_VERSION == 12
+
+
+def test_header_carries_the_declaration_the_citations_and_the_limits():
+    header = open(os.path.join(REPO, "include", "gpmpc_hip.h")).read()
+    assert "int     gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan" in header
+    assert "#define GPMPC_ABI_VERSION 12" in header
+    assert "#define GPMPC_INFO_NONFINITE         0x0800" in header
+    doc = header[header.index(" * gpmpc_moment_rollout - "):]
+    for cite in ("linearization_based_predictions.py:29-31,136-185", "robust_tube_based_GPMPC_koller.py:83-104,277-287",
+                 "zoro_code.py:34-74", ":100,157-161"):
+        assert cite in doc, cite
+    for text in ("at most 64 label rows", "ABI version stays 12", "exactly symmetric", "B == 0: nothing is launched"):
+        assert text in doc, text
+    src = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "moments.hip")).read()
+    assert "MOM_MAX_ROWS = 64" in src
+    build = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "build.py")).read()
+    assert '"moments.hip"' in build
+
+
+def _gp(g_ny=3, D=2, T=3, N_r=45, has_grad=0):
+    d = _lib.GpDesc()
+    d.g_ny, d.D, d.T, d.N_r, d.real_has_grad = g_ny, D, T, N_r, has_grad
+    return d
+
+
+def _env(env_id=1, nx=4, nu=2):
+    e = _lib.EnvDesc()
+    e.env_id, e.nx, e.nu = env_id, nx, nu
+    return e
+
+
+POINTERS = ("plan", "X_r", "x0", "U", "P0", "M", "P", "S", "A", "info")
+
+
+def _call(lib, gp=None, env=None, B=4, H=3, no_gp=False, no_env=False, **ptr):
+    """The device pointers are dummies that are never dereferenced: every case below must be decided before any device work."""
+    p = {k: ptr.get(k, 8) for k in POINTERS}
+    g = None if no_gp else C.byref(gp if gp is not None else _gp())
+    e = None if no_env else C.byref(env if env is not None else _env())
+    return lib.gpmpc_moment_rollout(g, e, p["plan"], p["X_r"], B, H, p["x0"], 1, p["U"], 1, p["P0"], p["M"], p["P"], p["S"], p["A"],
+                                    p["info"], None)
+
+
+def _ids(kw):
+    return ",".join(f"{k}=({v.g_ny},{v.D},{v.T},{v.N_r},{v.real_has_grad})" if isinstance(v, _lib.GpDesc)
+                    else f"{k}=({v.env_id},{v.nx},{v.nu})" if isinstance(v, _lib.EnvDesc) else f"{k}={v}" for k, v in kw.items())
+
+
+BAD_ARG = [dict(no_gp=True), dict(no_env=True), dict(plan=None), dict(X_r=None), dict(x0=None), dict(U=None), dict(M=None), dict(P=None),
+           dict(info=None), dict(B=-1), dict(H=-2), dict(gp=_gp(g_ny=0)), dict(gp=_gp(T=2)), dict(gp=_gp(N_r=0)),
+           dict(gp=_gp(T=1, has_grad=1)), dict(env=_env(nx=3)), dict(env=_env(nu=1)), dict(env=_env(env_id=0)),
+           dict(env=_env(env_id=7)), dict(gp=_gp(g_ny=1)), dict(gp=_gp(g_ny=3), env=_env(0, 2, 1))]
+
+
+@pytest.mark.parametrize("kw", BAD_ARG, ids=_ids)
+def test_argument_checks_come_before_any_device_work(lib, kw):
+    assert _call(lib, **kw) == -1
+    assert NAME in lib.gpmpc_last_error_string().decode()
+
+
+@pytest.mark.parametrize("gp", [_gp(N_r=65), _gp(N_r=65, T=1), _gp(N_r=22, has_grad=1), _gp(D=3, T=4, N_r=10), _gp(D=3, T=1, N_r=10)],
+                         ids=["65 value rows", "65 rows, T=1", "22 points x 3 tasks", "D=3 T=4", "D=3 T=1"])
+def test_sizes_outside_the_kernel_are_unsupported(lib, gp):
+    assert _call(lib, gp=gp) == -4
+    msg = lib.gpmpc_last_error_string().decode()
+    assert NAME in msg and ("64 label rows" in msg or "D = 2" in msg), msg
+
+
+def test_the_limits_admit_what_the_issue_lists_and_an_empty_batch_is_ok(lib):
+    for gp, env in ((_gp(N_r=64), _env()), (_gp(N_r=21, has_grad=1), _env()), (_gp(g_ny=1, N_r=36), _env(0, 2, 1)),
+                    (_gp(g_ny=1, N_r=64, T=1), _env(0, 2, 1))):
+        assert _call(lib, gp=gp, env=env, B=0) == 0                     # B = 0: valid, nothing is launched
+    assert _call(lib, B=0, H=0, U=None) == 0                            # without steps there is no input to read
+    none = {k: None for k in POINTERS}
+    assert _call(lib, B=0, **none) == 0                                 # the empty arrays of an empty batch have no address
+    assert _call(lib, B=0, gp=_gp(N_r=65), **none) == -4 and _call(lib, B=0, env=_env(nx=3), **none) == -1   # sizes still checked
+
+
+def test_wrappers_need_a_hip_device_and_are_exported():
+    import sampling_gpmpc_amd as sg
+    for name in ("MomentTube", "moment_rollout", "moment_rollout_plan"):
+        assert hasattr(sg, name) and name in sg.__all__
+    from tests.helpers import load_params
+    p = load_params("params_pendulum1D_samples")
+    p["common"]["use_cuda"] = False
+    agent = sg.Agent(p, sg.make_env(p))
+    with pytest.raises(_lib.GpmpcError):
+        sg.moment_rollout(agent, torch.zeros(2, dtype=torch.float64), torch.zeros(3, 1, dtype=torch.float64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the references
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ref.SHIPPED + ref.RAW)
+def test_a_agrees_with_b_within_the_recorded_table(name):
+    """tests/test_hip_moments.py takes its tolerances from WORST_AB, the A-against-B differences as measured when the table was
+    written.  Re-measured here; another BLAS may round differently, so each figure may be up to twice the recorded one (plus the
+    rounding floor)."""
+    from tests.test_hip_moments import WORST_AB
+    got = ref.measure_ab(name)
+    assert sorted(got) == sorted(WORST_AB[name]) == ["A", "P", "S", "mean"]
+    for q, v in got.items():
+        assert v <= 2.0 * WORST_AB[name][q] + ref.FLOOR, (name, q, v)
+
+
+@pytest.mark.parametrize("name", ["pend_nofb", "car_fb", "raw17", "grad5"])
+def test_a_agrees_with_the_oracle_at_the_test_points(name):
+    """Reference A's posterior mean and variance of the first step against oracle/gp_oracle.py at the same GP inputs.  The oracle is
+    a third evaluation of the same algebra (Cholesky solves of its own kernel matrix): the three differ by eps * cond(K) relative
+    to the labels' / the outputscale's size; cond(K) <= 1.3e7 for the shipped sets, 2.2e-16 * 1.3e7 = 2.9e-9, bound 1e-8."""
+    c = ref.CASES[name]()
+    r = ref.rollout_A(name, raw_variance=True)
+    n = min(16, c.x0.shape[0])
+    x, u_ff = c.x0[:n], c.U[:n, 0]
+    xi = ref._gp_input(c, x, ref._feedback(c, x, u_ff))
+    m_o, v_o = ref.oracle_mean_var(c, xi)                                   # (g_ny, n)
+    g_ny = c.Y.shape[0]
+    fac = ref._factor_A(name)
+    m_a = torch.stack([ref._value_rows_A(c, o, xi) @ fac[o][1] for o in range(g_ny)])
+    ymax = torch.stack([c.Y[o, :, 0].abs().max() for o in range(g_ny)])
+    assert float(((m_a - m_o).abs() / ymax[:, None]).max()) <= 1e-8
+    assert float(((r["S"][:n, 0].T - v_o).abs() / c.outputscale[:, None]).max()) <= 1e-8
+    # and the mean step is the environment's: mu_1 = env_step(mu_0, u, m)
+    torch.testing.assert_close(r["M"][:n, :, 1], ref._env_step(c, x, ref._feedback(c, x, u_ff), m_a.T), rtol=1e-12, atol=1e-14)
+
+
+def test_reference_a_reproduces_the_orientation_figures():
+    """The nominal candidate of the full-length cases: x0 = env.start, U = synthetic_u_ff (figures of a torch script, 4-5 digits)."""
+    r = ref.reference("pend_full")                                         # (3.0911, 2.0857) there; its diag P_H differed by 12 %
+    torch.testing.assert_close(r["M"][0, :, -1], torch.tensor([3.0911, 2.0857], dtype=torch.float64), rtol=0, atol=2e-4)
+    r = ref.reference("car_full")
+    torch.testing.assert_close(r["M"][0, :, -1], torch.tensor([47.2084, 2.8515, -0.0245, 12.7891], dtype=torch.float64), rtol=0, atol=6e-5)
+    torch.testing.assert_close(torch.diagonal(r["P"][0, -1]), torch.tensor([3.539e-4, 1.304e-4, 5.83e-6, 6.05e-5], dtype=torch.float64),
+                               rtol=2e-3, atol=0)
+    assert abs(float(torch.linalg.eigvalsh(r["P"][0, -1])[0]) - 5.5e-6) < 1e-7
+    nofb = ref.reference("car_nofb")["P"]
+    assert bool((nofb[:, :, 3, :] == 0).all()) and bool((nofb[:, :, :, 3] == 0).all())      # row and column v: exactly zero
+
+
+def test_the_variance_floor_fixture_stays_inside_its_window():
+    c = ref.CASES["floor"]()
+    r = ref.rollout_A("floor", raw_variance=True)
+    raw = float(r["S_raw"][0, 0, 0])
+    assert -1e-12 < raw < 1e-11, raw                                       # far below the 1e-10 floor whatever the rounding
+    assert float(r["S"][0, 0, 0]) == c.var_floor == 1e-10
+    assert float(r["S_raw"][1, 0, 0]) > 0.1                                # the neighbour is nowhere near it
+    # the shipped configurations never reach the floor
+    assert float(ref.reference("car_full")["S"].min()) > 1e-8 and float(ref.reference("pend_full")["S"].min()) > 1e-6
+    for name in ("pend_nofb", "pend_fb", "car_nofb", "car_fb"):
+        assert float(ref.reference(name)["S"].min()) > 1e-9, name
