@@ -45,7 +45,11 @@ EXTRA_FLAGS = {"rollout_fast.hip": os.environ.get("GPMPC_FAST_FLAGS", "-mllvm -d
                "rollout.hip": os.environ.get("GPMPC_ROLLOUT_FLAGS", "-mllvm -disable-machine-licm").split(),
                "rollout_tiles.hip": os.environ.get("GPMPC_TILES_FLAGS", "").split(),
                # rollout_one.hip: without machine-LICM no SGPR is spilled (28 otherwise: v_readlane / v_writelane pairs in the step)
-               "rollout_one.hip": os.environ.get("GPMPC_ONE_FLAGS", "-mllvm -disable-machine-licm").split(),
+               # and without the IR load/store vectoriser the converter writes of the 29 step blocks stay scalar stores that the
+               # machine pass pairs into ds_write2_b64 with separate operands: a <2 x double> store wants its halves in adjacent
+               # registers, and the values - shared by all blocks, paired differently in each - were copied there (4 v_mov per
+               # write in 13 of the blocks)
+               "rollout_one.hip": os.environ.get("GPMPC_ONE_FLAGS", "-mllvm -disable-machine-licm -mllvm -amdgpu-load-store-vectorizer=0").split(),
                "rollout_indep.hip": os.environ.get("GPMPC_INDEP_FLAGS", "").split(),
                "joint_mfma.hip": os.environ.get("GPMPC_JOINT_MFMA_FLAGS", "").split()}
 

@@ -41,6 +41,16 @@
 //     it: then - and only then - (ii) and the exponential run again from the final value in the cold block.  The converters
 //     are untouched by the append and their layout does not depend on the epoch, so the hand-over crosses epoch changes.
 //     (profiles/one_rotated_phases.md; the entries need no register across the append, LDS carries them.)
+//   * the append is selected by the STEP INDEX.  INVARIANT: n_h == 3 t at the head of every step - the kernel is dispatched
+//     for unseeded launches only (rollout_one_sizing) and every step but the last appends T = 3 rows.  So the incomplete
+//     tile row, its block, the lanes of the new rows, whether they reach into the next tile row or wrap into the next group,
+//     both EXEC masks of every panel write, every lane pattern of the diagonal tiles' selects and the converter columns of
+//     the next entries are functions of t alone: section (vi) dispatches on t ONCE per step (bisection over the epoch's 3 - 6
+//     steps) into a block in which all of them are compile-time constants - masks are s_mov literals
+//     (rollout_one_gen.inc: OneRowMask; one_apply: one v_cndmask pair per value the step's pattern contains), converter
+//     writes take immediate offsets, no v_cmp / clamp / ballot remains.  n_h stays the run-time variable the shared part
+//     (one_solve, the extraction) reads; GPMPC_ONE_DEBUG checks the invariant in every block.  The values written are the
+//     ones the run-time selects produced: results are bit-identical (profiles/one_append_steps.md).
 //
 // (A first version grouped FOUR TILE ROWS per MFMA with the solution tiles replicated in all blocks: 1.5x the MFMAs, three
 // times the masked writes; tools/experiments/rollout_one_superrow/.)
@@ -62,10 +72,19 @@ __device__ double g_one_dbg[64 * 64];
 #define OPH_DECL long long oph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long opht_ = __builtin_readcyclecounter()
 #define OPH(i) do { const long long n_ = __builtin_readcyclecounter(); oph_[i] += n_ - opht_; opht_ = n_; } while (0)
 #define OPH_STORE do { if (blockIdx.x == 0 && threadIdx.x == 0) for (int i_ = 0; i_ < 8; ++i_) g_one_phase_cycles[i_] = oph_[i_]; } while (0)
+#elif defined(GPMPC_ONE_PHASE_MARKS)                              // tools/one_phase_mix.py: the phases' ends as comments in the ISA
+#define OPH_DECL
+#define OPH(i) asm volatile("; one_phase_end " #i)
+#define OPH_STORE
 #else
 #define OPH_DECL
 #define OPH(i)
 #define OPH_STORE
+#endif
+#ifdef GPMPC_ONE_PHASE_MARKS
+#define OPH_MARK(name) asm volatile("; one_phase_" name)
+#else
+#define OPH_MARK(name)
 #endif
 #ifndef GPMPC_ONE_DEBUG_STEP
 #define GPMPC_ONE_DEBUG_STEP 2
@@ -203,10 +222,65 @@ __device__ __forceinline__ void one_axis9(double& P0, double& P1, double R0, dou
         : "+v"(P0), "+v"(P1)
         : "v"(R0), "v"(R1), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]), "v"(c[6]), "v"(c[7]), "v"(c[8]));
 }
-__device__ __forceinline__ double one_pick3(int i, double v0, double v1, double v2) {
-    const double t = (i == 1) ? v1 : v2;
-    return (i == 0) ? v0 : t;
+// ---- the append's selects by PATTERN: in step t the factor has n_h = 3 t rows, so which lane of a register receives which of
+// the step's values is known when the step's block is compiled.  A pattern maps a lane (kq, bm, jq) to the id of the value it
+// receives (OV_KEEP: none); one_apply turns it into one select under a CONSTANT lane mask per value the pattern contains
+// (s_mov of the mask + v_cndmask: no compare, no index clamp).
+enum OneVal { OV_KEEP = 0, OV_C00, OV_C10, OV_C11, OV_C20, OV_C21, OV_C22, OV_CI0, OV_CI1, OV_CI2, OV_OLD, OV_COUNT, OV_ZERO = OV_KEEP };
+// lanes of M: a, the others b
+template <unsigned long long M>
+__device__ __forceinline__ double one_sel(double a, double b) {
+    return __builtin_amdgcn_inverse_ballot_w64(M) ? a : b;
 }
+template <class Pat, int ID>
+constexpr unsigned long long one_pat_mask() {
+    unsigned long long m = 0;
+    for (int l = 0; l < 64; ++l)
+        if (Pat::at(l >> 4, (l >> 2) & 3, l & 3) == ID) m |= 1ull << l;
+    return m;
+}
+template <class Pat>
+__device__ __forceinline__ double one_apply(double x, const double (&val)[OV_COUNT]) {
+    one_for<1, OV_COUNT>([&](auto ic) {
+        constexpr int ID = decltype(ic)::value;
+        constexpr unsigned long long M = one_pat_mask<Pat, ID>();
+        if constexpr (M != 0) x = one_sel<M>(val[ID], x);
+    });
+    return x;
+}
+// A new row (index ri = 0 .. 2 counted from the first new row) against column rk (same origin): old columns (rk < 0) carry v of
+// the incomplete tile row, new ones the 3 x 3 factor C[ri][rk], columns behind the row's diagonal are zero - and stay what they
+// are: every row is new exactly once, and until then its lanes hold the identity the diagonal tiles start from.
+constexpr int one_new_entry(int ri, int rk) {
+    if (rk < 0) return OV_OLD;
+    if (rk > ri) return OV_ZERO;
+    return ri == 0 ? OV_C00 : (ri == 1 ? OV_C10 + rk : OV_C20 + rk);
+}
+constexpr int one_new_inv(int i) { return (i >= 0 && i < 3) ? OV_CI0 + i : OV_KEEP; }
+// tile row tn + 1 against the incomplete tile's columns (block BT) when the new rows reach into it: rows jq < I0 - 1
+template <int I0, int BT>
+struct OnePatReach {
+    static constexpr int at(int kq, int bm, int jq) {
+        return (bm == BT && jq < I0 - 1 && kq >= I0) ? one_new_entry(4 + jq - I0, kq - I0) : OV_KEEP;
+    }
+};
+// the diagonal tiles of a group, natural map of L^T: row of L = 4 bm + jq, column = 4 bm + kq inside the group; LO = the first
+// new row inside the group's 16 rows (negative: the rows that wrapped into the next group)
+template <int LO>
+struct OnePatDiag {
+    static constexpr int at(int kq, int bm, int jq) {
+        const int ri = 4 * bm + jq - LO;
+        return (ri >= 0 && ri < 3) ? one_new_entry(ri, 4 * bm + kq - LO) : OV_KEEP;
+    }
+};
+template <int LO>
+struct OnePatInvRow {                                             // 1 / diag along the rows of L^T: the lane's L-column is a new row
+    static constexpr int at(int kq, int bm, int) { return one_new_inv(4 * bm + kq - LO); }
+};
+template <int LO>
+struct OnePatInvCol {                                             // 1 / diag along its columns: the lane's L-row is a new row
+    static constexpr int at(int, int bm, int jq) { return one_new_inv(4 * bm + jq - LO); }
+};
 
 // chol3_pair_lean (gpmpc_device.hpp) cut behind its FIRST pivot: the sample's y[0] = sqrt(S_00) z_0 + mu_0 - all the next
 // state needs - is known after one_chol_pivot1.  one_chol_rest runs pivots 2 and 3 with the NEXT step's exponential
@@ -410,42 +484,60 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         Rq0 = one_bpermute(ea, bp_addr);
         Rq1 = one_bpermute(ea * gq, bp_addr);
     };
-    // (c) the right-hand sides of the nh appended rows and v_r = W k_r into the lane-map converters
-    auto ent_c = [&](int nh, double kk, double xi0, double xi1, double Rq0, double Rq1) {
+    // (c) the right-hand sides of the nh appended rows and v_r = W k_r into the lane-map converters: the values (the same
+    //     code for every step), then the writes - their column positions follow nh, a compile-time constant of the step's block
+    struct OneEntC {
+        double vr[T], hs[T][T];
+    };
+    auto ent_c_vals = [&](bool rows, double kk, double xi0, double xi1, double Rq0, double Rq1, OneEntC& e) {
         const double q0 = (xh[0] - xi0) * il0, q1 = (xh[1] - xi1) * il1;
-        const int i0 = nh & 3, ycol = (i0 + 3) & 3;
-        const int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
         // (the DPP products first: their operands - the ds_bpermute results - arrived long ago, while a wait behind the
         // ds_writes below would also wait for those)
         // ---- v_r = W k_r through the grid root (rollout_fast.hip, step 2): lane = real point ------------------------------
-        double vr[T];
         {
             double PA0 = 0.0, PA1 = 0.0, PB0 = 0.0, PB1 = 0.0;
             one_axis4(PA0, PA1, Rq0, Rq1, qa);                    // lanes 0 .. 3 of the row: axis 0
             one_axis9(PB0, PB1, Rq0, Rq1, qb);                    // lanes 4 .. 12: axis 1
             const double s0 = dsc * PB0;
-            vr[0] = s0 * PA0;
-            vr[1] = s0 * PA1;
-            vr[2] = dsc * PA0 * PB1;
+            e.vr[0] = s0 * PA0;
+            e.vr[1] = s0 * PA1;
+            e.vr[2] = dsc * PA0 * PB1;
         }
         // ---- right-hand sides of the appended rows: lane = point, cov(task a of the point, task b of the test point) ----
-        if (nh > 0 && jpt >= 0 && jpt < 32) {
+        if (rows) {
             // k (A_a B_b + [a == b > 0] / l_a^2) with A = (1, -q0, -q1), B = (1, q0, q1)
             const double kA[T] = {kk, -kk * q0, -kk * q1}, kd[T] = {0.0, kk * il0, kk * il1};
 #pragma unroll
             for (int aa = 0; aa < T; ++aa) {
-                double* dst = HSb + (3 * jpt + aa) * kOneRS;
-                dst[cb0] = kA[aa];
-                dst[cb1] = fma(kA[aa], q0, (aa == 1) ? kd[1] : 0.0);
-                dst[cb2] = fma(kA[aa], q1, (aa == 2) ? kd[2] : 0.0);
-                dst[ycol] = yt[aa];                               // (zero until the lane's point exists)
+                e.hs[aa][0] = kA[aa];
+                e.hs[aa][1] = fma(kA[aa], q0, (aa == 1) ? kd[1] : 0.0);
+                e.hs[aa][2] = fma(kA[aa], q1, (aa == 2) ? kd[2] : 0.0);
             }
         }
-        if (lane < NR) {                                          // rows of v_r, task column c at (i0 + c) & 3, whitened label beside
+    };
+    constexpr unsigned long long kPtLanes = ((1ull << 32) - 1) << kPt0;    // the lanes of the 32 appended points
+    constexpr unsigned long long kRealLanes = (1ull << NR) - 1;           // the lanes of the real points
+    auto ent_c_put = [&](auto nhc, const OneEntC& e) {
+        constexpr int nh = decltype(nhc)::value;
+        constexpr int i0 = nh & 3, ycol = (i0 + 3) & 3;
+        constexpr int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
+        if constexpr (nh > 0) {
+            if (__builtin_amdgcn_inverse_ballot_w64(kPtLanes)) {
+#pragma unroll
+                for (int aa = 0; aa < T; ++aa) {
+                    double* dst = HSb + (3 * jpt + aa) * kOneRS;
+                    dst[cb0] = e.hs[aa][0];
+                    dst[cb1] = e.hs[aa][1];
+                    dst[cb2] = e.hs[aa][2];
+                    dst[ycol] = yt[aa];                           // (zero until the lane's point exists)
+                }
+            }
+        }
+        if (__builtin_amdgcn_inverse_ballot_w64(kRealLanes)) {    // rows of v_r, task column c at (i0 + c) & 3, whitened label beside
             double* dst = VRb + lane * kOneRS;
-            dst[cb0] = vr[0];
-            dst[cb1] = vr[1];
-            dst[cb2] = vr[2];
+            dst[cb0] = e.vr[0];
+            dst[cb1] = e.vr[1];
+            dst[cb2] = e.vr[2];
             dst[ycol] = w_lane;
         }
     };
@@ -456,11 +548,14 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         double kk, Rq0, Rq1;
         const double ea = one_exp_neg(ent_a(0, true, x, ucur), ek);
         ent_b(0, ea, x[0], ucur, kk, Rq0, Rq1);
-        ent_c(0, kk, x[0], ucur, Rq0, Rq1);
+        OneEntC e;
+        ent_c_vals(false, kk, x[0], ucur, Rq0, Rq1, e);
+        ent_c_put(std::integral_constant<int, 0>{}, e);
     }
 #ifdef GPMPC_PHASE_TIMERS
     opht_ = __builtin_readcyclecounter();
 #endif
+    OPH_MARK("end prologue");
 
     auto step = [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;                    // group of the incomplete tile (unified tile 9 + (n_h >> 2))
@@ -581,6 +676,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         if (__builtin_expect(!r_ok, 0)) info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
         draw();
         if (__builtin_expect(clip || all_zero || !r_ok, 0)) {
+            OPH_MARK("cold begin");
             if (all_zero) {                                       // (uniform; only with a threshold >= 0) the mean, nothing to clip
 #pragma unroll
                 for (int bq = 0; bq < T; ++bq) y[bq] = mu[bq];
@@ -602,6 +698,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 const double ea = one_exp_neg(ent_a(t + 1, more, xs, un), ek);
                 ent_b(t + 1, ea, x0n, un, kk, Rq0, Rq1);
             }
+            OPH_MARK("cold end");
         }
         if (!LEAN && lane == 0 && one_wanted(Y_s)) {
 #pragma unroll
@@ -617,70 +714,15 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 for (int bq = 0; bq < T; ++bq) yt[bq] = mine ? y[bq] : yt[bq];   // the label column is whitened by the same MFMAs (w_r rides in Vu)
             }
             // ---- (v) the rest of step t + 1's entries: their LDS writes land while the append runs ---------------------------
-            ent_c(n_h + T, kk, x0n, un, Rq0, Rq1);
-            OPH(0);
+            OneEntC ec;
+            ent_c_vals(true, kk, x0n, un, Rq0, Rq1, ec);
             // ---- (vi) append the point (A.9): three rows of the factor = lanes of the panels -------------------------------
-            const int tn = n_h >> 2;                              // the incomplete tile row; its unified tile is 4 K + bt
-            const int bt = (NKT + tn) & 3;
-            const int lo = n_h - 4 * R0;                          // first new row inside group K's 16 rows
-            // C[ci][ck] by lane-varying indices (clamped to 0 .. 2); by VALUE: a select between captured references is a
-            // select of addresses, which hipcc turns into a table of pointers in scratch memory
-            const double c00 = C[0][0], c10 = C[1][0], c11 = C[1][1], c20 = C[2][0], c21 = C[2][1], c22 = C[2][2];
-            const double ci0 = cinv[0], ci1 = cinv[1], ci2 = cinv[2];
-            auto c_pick = [=](int ci, int ck) -> double {
-                const double r0 = one_pick3(ci, c00, c10, c20);
-                const double r1 = one_pick3(ci, c11, c11, c21);
-                return one_pick3(ck, r0, r1, c22);
-            };
-            // A new row (index ri = 0 .. 2 counted from the first new row) against column rk (same origin): old columns
-            // (rk < 0) carry v of the incomplete tile row (`vold`), new ones the 3 x 3 factor
-            auto new_entry = [&](int ri, int rk, double vold) -> double {
-                const int ci = min(max(ri, 0), 2), ck = min(max(rk, 0), 2);
-                const double cval = (rk <= ri) ? c_pick(ci, ck) : 0.0;
-                return (rk < 0) ? vold : cval;
-            };
-            // panels of the new rows' tile rows: lane (kq, bm, jq) of panel (r, g) is row 4 r + jq against column 4 (4 g + bm) + kq,
-            // and the value is v of that column for the row's right-hand side = this very lane of Vu[g]
-            // The masked writes run under uniform C++ branches (only the incomplete tile row and, when the new rows reach into
-            // it, the next one have anything to receive) WITHOUT naming the panels as operands - a tied physical-register
-            // operand defined under a branch makes hipcc carry the panel in a virtual register across it; one_touch_row
-            // (no instruction) tells the compiler afterwards that the panels of the candidate rows may have changed.
-            auto row_masks = [&](int r, int b, unsigned long long& mBase, unsigned long long& mLast) {
-                const int rowg = 4 * r + jq;
-                int bmv = bm;
-                asm volatile("" : "+v"(bmv));
-                const bool nw = (rowg >= n_h) && (rowg < n_h + 3);
-                mBase = __ballot(nw);
-                mLast = __ballot(nw && bmv < b);
-            };
-            // (a binary decision over the <= 4 candidate rows: a compare chain takes a branch per row in front of the right one)
-            one_pick_row<(R0 > 0 ? R0 : 0), (R0 + 4 < kOneNTR ? R0 + 4 : kOneNTR)>(tn, [&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                {
-                    unsigned long long mBase, mLast;
-                    row_masks(r, (NKT + r) & 3, mBase, mLast);
-                    one_hset_row<r>(mBase, mLast, Vu);
-                    if constexpr (r + 1 < kOneNTR) {
-                        if (i0 >= 2) {                            // rows n_h .. n_h + 2 reach into tile row r + 1
-                            // against the incomplete tile's columns that row has old columns (v) and new ones (the 3 x 3 factor)
-                            double Vm[K + 2];
-#pragma unroll
-                            for (int gg = 0; gg <= K; ++gg) Vm[gg] = Vu[gg];
-                            Vm[K + 1] = 0.0;
-                            const double mixC = new_entry(4 + jq - i0, kq - i0, Vu[K]);
-                            Vm[K] = (bm == bt) ? mixC : Vu[K];
-                            row_masks(r + 1, (NKT + r + 1) & 3, mBase, mLast);
-                            one_hset_row<r + 1>(mBase, mLast, Vm);
-                        }
-                    }
-                }
-            });
-            one_for<(R0 > 0 ? R0 : 0), (R0 + 5 < kOneNTR ? R0 + 5 : kOneNTR)>([&](auto rc) { one_touch_row<decltype(rc)::value>(P); });
-            OPH(5);
-            // The diagonal tiles of group K: ud = L^T of the lane's own tile (natural map, one tile per block), drow / dcol =
-            // 1 / diag along its rows / columns.  New rows enter by select; ALL FOUR tile inverses come out of the same three
-            // MFMAs, U^-1 = (I + M)(I + M^2) D^-1 with U = D (I - M) (rollout_tiles.hip, phase H) - complete tiles reproduce
-            // what they had, so the whole register is committed.
+            // n_h == 3 t: ONE dispatch on the step index, and inside the step's block the incomplete tile row, the lanes of the
+            // new rows and every select below are compile-time - code selection instead of run-time selection, the values
+            // written are what run-time selects on n_h would produce.  The values of the selects: the 3 x 3 factor, its inverse diagonal, v of the row.
+            const double sv[OV_COUNT] = {0.0, C[0][0], C[1][0], C[1][1], C[2][0], C[2][1], C[2][2], cinv[0], cinv[1], cinv[2], Vu[K]};
+            // U^-1 = (I + M)(I + M^2) D^-1 with U = D (I - M) (rollout_tiles.hip, phase H): ALL FOUR tile inverses of a group
+            // come out of the same three MFMAs - complete tiles reproduce what they had, so the whole register is committed.
             auto inverse_tiles = [&](double U, double dr, double dcl) -> double {
                 const double M = Inat - dr * U;
                 const double Mt = one_mfma_zero(M, Inat);                     // M^T
@@ -688,38 +730,55 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 const double Pq = one_mfma_zero(Inat + Mt, Inat + M2);        // (I + M)(I + M^2)
                 return Pq * dcl;
             };
+            constexpr int TB = OneEpoch<K>::t_begin, TE = OneEpoch<K>::t_end < kOneAppendSteps ? OneEpoch<K>::t_end : kOneAppendSteps;
+            one_pick_row<TB, TE>(t, [&](auto tc) {
+                constexpr int TT = decltype(tc)::value, NH = T * TT;
+                constexpr int i0 = NH & 3;
+                constexpr int tn = NH >> 2;                       // the incomplete tile row; its unified tile is 4 K + bt
+                constexpr int bt = (NKT + tn) & 3;
+                constexpr int lo = NH - 4 * R0;                   // first new row inside group K's 16 rows
+                static_assert(((NKT + tn) >> 2) == K && lo == 4 * bt + i0 && tn >= 0 && tn < kOneNTR, "step outside its epoch");
+#ifdef GPMPC_ONE_DEBUG
+                if (n_h != NH) g_one_dbg[63 * 64 + lane] = (double)(n_h - NH);   // the invariant n_h == 3 t does not hold
+#endif
+                ent_c_put(std::integral_constant<int, NH + T>{}, ec);
+                OPH(1);
+                // panels of the new rows' tile rows: lane (kq, bm, jq) of panel (r, g) is row 4 r + jq against column 4 (4 g + bm) + kq,
+                // and the value is v of that column for the row's right-hand side = this very lane of Vu[g].
+                // The masked writes stand under this dispatch WITHOUT naming the panels as operands - a tied physical-register
+                // operand defined under a branch makes hipcc carry the panel in a virtual register across it; one_touch_row
+                // (no instruction) tells the compiler afterwards that the panels of the epoch's candidate rows may have changed.
+                one_hset_row_at<tn, NH>(Vu);
+                if constexpr (i0 >= 2 && tn + 1 < kOneNTR) {      // rows n_h .. n_h + 2 reach into tile row tn + 1
+                    // against the incomplete tile's columns that row has old columns (v) and new ones (the 3 x 3 factor)
+                    double Vm[K + 2];
+#pragma unroll
+                    for (int gg = 0; gg <= K; ++gg) Vm[gg] = Vu[gg];
+                    Vm[K + 1] = 0.0;
+                    Vm[K] = one_apply<OnePatReach<i0, bt>>(Vu[K], sv);
+                    one_hset_row_at<tn + 1, NH>(Vm);
+                }
+                OPH(5);
+                // The diagonal tiles of group K: ud = L^T of the lane's own tile (natural map, one tile per block), drow / dcol =
+                // 1 / diag along its rows / columns.  New rows enter by select.
+                ud = one_apply<OnePatDiag<lo>>(ud, sv);
+                drow = one_apply<OnePatInvRow<lo>>(drow, sv);
+                dcol = one_apply<OnePatInvCol<lo>>(dcol, sv);
+                if constexpr (K < KLAST && lo + 3 > 16) {         // (once per epoch) rows wrapped into group K + 1: its first diagonal tile
+                    ud1 = one_apply<OnePatDiag<lo - 16>>(ud1, sv);            // (all of its columns are new: no old value)
+                    drow1 = one_apply<OnePatInvRow<lo - 16>>(drow1, sv);
+                    dcol1 = one_apply<OnePatInvCol<lo - 16>>(dcol1, sv);
+                    const double G1 = inverse_tiles(ud1, drow1, dcol1);
+                    one_hset_gd<K + 1>(G1);                       // (hidden write under the dispatch, see above)
+                }
+            });
+            one_for<(R0 > 0 ? R0 : 0), (R0 + 5 < kOneNTR ? R0 + 5 : kOneNTR)>([&](auto rc) { one_touch_row<decltype(rc)::value>(P); });
+            if constexpr (K < KLAST) one_touch_gd<K + 1>(P);
             {
-                // natural map of L^T: row index of L = 4 bm + jq (= rA), column index = 4 bm + kq, both inside the group
-                const bool newK = (rA >= lo) && (rA < lo + 3);
-                int kqv = kq;                                     // (opaque: hipcc reduces rkD <= rA - lo to the loop-invariant
-                asm volatile("" : "+v"(kqv));                     // kq <= jq and keeps that lane mask in an SGPR pair it has to spill)
-                const int rkD = 4 * bm + kqv - lo;
-                const double mixD = new_entry(rA - lo, rkD, Vu[K]);
-                ud = newK ? mixD : ud;
-                const bool newRowK = (rkD >= 0) && (rkD < 3);            // the lane's L-column index is a new row
-                const double cK = one_pick3(min(max(rkD, 0), 2), ci0, ci1, ci2);
-                const double cJ = one_pick3(min(max(rA - lo, 0), 2), ci0, ci1, ci2);
-                drow = newRowK ? cK : drow;
-                dcol = newK ? cJ : dcol;
                 const double Gt = inverse_tiles(ud, drow, dcol);
                 ODBG(8, ud);
                 ODBG(9, Gt);
                 one_set_gd<K>(P, ~0ull, Gt);
-            }
-            if constexpr (K < KLAST) {
-                if (__builtin_expect(lo + 3 > 16, 0)) {           // (uniform, once per epoch) rows wrapped into group K + 1: its first diagonal tile
-                    const bool newK1 = rA < lo + 3 - 16;
-                    const int rkD1 = 4 * bm + kq + 16 - lo;       // >= 1: all of its columns are new
-                    const double mixD1 = new_entry(rA + 16 - lo, rkD1, 0.0);
-                    ud1 = newK1 ? mixD1 : ud1;
-                    const double cK1 = one_pick3(min(max(rkD1, 0), 2), ci0, ci1, ci2);
-                    const double cJ1 = one_pick3(min(max(rA + 16 - lo, 0), 2), ci0, ci1, ci2);
-                    drow1 = (rkD1 < 3) ? cK1 : drow1;
-                    dcol1 = newK1 ? cJ1 : dcol1;
-                    const double G1 = inverse_tiles(ud1, drow1, dcol1);
-                    one_hset_gd<K + 1>(G1);                       // (hidden write under the branch, see above)
-                }
-                one_touch_gd<K + 1>(P);
             }
             n_h += T;
         }

@@ -14,12 +14,13 @@ for (ns, h) in CASES:
     print("   path", _lib.load().gpmpc_debug_last_rollout_path(), flush=True)
     if os.environ.get("GPMPC_PHASE_TIMERS") == "1" and _lib.load().gpmpc_debug_last_rollout_path() == 4:
         raw = C.CDLL(_lib.LIB_PATH); out = (C.c_longlong * 16)(); raw.gpmpc_debug_read_one_phases(out)
-        # (rotated loop: "entries" = the LDS reads at the head of the step + the DPP products and converter writes behind the sample;
-        # the next step's exponential runs inside "sample", in the levels of pivots 2 and 3)
-        names = ["entries+vr+lds", "-", "solve", "gram+1st extract", "sample+next exp", "append sets", "append diag", "state"]
+        # (rotated loop: the entries are the LDS reads at the head of the step and the DPP products and converter writes behind the
+        # sample - the writes stand inside the step's append block; the next step's exponential runs inside "sample", in the
+        # levels of pivots 2 and 3)
+        names = ["entries: lds reads", "entries: vr+writes", "solve", "gram+1st extract", "sample+next exp", "append sets", "append diag", "state"]
         tot = sum(out[:8])
         print("   total cycles", tot, "per step", tot // h)
-        for n, v in zip(names, out[:8]): print(f"   {n:16s} {v:9d} {v // h:7d}/step {100.0 * v / max(tot, 1):5.1f}%%")
+        for n, v in zip(names, out[:8]): print(f"   {n:18s} {v:9d} {v // h:7d}/step {100.0 * v / max(tot, 1):5.1f}%%")
         print(f"   prologue (kernel entry -> step loop) {out[8]} cycles, whole kernel of wave 0 {out[9]} cycles (the step loop {tot})")
 '''
 cases = [(1024, 30), (1024, 15), (2048, 30), (256, 30)]

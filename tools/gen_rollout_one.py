@@ -17,7 +17,9 @@ diagonal tiles of group g, inverted - block b holds (L_bb^-1)^T in the natural m
 Statements: the Gram / generic chains open with s_nop 1 and close with s_nop 5 (hipcc pads nothing around inline asm); the
 forward substitution of a step is ONE statement per epoch (solve_stmt) whose wait states hold the next tile row's independent
 MFMAs; tools/check_dpp_hazard.py checks the ISA of the result.  The subtracting form uses the FP64 MFMA's neg modifier
-(neg:[1,0,0]: -A B + C).  --variant ... --out ...: schedule experiments of tools/ubench/one_solve_chain.hip.
+(neg:[1,0,0]: -A B + C).  The append is selected by the step index (n_h = 3 t): emit_append writes the steps of every epoch and,
+per (tile row, first new row), the two EXEC masks of the row's masked panel writes as constants (append_row_masks;
+tests/test_one_append_masks.py checks them against the lane rule).  --variant ... --out ...: schedule experiments of tools/ubench/one_solve_chain.hip.
 """
 import os
 import sys
@@ -328,6 +330,63 @@ def hidden_set_stmt(items, mask):
     return f"    asm volatile({body}\n        : \"=&s\"(sv_)\n        : {', '.join(ins)});\n"
 
 
+# ---- the append of a step as code selection: n_h = 3 t is static ----------------------------------------------------------------
+# rollout_one_kernel runs unseeded launches only and every step but the last appends T = 3 rows, so step t finds n_h = 3 t rows
+# and everything its append selects by - the incomplete tile row, the lanes of the new rows, the EXEC masks of the panel writes
+# - is a function of t alone.  The kernel dispatches on t once per step (one_pick_row over the epoch's steps) and the masks
+# below reach the masked writes as 64-bit constants.
+T_ROWS = 3
+APPEND_STEPS = (4 * NTR) // T_ROWS            # steps t = 0 .. 28 append (rows 3 t .. 3 t + 2 of the 88)
+
+
+def epoch_of(t):
+    """group K of the incomplete tile when step t starts (the step loop's epoch)"""
+    return (NKT + ((T_ROWS * t) >> 2)) >> 2
+
+
+def epoch_steps(K):
+    """the steps t of epoch K as range(begin, end), from the loop condition ((NKT + (n_h >> 2)) >> 2) == K with n_h = 3 t"""
+    lo4, hi4 = 4 * (4 * K - NKT), 4 * (4 * K + 4 - NKT)          # n_h in [lo4, hi4)
+    begin = max(0, -(-lo4 // T_ROWS))
+    end = min(max(begin, -(-hi4 // T_ROWS)), APPEND_STEPS + 1)   # (H <= 30: the last step, t = 29, appends nothing)
+    return range(begin, end)
+
+
+def append_rows(t):
+    """the tile rows that receive lanes in step t: the incomplete one and, when the three new rows reach into it, the next"""
+    nh = T_ROWS * t
+    tn = nh >> 2
+    return [tn] + ([tn + 1] if (nh & 3) >= 2 and tn + 1 < NTR else [])
+
+
+def append_row_masks(r, nh):
+    """(mBase, mLast) of one_hset_row_<r> when rows nh .. nh + 2 are appended: lane (kq, bm, jq) = 16 kq + 4 bm + jq holds row
+    4 r + jq of the panel; mBase = the lanes of the new rows (the full groups), mLast = those of the blocks in front of the
+    row's own diagonal tile (block (NKT + r) & 3 of its group).  Zero when no new row lies in tile row r."""
+    j0, j1 = max(nh - 4 * r, 0), min(nh + T_ROWS - 4 * r, 4)
+    nib = sum(1 << j for j in range(j0, j1))                     # the new rows' jq inside one block
+    b = u_of(r) & 3
+    row16 = sum(nib << (4 * bm) for bm in range(b))              # the blocks bm < b of one DPP row (one kq)
+    return nib * 0x1111111111111111, row16 * 0x0001000100010001
+
+
+def emit_append(f):
+    f.write("// ---- the append of step t, n_h = 3 t: the steps of an epoch and the EXEC masks of the panel writes as constants ------------\n")
+    f.write(f"constexpr int kOneAppendSteps = {APPEND_STEPS};\n")
+    f.write("template <int K> struct OneEpoch;\n")
+    for K in Map().gd:
+        s = epoch_steps(K)
+        f.write(f"template <> struct OneEpoch<{K}> {{ static constexpr int t_begin = {s.start}, t_end = {s.stop}; }};\n")
+    f.write("template <int R, int NH> struct OneRowMask;\n")
+    for t in range(APPEND_STEPS):
+        for r in append_rows(t):
+            mb, ml = append_row_masks(r, T_ROWS * t)
+            f.write(f"template <> struct OneRowMask<{r}, {T_ROWS * t}> {{ static constexpr unsigned long long base = 0x{mb:016x}ull, last = 0x{ml:016x}ull; }};\n")
+    f.write("// the masked writes of tile row R for the new rows NH .. NH + 2 (hidden form: see one_hset_row)\n")
+    f.write("template <int R, int NH>\n__device__ __forceinline__ void one_hset_row_at(const double* V) {\n"
+            "    one_hset_row<R>(OneRowMask<R, NH>::base, OneRowMask<R, NH>::last, V);\n}\n")
+
+
 def emit(f):
     m = Map()
     f.write(f"// ---- NKT = {NKT}, {NTR} tile rows: {m.count} panels in a[0:{2 * m.count - 1}] ----------------------------------------------------\n")
@@ -401,6 +460,7 @@ def emit(f):
     disp("one_set_gd", "void", "OnePanels& P, unsigned long long mask, double v", "P, mask, v", m.gd)
     disp("one_hset_gd", "void", "double v", "v", m.gd)
     disp("one_touch_gd", "void", "OnePanels& P", "P", m.gd)
+    emit_append(f)
 
 
 def generic(f):

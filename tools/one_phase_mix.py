@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""Static instruction mix of rollout_one_kernel per epoch and phase of the step (CPU only: hipcc cross-compiles).
+
+Compiles rollout_one.hip to assembly with the flags of csrc/build.py plus -DGPMPC_ONE_PHASE_MARKS, which turns the phase
+timers' positions (OPH(i): the phase that ENDS there) and the bounds of the cold block into comments of the ISA, and counts the
+instructions between the marks of the LEAN instantiation (--full: the other one) by class:
+
+    VALU (every v_* but the MFMAs; v_cmp / v_cndmask / DPP / v_accvgpr_write are counted again in columns of their own),
+    MFMA, SALU (s_* without branches, s_nop and s_waitcnt), branch, s_nop, LDS (ds_*), wait (s_waitcnt), mem (global / flat / SMEM)
+
+The marks are asm statements: like the timers they fence the scheduler, so the counts are those of the marked build - a few
+instructions off the shipped one.  The attribution is by position in the file: code between two marks belongs to the phase the
+second one ends.  The step blocks of the append (one per step t) each carry their own marks; their counts are summed over
+the blocks of the epoch, and `blocks` says how many there are - a step runs ONE of them.
+
+    python tools/one_phase_mix.py [--full] [--src DIR]      DIR: another csrc directory (e.g. a checkout of the parent commit)
+"""
+import collections
+import importlib.util
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
+PHASES = {"0": "entries: LDS reads", "1": "entries: products + writes", "2": "solve", "3": "Gram + extract", "4": "sample",
+          "5": "append: panel writes", "6": "append: diagonal tiles", "7": "state"}
+COLS = ["VALU", "v_cmp", "v_cndmask", "DPP", "v_accvgpr_write", "MFMA", "SALU", "branch", "s_nop", "LDS", "wait", "mem"]
+KFIRST = 2
+
+
+def compile_to_isa(csrc):
+    spec = importlib.util.spec_from_file_location("gpmpc_build", os.path.join(CSRC, "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    out = os.path.join(tempfile.mkdtemp(prefix="gpmpc_mix_"), "rollout_one.s")
+    # (the quoted includes of rollout_one.hip are found beside it first: --src compiles that directory's headers)
+    flags = [f for f in b.FLAGS if f != "-fPIC"] + ["-DGPMPC_ONE_PHASE_MARKS"]
+    cmd = [b.HIPCC, "-x", "hip", "-S", "--cuda-device-only", os.path.join(csrc, "rollout_one.hip"), "-o", out] + flags + \
+        b.EXTRA_FLAGS.get("rollout_one.hip", [])
+    subprocess.run(cmd, check=True, capture_output=True)
+    return out
+
+
+def classes(op, text):
+    if op.startswith("v_mfma"):
+        return ["MFMA"]
+    if op.startswith("v_"):
+        c = ["VALU"]
+        if op.startswith("v_cmp"):
+            c.append("v_cmp")
+        if op.startswith("v_cndmask"):
+            c.append("v_cndmask")
+        if "_dpp" in op or " row_" in text or "quad_perm" in text:
+            c.append("DPP")
+        if op.startswith("v_accvgpr_write"):
+            c.append("v_accvgpr_write")
+        return c
+    if op.startswith("ds_"):
+        return ["LDS"]
+    if op in ("s_branch", "s_setpc_b64") or op.startswith("s_cbranch"):
+        return ["branch"]
+    if op == "s_nop":
+        return ["s_nop"]
+    if op == "s_waitcnt":
+        return ["wait"]
+    if op.startswith(("global_", "flat_", "buffer_", "scratch_", "s_load", "s_buffer_load")):
+        return ["mem"]
+    if op.startswith("s_"):
+        return ["SALU"]
+    return []
+
+
+def scan(path, lean=True):
+    want = "ILi4ELi0ELb1EEE" if lean else "ILi4ELi0ELb0EEE"
+    table = collections.OrderedDict()           # (epoch label, phase label) -> Counter
+    blocks = collections.Counter()              # epoch label -> marks "1" seen (step blocks)
+    inside, cold, epoch = False, False, "prologue"
+    pending = collections.Counter()
+    code_len = None
+
+    def flush(key):
+        nonlocal pending
+        table.setdefault(key, collections.Counter()).update(pending)
+        pending = collections.Counter()
+
+    k = KFIRST
+    for raw in open(path):
+        t = raw.strip()
+        m = re.match(r"^(_Z\w+):", t)
+        if m:
+            inside = "rollout_one_kernel" in m.group(1) and want in m.group(1)
+            continue
+        if not inside:
+            continue
+        if t.startswith("; codeLenInByte"):
+            code_len = int(t.split("=")[1])
+            inside = False
+            continue
+        m = re.match(r"^; one_phase_(\w+) (\w+)", t)
+        if m:
+            kind, what = m.groups()
+            if kind == "end" and what == "prologue":
+                flush(("prologue", "kernel entry .. step loop"))
+                epoch = f"K = {k}"
+            elif kind == "cold" and what == "begin":
+                flush((epoch, "(between the marks: loop control, joins)"))
+                cold = True
+            elif kind == "cold" and what == "end":
+                flush((epoch, "cold block (clip, repair)"))
+                cold = False
+            elif kind == "end":
+                flush((epoch, PHASES[what]))
+                if what == "1":
+                    blocks[epoch] += 1
+                if what == "7":
+                    k += 1
+                    epoch = f"K = {k}"
+            continue
+        code = t.split(";")[0].strip()
+        if not code or code.startswith(".") or code.endswith(":"):
+            continue
+        op = code.split()[0]
+        pending.update(classes(op, code))
+        pending["all"] += 1
+    flush(("epilogue", "behind the last mark (rare paths of the last epoch, epilogue)"))
+    return table, blocks, code_len
+
+
+def main():
+    csrc = CSRC
+    if "--src" in sys.argv:
+        csrc = os.path.abspath(sys.argv[sys.argv.index("--src") + 1])
+    path = compile_to_isa(csrc)
+    table, blocks, code_len = scan(path, lean="--full" not in sys.argv)
+    print(f"{path}: rollout_one_kernel<4, pendulum1D, {'LEAN' if '--full' not in sys.argv else 'full'}>, codeLenInByte = {code_len}\n")
+    print("| epoch | phase | all | " + " | ".join(COLS) + " |")
+    print("|---|---|---|" + "---|" * len(COLS))
+    last = None
+    for (epoch, phase), c in table.items():
+        if c["all"] == 0:
+            continue
+        label = epoch
+        if epoch != last and blocks.get(epoch):
+            label += f" ({blocks[epoch]} step block{'s' if blocks[epoch] > 1 else ''})"
+        last = epoch
+        print(f"| {label} | {phase} | {c['all']} | " + " | ".join(str(c[k]) for k in COLS) + " |")
+
+
+if __name__ == "__main__":
+    main()
