@@ -645,6 +645,49 @@ int     gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
                              double* P /* (B, H+1, nx, nx) */, double* S /* (B, H, g_ny) or NULL */,
                              double* A /* (B, H, nx, nx) or NULL */, int32_t* info /* (B) */, void* stream);
 
+/*
+ * gpmpc_tube_gram / gpmpc_tube_apply - the two device pieces of the condensed tube QP, the QP step of the
+ * sampled-dynamics OCP.  Additive entry points: the ABI version stays 12.
+ * Replaces: what reference src/utils/ocp.py / src/utils/model.py:6-95 hand to acados (FULL_CONDENSING_HPIPM): Ns affine models per
+ * stage that share one input sequence.  For sample i and t = 0..H-1:  x_{i,t+1} = A_{i,t} x_{i,t} + B_{i,t} v_t + c_{i,t}, x_{i,0}
+ * given, so x_{i,t} = G_{i,t} v + g_{i,t} with v = (v_0 .. v_{H-1}) in R^n, n = H nu, G_{i,0} = 0 and
+ * G_{i,t+1} = A_{i,t} G_{i,t} + B_{i,t} S_t (S_t selects v_t).  G_{i,t} (nx x n) is never stored in device memory.
+ *   A      [dev] (Ns, nx, H, nx)     the layout of y_grad of gpmpc_assemble_jacobians (row, stage, column)
+ *   B      [dev] (Ns, nx, H, nu)     the layout of u_grad
+ *
+ * gpmpc_tube_gram:
+ *   Theta  [dev] (Ns, H+1, nx, nx)   symmetric (read as given); or NULL: only b is computed
+ *   Xi     [dev] (Ns, H, nx, nu)     or NULL (needs Theta)
+ *   eta    [dev] (Ns, H+1, nx)       or NULL: b is not computed
+ *   W      [dev] (n, n)   out = sum_i sum_t [ G_{i,t}^T Theta_{i,t} G_{i,t} + G_{i,t}^T Xi_{i,t} S_t + (G_{i,t}^T Xi_{i,t} S_t)^T ]
+ *                         (NULL exactly when Theta is NULL); the lower triangle is computed and mirrored: exactly symmetric
+ *   b      [dev] (n)      out = sum_i sum_t G_{i,t}^T eta_{i,t}   (NULL exactly when eta is NULL)
+ * Stage 0 of Theta and eta multiplies G_{i,0} = 0 and is not read.  One workgroup walks a fixed block of samples and keeps W's
+ * lower 16 x 16 tiles in MFMA accumulators (v_mfma_f64_16x16x4_f64, one K-step per stage and tile); its partial sums go to the
+ * workspace and a second kernel adds them in a fixed order.  No floating-point atomics: the same call gives the same bits
+ * twice, and the number of partials is a function of Ns only.
+ * gpmpc_tube_gram_workspace_bytes(Ns, H, nx, nu): the workspace of any call with these sizes (0 for sizes outside the limits).
+ *
+ * gpmpc_tube_apply: the linearised tubes of n_seq candidate input sequences in one launch, one (sequence, sample) per lane:
+ *   c      [dev] (Ns, nx, H)         or NULL (zero): the layout of gp_val (Ns, nx, H, 1)
+ *   x0     [dev] (Ns, nx)            or NULL (zero).  With c and x0 both NULL the result is G v: the tube of a DIRECTION
+ *   V      [dev] (n_seq, H, nu)
+ *   X      [dev] (n_seq, Ns, nx, H+1) out: X[k][i][:, t] = G_{i,t} v^(k) + g_{i,t}, the tube layout of gpmpc_rollout's X_traj
+ * A sample's bits depend on nothing but its own A, B, c, x0 and the sequence: not on Ns, its position, n_seq or k.
+ *
+ * Limits (the contract): 1 <= nx <= 4, 1 <= nu <= 2, n = H nu <= 128, Ns < 2^31 (apply: n_seq Ns < 2^31); GPMPC_E_UNSUPPORTED
+ * beyond, before any device work.  This covers the pendulum (nx 2, nu 1) and the car (nx 4, nu 2) up to H = 64.
+ * GPMPC_E_ARG (before any device work): Ns, H, nx, nu or n_seq < 1; NULL A or B; gram: Theta and eta both NULL, W without Theta
+ * or Theta without W, b without eta or eta without b, Xi without Theta; apply: NULL V or X.  GPMPC_E_WORKSPACE: NULL workspace
+ * or fewer bytes than gpmpc_tube_gram_workspace_bytes().  No hidden allocation, no host round trip, everything goes to `stream`.
+ */
+size_t  gpmpc_tube_gram_workspace_bytes(int64_t Ns, int32_t H, int32_t nx, int32_t nu);
+int     gpmpc_tube_gram(int64_t Ns, int32_t H, int32_t nx, int32_t nu, const double* A, const double* B, const double* Theta,
+                        const double* Xi, const double* eta, double* W, double* b, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int     gpmpc_tube_apply(int64_t Ns, int32_t H, int32_t nx, int32_t nu, int32_t n_seq, const double* A, const double* B,
+                         const double* c, const double* x0, const double* V, double* X, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,10 +13,13 @@ from .small_ball import (SmallBall, reference_grid, posterior_on_grid, sup_devia
 from .mle import (MarginalLikelihood, FitResult, marginal_likelihood, pack_theta, unpack_theta, theta_from_params,  # noqa: F401
                   theta_to_params, fit_hyperparameters, restarts, rkhs_norm_and_beta)
 from .moments import MomentTube, moment_rollout, moment_rollout_plan    # noqa: F401
+from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, solve_tube_qp  # noqa: F401
+from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
            "HullQuery", "hull_query", "tube_coverage", "SmallBall", "reference_grid", "posterior_on_grid", "sup_deviation",
            "small_ball_probability", "sup_deviation_quantile", "required_samples", "MarginalLikelihood", "FitResult",
            "marginal_likelihood", "pack_theta", "unpack_theta", "theta_from_params", "theta_to_params", "fit_hyperparameters",
-           "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan"]
+           "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "TubeQP", "TubeQPResult",
+           "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver"]

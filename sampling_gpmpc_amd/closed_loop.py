@@ -12,6 +12,9 @@ reference ``src/solver.py:56-156`` as far as it touches the hot path - ``train_h
 ``p_lin`` in the acados layout, packed on the device - with the QP step replaced by the deterministic surrogate SURVEY.md
 section 8d names: the next iterate's linearisation point of stage j+1 is the sample mean of stage j's predicted next
 state, inputs stay at the nominal sequence.  With acados present a ``DEMPC_solver`` can be dropped in unchanged.
+
+``CondensedSolver`` runs the same loop and DOES solve the QP: the condensed tube QP of ``tube_qp.py`` on the
+device, full step.  ``SurrogateSolver`` remains ``ClosedLoop``'s default.
 """
 from __future__ import annotations
 
@@ -85,6 +88,94 @@ class SurrogateSolver:
             if sqp_iter >= 1 and x_diff < self.tol_nlp:
                 break
         return 0
+
+    def get_solution(self):
+        return self.x_h.copy(), self.u_h.copy(), np.zeros(self.H + 1)
+
+    def get_and_shift_solution(self):
+        X, U, Sl = self.get_solution()
+        self.x_h[:-1] = X[1:]
+        self.u_h[:-1] = U[1:]
+        return X, U, Sl
+
+
+class CondensedSolver:
+    """SQP driver with ``SurrogateSolver``'s surface whose QP step is the condensed tube QP (``tube_qp.solve_tube_qp``) on the device:
+    after ``sqp_linearisation`` the QP of the Jacobians is solved and the full step taken - ``u_h <- v*``, ``x_h <-`` the per-sample
+    states of the QP, as acados returns them.  The loop ends as the reference's does (``src/solver.py:74-81,146-151``): on a QP that
+    does not end ``OK`` (``solve`` then returns 1), or once ``x_h`` and ``u_h`` both move less than ``tol_nlp``.
+
+    ``qp_status``: the status of every QP solved so far; ``record=True`` also keeps ``(TubeQP, TubeQPResult)`` pairs in ``qp_log``.
+    An agent without ``sqp_linearisation`` (the oracle) is driven through the reference-shaped calls; the QP runs on ``device``
+    either way - there is no host solver."""
+
+    def __init__(self, params, u_nominal: Optional[np.ndarray] = None, qp_tol: float = 1e-8, qp_max_iter: int = 50,
+                 record: bool = False, device="cuda"):
+        self.params = params
+        self.H = params["optimizer"]["H"]
+        self.max_sqp_iter = params["optimizer"]["SEMPC"]["max_sqp_iter"]
+        self.tol_nlp = params["optimizer"]["SEMPC"]["tol_nlp"]
+        self.nx, self.nu = params["agent"]["dim"]["nx"], params["agent"]["dim"]["nu"]
+        self.ns = params["agent"]["num_dyn_samples"]
+        self.x_h = np.zeros((self.H + 1, self.nx * self.ns))
+        self.u_h = np.zeros((self.H, self.nu)) if u_nominal is None else np.array(u_nominal, dtype=np.float64).reshape(self.H, self.nu)
+        self.qp_tol, self.qp_max_iter, self.record, self.device = qp_tol, qp_max_iter, record, device
+        self.p_lin = None
+        self.iterations = 0
+        self.gp_ms, self.qp_ms = [], []                           # per SQP iteration: GP side and QP wall time (ms)
+        self.qp_status, self.qp_log = [], []
+
+    def set_initial_state(self, st_curr):
+        st = np.asarray(st_curr, dtype=np.float64).reshape(-1)
+        if st.size != self.nx * self.ns:
+            raise ValueError("st_curr must hold the current state once per sample (Ns * nx values)")
+        if not np.any(self.x_h):
+            self.x_h[:] = st[None, :]
+        self.x_h[0] = st
+
+    def solve(self, player) -> int:
+        from .tube_qp import OK, TubeQP, solve_tube_qp
+        p = self.params
+        H, ns, nx = self.H, self.ns, self.nx
+        fb = p["agent"]["feedback"]["use"]
+        K = np.array(p["optimizer"]["terminal_tightening"]["K"]) if fb else None
+        x_equi = np.array(p["env"]["goal_state"])
+        w = np.ones(H + 1) * p["optimizer"].get("w", 1.0)
+        xg = np.ones(H + 1) * np.asarray(player.get_next_to_go_loc(), dtype=np.float64).reshape(-1)[0]
+        self.gp_ms, self.qp_ms = [], []
+        status = 0
+        for sqp_iter in range(self.max_sqp_iter):
+            x_old, u_old = self.x_h.copy(), self.u_h.copy()
+            xs = self.x_h[:H]
+            t0 = time.perf_counter()
+            u_fb = (-(x_equi - xs.reshape(H, ns, -1)) @ K.T + np.tile(self.u_h[:, None, :], (ns, 1))) if fb else None
+            if hasattr(player, "sqp_linearisation"):
+                self.p_lin = player.sqp_linearisation(xs, u_fb if fb else self.u_h, sqp_iter, xg, w, K=K, u_nominal=self.u_h)
+                jac = None                                        # the Agent's device Jacobians, read in place
+            else:
+                player.train_hallucinated_dynGP(sqp_iter)
+                x_hat = player.get_batch_x_hat_u_diff(xs, u_fb) if fb else player.get_batch_x_hat(xs, self.u_h)
+                jac = tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(self.device)
+                            for a in player.dyn_fg_jacobians(x_hat, sqp_iter))
+            self.gp_ms.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            qp = TubeQP.from_agent(player, self.x_h, self.u_h, K=K, xg=xg[0], jacobians=jac)
+            res = solve_tube_qp(qp, v0=self.u_h, tol=self.qp_tol, max_iter=self.qp_max_iter)
+            self.qp_ms.append((time.perf_counter() - t0) * 1e3)
+            self.qp_status.append(res.status)
+            if self.record:
+                self.qp_log.append((qp.clone(), res))              # the Agent's Jacobian buffers are reused
+            self.iterations = sqp_iter + 1
+            if res.status != OK:
+                status = 1
+                break
+            self.u_h = res.v.cpu().numpy().reshape(H, self.nu)
+            self.x_h = res.X.permute(2, 0, 1).reshape(H + 1, ns * nx).cpu().numpy()
+            x_diff = np.linalg.norm(self.x_h - x_old) / (np.linalg.norm(x_old) + 1e-6)
+            u_diff = np.linalg.norm(self.u_h - u_old) / (np.linalg.norm(u_old) + 1e-6)
+            if sqp_iter >= 1 and x_diff < self.tol_nlp and u_diff < self.tol_nlp:
+                break
+        return status
 
     def get_solution(self):
         return self.x_h.copy(), self.u_h.copy(), np.zeros(self.H + 1)
