@@ -688,6 +688,63 @@ int     gpmpc_tube_gram(int64_t Ns, int32_t H, int32_t nx, int32_t nu, const dou
 int     gpmpc_tube_apply(int64_t Ns, int32_t H, int32_t nx, int32_t nu, int32_t n_seq, const double* A, const double* B,
                          const double* c, const double* x0, const double* V, double* X, void* stream);
 
+/*
+ * gpmpc_tube_rows - the constraint rows of the sampled-dynamics OCP over a tube: n_lin affine and n_quad quadric
+ * rows at every (sample, stage), their gradients, and the violation statistics per (stage, row) and per sample.  Additive entry
+ * point: the ABI version stays 12.
+ * Replaces: the constraint expressions of reference src/utils/ocp.py:47-104 (the car's obstacle ellipses 47-58, the tightened
+ * state box and the input rows under feedback 59-92, the pendulum's terminal ellipsoid 94-104) with the bounds of
+ * ocp.py:186-241, which casadi evaluates inside acados and which nothing evaluates over a sampled tube or the true reachable set.
+ *
+ * Input
+ *   X      [dev] the tube, read in place: element (i, k, t) at X[i*stride_sample + k*stride_dim + t*stride_stage], strides in
+ *                doubles as in gpmpc_hull_query.  The (Ns, nx, H+1) tube of gpmpc_rollout / gpmpc_tube_apply is
+ *                (nx (H+1), H+1, 1); one sequence of a gpmpc_tube_apply result or a permuted view is read without a copy.
+ *   Ns, T = H+1 stages, 1 <= nx <= 4
+ *   E      [dev] (n_lin, nx), off [dev] (T, n_lin) or NULL (zero): affine row r at stage t is  E_r x + off[t, r]  (off carries F v_t
+ *                and -K x_goal for the input rows under feedback): v = E_r0 x_0, then v = fma(E_rk, x_k, v) for k = 1..nx-1, then
+ *                v + off
+ *   M      [dev] (n_quad, nx, nx) symmetric, READ AS GIVEN, c [dev] (n_quad, nx): quadric row q is d^T M d with d = x - c, in one
+ *                fixed order: s_k = M_k0 d_0, s_k = fma(M_kl, d_l, s_k) for l = 1..nx-1; v = d_0 s_0, v = fma(d_k, s_k, v).  Zero
+ *                rows and columns of M are allowed (the car's ellipse is diag(1/a, 1/b, 0, 0), a and b as the YAML gives them:
+ *                ocp.py:54-56 divides by them unsquared).  Rows are numbered affine first: n_rows = n_lin + n_quad.
+ *   lo, hi [dev] (T, n_rows), +-inf allowed: a side that is not finite takes no part; a row with no finite side at a stage is
+ *                INACTIVE there (the terminal ellipsoid is active at t = H only).  May be NULL when only val / grad are wanted.
+ *   tol    >= 0
+ * margin(i, t, r) = min(val - lo, hi - val) over the finite sides.  A state with a non-finite coordinate (failed chains leave NaN)
+ * counts as a VIOLATION of every active row of its stage: its margin is -inf in worst and min_margin, it is counted in n_viol,
+ * and the stage carries GPMPC_TUBE_ROWS_NONFINITE; a margin that comes out NaN is -inf likewise.  This is the one place where the
+ * entry point differs from gpmpc_hull_query, which IGNORES such points: there the question is coverage, here it is safety, and
+ * an unsafe answer must not look safe.
+ * Outputs - each may be NULL (not wanted), at least one must be given:
+ *   val        [dev] (Ns, T, n_rows)           the row values (also at stages where the row is inactive)
+ *   grad       [dev] (Ns, T, n_quad, nx)       2 M d = 2 s.  An affine row's gradient is E
+ *   n_viol     [dev] (T, n_rows) int32         samples with margin < -tol (0 for an inactive row)
+ *   min_margin [dev] (T, n_rows)               minimum over the samples, NaN for an inactive row
+ *   argmin     [dev] (T, n_rows) int32         the lowest sample index attaining it, -1 for an inactive row
+ *   info       [dev] (T) uint32                GPMPC_TUBE_ROWS_* bits
+ *   worst      [dev] (Ns)                      the sample's minimum margin over all active (stage, row), NaN if there is none
+ *   first_out  [dev] (Ns) int32                the first stage with any margin < -tol, -1 if never
+ * The reductions are taken from the very values that are (or would be) written to val - they equal a host reduction of the
+ * returned array with the rule above for non-finite states - and are the same bits with or without val, on every run and for
+ * every Ns: each is a count, an OR, or a minimum whose ties (+0 and -0 compare equal) go to the lowest index.  A sample's val /
+ * grad bits depend on nothing but its own state and the row data: not on Ns, its position, or which outputs are wanted.  No
+ * atomics are used; the per-(stage, row) results go through one 24-byte record per (64-sample tile, stage, row) in the workspace
+ * (gpmpc_tube_rows_workspace_bytes(); 0 for sizes outside the limits) and a finishing kernel.
+ * Limits: nx <= 4, n_lin <= 16, n_quad <= 8, Ns < 2^31 (and T n_rows < 2^31); GPMPC_E_UNSUPPORTED beyond, before any device work.
+ * All launches go to `stream`; no hidden allocation, no host round trip.  GPMPC_E_ARG (before any device work): NULL X; Ns, T or
+ * nx < 1; n_lin or n_quad < 0 or both 0; NULL E with n_lin > 0; NULL M or c with n_quad > 0; off without affine rows; grad
+ * without quadric rows; all outputs NULL; NULL lo or hi when a reduction is wanted; tol < 0 or NaN.  GPMPC_E_WORKSPACE: a
+ * per-(stage, row) output wanted with a NULL workspace or fewer bytes than gpmpc_tube_rows_workspace_bytes().
+ */
+#define GPMPC_TUBE_ROWS_NONFINITE 0x1u  /* at least one sample of the stage had a non-finite state                            */
+size_t  gpmpc_tube_rows_workspace_bytes(int64_t Ns, int32_t T, int32_t n_lin, int32_t n_quad);
+int     gpmpc_tube_rows(const double* X, long long stride_sample, long long stride_dim, long long stride_stage, int64_t Ns,
+                        int32_t T, int32_t nx, const double* E, const double* off, int32_t n_lin, const double* M,
+                        const double* c, int32_t n_quad, const double* lo, const double* hi, double tol, double* val,
+                        double* grad, int32_t* n_viol, double* min_margin, int32_t* argmin, double* worst, int32_t* first_out,
+                        uint32_t* info, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

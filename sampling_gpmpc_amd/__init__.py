@@ -14,6 +14,8 @@ from .mle import (MarginalLikelihood, FitResult, marginal_likelihood, pack_theta
                   theta_to_params, fit_hyperparameters, restarts, rkhs_norm_and_beta)
 from .moments import MomentTube, moment_rollout, moment_rollout_plan    # noqa: F401
 from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, solve_tube_qp  # noqa: F401
+# the wrapper tube_rows.tube_rows is not re-exported: the name is the module's
+from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
@@ -22,4 +24,5 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "small_ball_probability", "sup_deviation_quantile", "required_samples", "MarginalLikelihood", "FitResult",
            "marginal_likelihood", "pack_theta", "unpack_theta", "theta_from_params", "theta_to_params", "fit_hyperparameters",
            "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "TubeQP", "TubeQPResult",
-           "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver"]
+           "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
+           "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube"]

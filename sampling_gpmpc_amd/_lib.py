@@ -34,6 +34,7 @@ INFO_NONFINITE = 0x0800                                 # gpmpc_moment_rollout
 HULL_OVERFLOW, HULL_NONFINITE, HULL_EMPTY, HULL_DEGENERATE = 0x1, 0x2, 0x4, 0x8
 # gpmpc_hull_query: per-set info word
 HULLQ_BAD_HULL, HULLQ_NONFINITE, HULLQ_EMPTY_HULL = 0x1, 0x2, 0x4
+TUBE_ROWS_NONFINITE = 0x1                               # gpmpc_tube_rows: per-stage info word
 
 ROOT_AUTO, ROOT_EIGH, ROOT_CHOLESKY = 0, 1, 2
 # gpmpc_rollout_pin_kernel / gpmpc_rollout_last_kernel (include/gpmpc_hip.h)
@@ -107,6 +108,9 @@ SYMBOLS = {
     "gpmpc_tube_gram_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "gpmpc_tube_gram": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gpmpc_tube_apply": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_tube_rows_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
+    "gpmpc_tube_rows": (C.c_int, [_P, C.c_longlong, C.c_longlong, C.c_longlong, _I64, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _P,
+                                  _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -105,13 +105,18 @@ class CondensedSolver:
     states of the QP, as acados returns them.  The loop ends as the reference's does (``src/solver.py:74-81,146-151``): on a QP that
     does not end ``OK`` (``solve`` then returns 1), or once ``x_h`` and ``u_h`` both move less than ``tol_nlp``.
 
+    ``nonlinear_rows=True`` solves the reference's problem where it has nonlinear constraints: every QP then carries the pendulum's slacked
+    terminal ellipsoid, or a bicycle configuration's ``env.ellipses`` with the slacked state box, linearised at the iterate
+    (``TubeQP.from_agent(..., nonlinear=True)``); the default leaves them out, as before.
+
     ``qp_status``: the status of every QP solved so far; ``record=True`` also keeps ``(TubeQP, TubeQPResult)`` pairs in ``qp_log``.
     An agent without ``sqp_linearisation`` (the oracle) is driven through the reference-shaped calls; the QP runs on ``device``
     either way - there is no host solver."""
 
     def __init__(self, params, u_nominal: Optional[np.ndarray] = None, qp_tol: float = 1e-8, qp_max_iter: int = 50,
-                 record: bool = False, device="cuda"):
+                 record: bool = False, device="cuda", nonlinear_rows: bool = False):
         self.params = params
+        self.nonlinear_rows = bool(nonlinear_rows)
         self.H = params["optimizer"]["H"]
         self.max_sqp_iter = params["optimizer"]["SEMPC"]["max_sqp_iter"]
         self.tol_nlp = params["optimizer"]["SEMPC"]["tol_nlp"]
@@ -159,7 +164,7 @@ class CondensedSolver:
                             for a in player.dyn_fg_jacobians(x_hat, sqp_iter))
             self.gp_ms.append((time.perf_counter() - t0) * 1e3)
             t0 = time.perf_counter()
-            qp = TubeQP.from_agent(player, self.x_h, self.u_h, K=K, xg=xg[0], jacobians=jac)
+            qp = TubeQP.from_agent(player, self.x_h, self.u_h, K=K, xg=xg[0], jacobians=jac, nonlinear=self.nonlinear_rows)
             res = solve_tube_qp(qp, v0=self.u_h, tol=self.qp_tol, max_iter=self.qp_max_iter)
             self.qp_ms.append((time.perf_counter() - t0) * 1e3)
             self.qp_status.append(res.status)

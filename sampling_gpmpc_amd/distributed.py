@@ -382,6 +382,41 @@ def all_reduce_hull_query(q, group=None):
                                argmin=torch.where(none, torch.full_like(idx, -1), idx).to(q.argmin.dtype), info=info)
 
 
+def all_reduce_tube_check(chk, group=None):
+    """The per-(stage, row) results of a ``tube_rows.check_tube`` of a sample-sharded tube against replicated rows, over the whole tube:
+    ``n_viol`` and ``n_safe`` are summed, ``info`` is ORed, ``min_margin`` is the minimum and ``argmin`` becomes the GLOBAL sample index - the
+    shard's first index is the number of samples on the ranks below it, as in ``all_reduce_hull_query`` - with the lowest index among
+    equal minima, as on one device; ``Ns`` becomes the total.  The per-sample outputs (``worst``, ``first_out``) stay local.  Returns a new
+    ``TubeCheck``; works on the tensors' own device (CPU tensors under gloo).  Three small collectives and one host read (``Ns``)."""
+    import dataclasses
+    rank, world = dist.get_rank(group), dist.get_world_size(group)
+    dev, shape = chk.n_viol.device, chk.n_viol.shape
+    sizes = torch.zeros(world, dtype=torch.int64, device=dev)
+    sizes[rank] = int(chk.Ns)
+    # one SUM carries the counts, the info bit (a sum > 0 is the OR: RCCL has no bitwise reduction) and every shard's size
+    packed = torch.cat([chk.n_viol.reshape(-1).to(torch.int64), (chk.info.to(torch.int64) & 1), chk.n_safe.reshape(1).to(torch.int64),
+                        sizes])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    n_cells, T = chk.n_viol.numel(), chk.info.shape[0]
+    n_viol = packed[:n_cells].reshape(shape).to(chk.n_viol.dtype)
+    info = (packed[n_cells:n_cells + T] > 0).to(chk.info.dtype)
+    n_safe = packed[n_cells + T]
+    all_sizes = packed[n_cells + T + 1:]
+    lo = all_sizes[:rank].sum()
+    # an inactive row (NaN on every rank) takes no part in the minimum
+    m = torch.where(torch.isnan(chk.min_margin), torch.full_like(chk.min_margin, float("inf")), chk.min_margin)
+    dist.all_reduce(m, op=dist.ReduceOp.MIN, group=group)
+    big = torch.iinfo(torch.int64).max
+    local = chk.argmin.to(torch.int64)
+    idx = torch.where((local >= 0) & (chk.min_margin == m), local + lo, torch.full_like(local, big))
+    dist.all_reduce(idx, op=dist.ReduceOp.MIN, group=group)
+    none = idx == big
+    _lib.host_wait(all_sizes)
+    return dataclasses.replace(chk, Ns=int(all_sizes.sum().item()), n_viol=n_viol, info=info, n_safe=n_safe,
+                               min_margin=torch.where(none, torch.full_like(m, float("nan")), m),
+                               argmin=torch.where(none, torch.full_like(idx, -1), idx).to(chk.argmin.dtype))
+
+
 def all_reduce_small_ball(result, group=None):
     """The counts of a ``small_ball.sup_deviation`` run whose samples are spread over the ranks, each rank having drawn its own
     ``offset`` slice of the global sample ids (the stream makes the union the run one device would have made): ``n_within``,
