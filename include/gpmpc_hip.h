@@ -58,7 +58,7 @@ extern "C" {
 #define GPMPC_INFO_BAD_HYPER         0x0400 /* gpmpc_marginal_likelihood: a candidate entry is non-finite, ell or outputscale <= 0,
                                              * or a noise variance < 0: every output of that problem is NaN               */
 #define GPMPC_INFO_NONFINITE         0x0800 /* gpmpc_moment_rollout: an input of the candidate or a value computed for it was
-                                             * not finite: its outputs are NaN from that step on                           */
+                                             * not finite: its outputs are NaN from that step on (gpmpc_pathwise_*: likewise) */
 
 /* root_mode of gpmpc_joint_sample */
 #define GPMPC_ROOT_AUTO      0   /* gpytorch: Cholesky with the jitter chain; if ANY chain of the batch fails all  */
@@ -744,6 +744,73 @@ int     gpmpc_tube_rows(const double* X, long long stride_sample, long long stri
                         const double* c, int32_t n_quad, const double* lo, const double* hi, double tol, double* val,
                         double* grad, int32_t* n_viol, double* min_margin, int32_t* argmin, double* worst, int32_t* first_out,
                         uint32_t* info, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * gpmpc_pathwise_fit / gpmpc_pathwise_eval / gpmpc_pathwise_rollout - pathwise (weight-space) samples of the real-data GP: Matheron's
+ * update of a random-Fourier-feature prior sample.  A sample is a closed-form FUNCTION fixed once - a weight vector over M features of
+ * the RBF kernel plus a correction vector over the N_r real training points - so evaluating it, its gradient or a whole H-step rollout
+ * needs no factor, no jitter and nothing that grows with the SQP iteration, the MPC step or the horizon: M + N_r trigonometric /
+ * kernel evaluations per point and output.  Additive entry points: the ABI version stays 12.
+ * Replaces: the sample-the-weights-once scheme of reference extra/approx_sampling_mpc/src/agent.py:793-870,938-977 (sample_weights draws
+ * the weights once per sample; get_dynamics_grad evaluates value, y_grad and u_grad as feature sums for all samples) in its GP form:
+ * there the features are casadi drone physics, here random Fourier features of the plan's RBF kernel conditioned on the real data.
+ *
+ * The contract.  Outputs o < g_ny, inputs xi in R^D, the value-only real-data GP of the plan (real_has_grad == 0); M even, F = M / 2.
+ *   omega [dev] (g_ny, F, D)   frequencies; the caller draws them once as z / ell[o][d], z ~ N(0, 1).  An input: nothing here draws them.
+ *   Z     [dev] (Ns, V) with row stride ldz >= V, V = g_ny * (M + N_r): standard normals.  Column o*(M+N_r) + j is the feature weight
+ *                w_{i,o,j} for j < M and the label-noise normal e_{i,o,j-M} for j >= M - exactly what
+ *                gpmpc_base_samples(seed, 1, 1, offset, Ns, V, beta = +inf, ...) writes, one row per GLOBAL sample id, so results do not
+ *                depend on chunking or on the GPU count (as gpmpc_sup_deviation arranges).  Any other Z is allowed.
+ *   prior sample   g_{i,o}(xi) = sqrt(outputscale_o / F) sum_f [ w_{i,o,2f} cos(omega_{o,f} . xi) + w_{i,o,2f+1} sin(omega_{o,f} . xi) ]
+ *   update vector  v_{i,o} = (K_o + Sigma)^-1 ( y_o - g_{i,o}(X_r) - sqrt(noise[0]) e_{i,o} ), (K_o + Sigma) exactly the matrix the plan
+ *                  factorised, applied through the plan's L_rr^-1 as gpmpc_plan_build forms alpha_r, followed by ONE step of iterative
+ *                  refinement against the plan's factor (v += (K_o + Sigma)^-1 (r - L_rr L_rr^T v): the explicit inverse alone leaves a
+ *                  residual ~cond(L_rr) times that of a triangular solve, and the prediction sees the residual).  With Z = 0 this is
+ *                  the plan's alpha_r (refined: equal to rounding, not bit for bit) and the sample is the posterior mean
+ *   posterior sample  f_{i,o}(xi) = g_{i,o}(xi) + sum_n k_o(xi, X_n) v_{i,o,n};  its gradient (D entries): the -omega sin / +omega cos
+ *                  terms plus the derivative rows of the RBF kernel
+ *
+ * gpmpc_pathwise_fit: the update vectors.
+ *   plan [dev] of gpmpc_plan_build, X_r [dev] (N_r, D), Y_r [dev] (g_ny, N_r, T) (task 0 is read)
+ *   Vout [dev] (Ns, g_ny, N_r) out;  info [dev] (Ns) int32 out: 0 or GPMPC_INFO_NONFINITE
+ * gpmpc_pathwise_eval: value and gradient of every sample at m points per (sample, output).
+ *   x    [dev] read in place, element (i, o, p, d) at x[i*stride_sample + o*stride_output + p*stride_point + d], strides in doubles,
+ *               >= 0: the (Ns, g_ny, m, D) tensor of get_g_xu_hat is (g_ny m D, m D, D); a shared (m, D) set is (0, 0, D)
+ *   V    [dev] (Ns, g_ny, N_r)   the update vectors
+ *   out  [dev] (Ns, g_ny, m, 1 + D) with want_grad, else (Ns, g_ny, m, 1): the layout of Agent.sample_gp, gpmpc_assemble_jacobians
+ *               consumes it unchanged.  The value bits are the same with and without want_grad.
+ *   info [dev] (Ns) int32 out
+ * gpmpc_pathwise_rollout: the H-step rollout of every sample in one launch; environment step, feedback law and GP input selection
+ * are those of gpmpc_rollout.
+ *   x0 [dev] (Ns, nx) if x0_per_sample else (nx);  U [dev] (Ns, H, nu) if u_per_sample else (H, nu) (may be NULL when H == 0)
+ *   X_traj [dev] (Ns, nx, H+1) out: the tube layout of gpmpc_rollout
+ *   Y      [dev] (Ns, g_ny, H, 1 + D) out or NULL: the sample's value and gradient at every visited point
+ *   info   [dev] (Ns) int32 out
+ * Non-finite rule: a sample with a non-finite entry in its Z row (all V columns) or in V has NaN in all its outputs; an evaluation
+ * point x with a non-finite coordinate, or a value computed there that is not finite, gives NaN at that (sample, output, point); in
+ * the rollout a non-finite x0 makes the whole sample NaN, and when U[t] or anything computed in step t is not finite, Y of the steps
+ * >= t and X_traj of the steps > t are NaN.  Every such sample carries GPMPC_INFO_NONFINITE; no other sample is touched.
+ * Reproducibility: a sample's bits depend on its own inputs alone, not on Ns or its position in the batch (one sample per wave, one
+ * kernel path, every reduction in a fixed order, no atomics); the rollout's Y at step t is bit-equal to gpmpc_pathwise_eval at the
+ * rollout's own point (one shared device function).
+ * Limits (the contract): real_has_grad == 0; N_r <= 64; M a multiple of 128 and at most 1024; Ns < 2^31; fit and eval D <=
+ * GPMPC_MAX_D; rollout D = 2 and the two environments (pendulum1D nx 2, nu 1, g_ny 1; car nx 4, nu 2, g_ny 3).  GPMPC_E_UNSUPPORTED
+ * beyond, before any device work.  Ns == 0 or m == 0: nothing is launched, and the array pointers are not looked at (descriptors and
+ * sizes are still checked).  No workspace, no hidden allocation, no host round trip, everything goes to `stream`.  GPMPC_E_ARG
+ * (before any device work): NULL gp or env; a bad gp descriptor; Ns, m or H < 0; M < 2 or odd; ldz < V; a negative stride; env.nx /
+ * env.nu / g_ny that do not belong to env.env_id; with work to do a NULL array other than Y (U only when H > 0).
+ */
+int     gpmpc_pathwise_fit(const gpmpc_gp_desc_t* gp, const void* plan, const double* X_r, const double* Y_r, int32_t M,
+                           const double* omega, int64_t Ns, const double* Z, int64_t ldz, double* Vout /* (Ns, g_ny, N_r) */,
+                           int32_t* info, void* stream);
+int     gpmpc_pathwise_eval(const gpmpc_gp_desc_t* gp, const double* X_r, int32_t M, const double* omega, int64_t Ns, int32_t m,
+                            const double* x, int64_t stride_sample, int64_t stride_output, int64_t stride_point, const double* Z,
+                            int64_t ldz, const double* V, int32_t want_grad, double* out, int32_t* info, void* stream);
+int     gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M,
+                               const double* omega, int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample, const double* U,
+                               int32_t u_per_sample, const double* Z, int64_t ldz, const double* V,
+                               double* X_traj /* (Ns, nx, H+1) */, double* Y /* (Ns, g_ny, H, 1+D) or NULL */, int32_t* info,
+                               void* stream);
 
 #ifdef __cplusplus
 }

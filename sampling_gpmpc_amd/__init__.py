@@ -17,6 +17,7 @@ from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, sol
 # the wrapper tube_rows.tube_rows is not re-exported: the name is the module's
 from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
+from .pathwise import PathwiseSamples, draw_omega, rff_kernel_error  # noqa: F401
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
@@ -25,4 +26,4 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "marginal_likelihood", "pack_theta", "unpack_theta", "theta_from_params", "theta_to_params", "fit_hyperparameters",
            "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "TubeQP", "TubeQPResult",
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
-           "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube"]
+           "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error"]

@@ -174,6 +174,7 @@ class Agent(object):
         self.debug_keep_root = False   # tests: keep the eigendecomposition root of the last joint draw (model_i_call.root)
         self._plans = {}          # T -> RealDataPlan (real block factorised once per label layout)
         self._ws_cache = {}
+        self._pathwise = None     # use_pathwise_samples: PathwiseSamples that stand in for the joint draw (None: the joint draw)
         # The hallucinated set grows by H points per SQP iteration and is reset once per MPC step - AFTER the model of iteration 0 has
         # been built (reference src/agent.py:261-272): a joint draw conditions on at most max_sqp_iter * H points.  The joint
         # workspace and the factor cache are sized for that once (multi-GiB device allocations cost 0.3-0.9 s each on this
@@ -414,6 +415,31 @@ class Agent(object):
         self.model_i_samples = y
         return y
 
+    def use_pathwise_samples(self, n_features, seed=0):
+        """Opt in to pathwise samples (``sampling_gpmpc_amd.pathwise``): ``get_batch_gp_sensitivities`` then evaluates ``self.ns``
+        fixed sample functions with ``n_features`` random Fourier features at the linearisation points instead of drawing jointly -
+        the same function at every SQP iteration and MPC step, no factor, no hallucinated set, no base samples.  A sharded Agent
+        draws its shard by global sample id.  ``use_pathwise_samples(None)`` restores the joint draw."""
+        if n_features is None:
+            self._pathwise = None
+            return None
+        from .pathwise import PathwiseSamples
+        self._pathwise = PathwiseSamples.draw(self, self.ns, int(n_features), int(seed), offset=(self.shard[0] if self.shard else 0))
+        return self._pathwise
+
+    def _pathwise_sensitivities(self, g_in, pinned):
+        """``get_batch_gp_sensitivities`` with the pathwise samples: value + gradient of every sample function at ``g_in``; the pinned
+        leading samples are overwritten as on the joint path (the mean is the ``Z = 0`` sample function)."""
+        pw = self._pathwise
+        y = pw.evaluate(g_in, want_grad=(self.in_dim_y != 1))
+        for slot, kind in enumerate(pinned):
+            if kind == "true_dyn":
+                truth = self.env_model.get_prior_data(g_in[slot, 0, :, :])
+                y[slot, :, :, :] = truth[:, :, [0]] if self.in_dim_y == 1 else truth
+            else:
+                y[[slot], :, :, :] = pw.mean_only().evaluate(g_in[[slot]], want_grad=(self.in_dim_y != 1))
+        return y
+
     def get_batch_gp_sensitivities(self, xu_hat, sqp_iter):
         """GP value+gradient sample at the linearisation points (reference ``src/agent.py:566-627``): a joint draw for
         every dynamics sample, except that the leading samples can be pinned - first to the true dynamics
@@ -422,6 +448,8 @@ class Agent(object):
         cfg = self.params["agent"]
         g_in = self.env_model.get_g_xu_hat(xu_hat).contiguous()
         pinned = [kind for kind, on in (("true_dyn", cfg["true_dyn_as_sample"]), ("mean", cfg["mean_as_dyn_sample"])) if on]
+        if self._pathwise is not None:
+            return self._pathwise_sensitivities(g_in, pinned)
         nothing_drawn = (len(pinned) >= 1 and self.ns == 1) or (len(pinned) == 2 and self.ns == 2)
         if nothing_drawn:
             y = torch.zeros((self.ns, self.g_ny, self.params["optimizer"]["H"], self.in_dim_y), dtype=F64,
@@ -461,7 +489,7 @@ class Agent(object):
         y_grad = flat[n1:n1 + n2].view(ns, self.nx, nH, self.nx)
         u_grad = flat[n1 + n2:].view(ns, self.nx, nH, self.nu)
         self._last_device_jacobians_flat = flat
-        plan = self.model_i.plan
+        plan = self.model_i.plan if self._pathwise is None else self._pathwise.plan
         _lib.check(lib.gpmpc_assemble_jacobians(plan.desc, self.env_desc(), ns, nH, _lib.dptr(xu_hat), _lib.dptr(y),
                                                 _lib.dptr(gp_val), _lib.dptr(y_grad), _lib.dptr(u_grad),
                                                 _lib.current_stream_ptr()), "gpmpc_assemble_jacobians")
@@ -578,7 +606,7 @@ class Agent(object):
         gp_val = flat[:n1].view(ns, nx, H, 1)
         y_grad = flat[n1:n1 + n2].view(ns, nx, H, nx)
         u_grad = flat[n1 + n2:].view(ns, nx, H, nu)
-        plan = self.model_i.plan
+        plan = self.model_i.plan if self._pathwise is None else self._pathwise.plan
         _lib.check(lib.gpmpc_assemble_jacobians_plin(plan.desc, self.env_desc(), ns, H, _lib.dptr(xu), _lib.dptr(y), _lib.dptr(gp_val),
                                                      _lib.dptr(y_grad), _lib.dptr(u_grad), _lib.dptr(seg[2]), _lib.dptr(seg[3]),
                                                      _lib.dptr(seg[4]), _lib.dptr(te), _lib.dptr(K_d), _lib.dptr(p_lin), stream),

@@ -1,0 +1,478 @@
+// Pathwise (weight-space) GP function samples: Matheron's update of a random-Fourier-feature prior sample (semantics:
+// include/gpmpc_hip.h, gpmpc_pathwise_fit / _eval / _rollout).  gfx950, wave64, FP64 on the vector pipe.
+//
+// A sample is a closed-form function fixed once: f(xi) = sqrt(os / F) sum_f [w_2f cos(omega_f . xi) + w_2f+1 sin(omega_f . xi)]
+//                                                       + sum_n k(xi, X_n) v_n.
+// Mapping: ONE SAMPLE PER WAVE in all three kernels.
+//   * lane l owns the frequencies f = l, l + 64, ... (F / 64 = M / 128 of them, <= 8): it reads their omega (shared by the samples,
+//     L2-resident) and its two weights per frequency from the sample's row of Z - neighbouring lanes read neighbouring 16-byte
+//     pairs, so a row is read in whole cache lines - takes ONE sincos per frequency and accumulates value and gradient in a fixed
+//     order (k = 0, 1, ...).  The features are re-read at every point instead of being pinned in registers: per point they are
+//     4 loads against a ~100-instruction FP64 sincos, and one instantiation serves every M (121 - 175 VGPRs);
+//   * lane n < N_r owns training row n: one exponential, k(xi, X_n) v_n and its derivative rows join the lane's partial sums;
+//   * value and gradient are reduced over the wave with the DPP ladder (wave_sum, gpmpc_device.hpp): a fixed order, no atomics.
+// pw_eval_point is the ONE evaluation function: gpmpc_pathwise_eval and every step of gpmpc_pathwise_rollout call the same
+// instantiation, so the rollout's Y is bit-equal to an evaluation at the rollout's own point.
+// The fit forms r = y - g(X_r) - sqrt(noise) e with pw_prior_lane at the training points, applies L_rr^-1 twice from LDS in the order
+// gpmpc_plan_build forms alpha_r, and refines once against the plan's factor L_rr.  Four samples share a workgroup's copy of both.
+#include "gpmpc_host.hpp"
+
+#include <climits>
+#include <cmath>
+
+namespace gpmpc {
+
+constexpr int PW_MAX_ROWS = 64;            // N_r: one training row per lane
+constexpr int PW_M_STEP = 128;             // M is a multiple of 128: every lane owns M / 128 (cos, sin) pairs
+constexpr int PW_MAX_M = 1024;
+constexpr int PW_LS = PW_MAX_ROWS + 1;     // LDS row stride of L_rr^-1 (odd: row-wise and column-wise reads are both conflict-free)
+
+__device__ __forceinline__ bool pw_finite(double v) { return fabs(v) < __builtin_inf(); }   // false for NaN and inf
+
+// the lane's share of the UNSCALED prior sample and of its gradient at xi: frequencies lane, lane + 64, ...
+//   om [F][D]: the output's frequencies;  zw [M]: the sample's feature weights of the output (w_2f with cos, w_2f+1 with sin)
+template <int D, bool GRAD>
+__device__ __forceinline__ void pw_prior_lane(const double* __restrict__ om, const double* __restrict__ zw, int F, int lane,
+                                              const double (&xi)[D], double& v, double (&g)[D]) {
+    v = 0.0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) g[d] = 0.0;
+#pragma unroll 2
+    for (int f = lane; f < F; f += kWave) {
+        double w[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) w[d] = om[(long)f * D + d];
+        const double wc = zw[2 * f], ws = zw[2 * f + 1];
+        double ang = w[0] * xi[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) ang = fma(w[d], xi[d], ang);
+        double sn, cs;
+        sincos(ang, &sn, &cs);
+        v = fma(wc, cs, v);
+        v = fma(ws, sn, v);
+        if (GRAD) {
+            const double t = fma(ws, cs, -(wc * sn));
+#pragma unroll
+            for (int d = 0; d < D; ++d) g[d] = fma(w[d], t, g[d]);
+        }
+    }
+}
+
+// The posterior sample and its gradient at xi (uniform over the wave), returned to every lane.
+//   scale = sqrt(os / F);  has_row: this lane owns training row xr with update weight vn
+template <int D, bool GRAD>
+__device__ __forceinline__ void pw_eval_point(const double* __restrict__ om, const double* __restrict__ zw, int F, int lane,
+                                              double scale, double os, const double* inv_l2, bool has_row, const double (&xr)[D],
+                                              double vn, const double (&xi)[D], double& val, double (&grad)[D]) {
+    double v, g[D];
+    pw_prior_lane<D, GRAD>(om, zw, F, lane, xi, v, g);
+    v *= scale;
+#pragma unroll
+    for (int d = 0; d < D; ++d) g[d] *= scale;
+    if (has_row) {
+        double q[D];                                                   // r = xi - X_n: the test point is the kernel's first argument
+        const double kv = kern_scalar<D>(xi, xr, inv_l2, os, q) * vn;
+        v += kv;
+        if (GRAD) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) g[d] = fma(-kv, q[d], g[d]);    // derivative row d of the test point: -k q_d
+        }
+    }
+    val = wave_sum(v);
+#pragma unroll
+    for (int d = 0; d < D; ++d) grad[d] = GRAD ? wave_sum(g[d]) : 0.0;
+}
+
+// every entry of a sample's row of n doubles is finite (wave-uniform answer)
+__device__ __forceinline__ bool pw_row_finite(const double* __restrict__ row, long n, int lane) {
+    bool ok = true;
+    for (long e = lane; e < n; e += kWave) ok = ok && pw_finite(row[e]);
+    return __all(ok);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fit
+// ---------------------------------------------------------------------------------------------------------------------
+struct PwFitArgs {
+    GpParams gp;
+    const double *plan, *X_r, *Y_r, *omega, *Z;
+    double* Vout;
+    int* info;
+    long Ns, ldz;
+    int M;
+};
+
+template <int D>
+__global__ __launch_bounds__(256) void pathwise_fit_kernel(const PwFitArgs a) {
+    __shared__ double Li_s[PW_MAX_ROWS * PW_LS];                        // Li_s[j * PW_LS + i] = L^-1[i][j]
+    __shared__ double L_s[PW_MAX_ROWS * PW_LS];                         // L_s[i * PW_LS + k] = L[i][k]
+    __shared__ double a_s[4][PW_MAX_ROWS], b_s[4][PW_MAX_ROWS];         // a wave's two vectors (no other wave touches its row)
+    const GpParams& gp = a.gp;
+    const int n = gp.N_r, F = a.M / 2, stride_o = a.M + n;              // n <= 64 (host)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long sraw = (long)blockIdx.x * 4 + wave;
+    const bool active = sraw < a.Ns;                                    // an idle wave computes sample Ns - 1 again and stores nothing
+    const long s = active ? sraw : a.Ns - 1;
+    const double* zrow = a.Z + s * a.ldz;
+    const double nan = __builtin_nan("");
+    bool dead = !pw_row_finite(zrow, (long)gp.g_ny * stride_o, lane);
+    const bool has_row = lane < n;
+    const int row = has_row ? lane : n - 1;
+    const double sd_noise = sqrt(gp.noise[0]);
+
+    // (K + Sigma)^-1 rhs = L^-T (L^-1 rhs) for this wave's vector, one row per lane, in the order gpmpc_plan_build forms alpha_r
+    auto apply_inverse = [&](double rhs) {
+        a_s[wave][lane] = has_row ? rhs : 0.0;
+        __syncthreads();
+        double w = 0.0;                                                 // w = L^-1 rhs, row `lane`, columns in ascending order
+        for (int j = 0; j < n; ++j) {
+            const double l = Li_s[j * PW_LS + row];
+            if (j <= lane) w = fma(l, a_s[wave][j], w);
+        }
+        b_s[wave][lane] = has_row ? w : 0.0;
+        __syncthreads();
+        double v = 0.0;                                                 // v = L^-T w, row `lane`
+        for (int i = 0; i < n; ++i) {
+            const double l = Li_s[row * PW_LS + i];
+            if (i >= lane) v = fma(l, b_s[wave][i], v);
+        }
+        __syncthreads();                                                // a_s / b_s may be written again
+        return v;
+    };
+
+    for (int o = 0; o < gp.g_ny; ++o) {
+        __syncthreads();                                                // the previous output's triangles have been read
+        const double* L = a.plan + o * gp.plan_stride;
+        const double* LinvT = L + (long)n * n;
+        for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
+            const int j = e / n, i = e - j * n;
+            Li_s[j * PW_LS + i] = LinvT[e];
+            L_s[j * PW_LS + i] = L[e];
+        }
+        const double* om = a.omega + (long)o * F * D;
+        const double* zw = zrow + (long)o * stride_o;
+        const double scale = sqrt(gp.os[o] / (double)F);
+        double g_own = 0.0;                                             // the prior sample at this lane's training row
+#pragma unroll 1
+        for (int p = 0; p < n; ++p) {
+            double xi[D], v, g[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) xi[d] = a.X_r[(long)p * D + d];
+            pw_prior_lane<D, false>(om, zw, F, lane, xi, v, g);
+            const double tot = wave_sum(v * scale);
+            if (lane == p) g_own = tot;
+        }
+        const double y = a.Y_r[((long)o * n + row) * gp.T];
+        const double r = (y - g_own) - sd_noise * zw[a.M + row];
+        double v = apply_inverse(r);                                    // (the barrier inside also covers the staging above)
+        // One step of iterative refinement against the plan's own factor: rho = r - L (L^T v), v += (K + Sigma)^-1 rho.  Applying
+        // the explicit inverse is not backward stable: its residual is ~cond(L) times that of a triangular solve, and the
+        // prediction k(xi, X)^T v sees the residual, not the forward error of v (measured: the value's error 7 x that of Cholesky
+        // solves without this step, level with them after it; a second step changes nothing).
+        a_s[wave][lane] = has_row ? v : 0.0;
+        __syncthreads();
+        double t = 0.0;                                                 // t = L^T v, row `lane`
+        for (int i = 0; i < n; ++i) {
+            const double l = L_s[i * PW_LS + row];
+            if (i >= lane) t = fma(l, a_s[wave][i], t);
+        }
+        b_s[wave][lane] = has_row ? t : 0.0;
+        __syncthreads();
+        double rho = r;                                                 // rho = r - L t
+        for (int k = 0; k < n; ++k) {
+            const double l = L_s[row * PW_LS + k];
+            if (k <= lane) rho = fma(-l, b_s[wave][k], rho);
+        }
+        __syncthreads();
+        v += apply_inverse(rho);
+        if (!__all(!has_row || pw_finite(v))) dead = true;
+        if (active && has_row) a.Vout[(s * gp.g_ny + o) * n + lane] = v;
+    }
+    if (dead && active) {                                               // (wave-uniform) the whole sample is NaN
+        for (int e = lane; e < gp.g_ny * n; e += kWave) a.Vout[s * gp.g_ny * n + e] = nan;
+    }
+    if (active && lane == 0) a.info[s] = dead ? GPMPC_INFO_NONFINITE : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// eval
+// ---------------------------------------------------------------------------------------------------------------------
+struct PwEvalArgs {
+    GpParams gp;
+    const double *X_r, *omega, *x, *Z, *V;
+    double* out;
+    int* info;
+    long Ns, ldz, ss, so, sp;
+    int M, m;
+};
+
+template <int D, bool GRAD>
+__global__ __launch_bounds__(256) void pathwise_eval_kernel(const PwEvalArgs a) {
+    const GpParams& gp = a.gp;
+    const int n = gp.N_r, F = a.M / 2, stride_o = a.M + n;
+    const int lane = threadIdx.x & 63;
+    const long s = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= a.Ns) return;                                              // (no workgroup barrier below)
+    constexpr int W = GRAD ? 1 + D : 1;
+    const double* zrow = a.Z + s * a.ldz;
+    const double nan = __builtin_nan("");
+    const bool dead = !(pw_row_finite(zrow, (long)gp.g_ny * stride_o, lane) && pw_row_finite(a.V + s * gp.g_ny * n, (long)gp.g_ny * n, lane));
+    int info_acc = dead ? GPMPC_INFO_NONFINITE : 0;
+    const bool has_row = lane < n;
+    const int row = has_row ? lane : n - 1;
+    double xr[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) xr[d] = a.X_r[(long)row * D + d];
+
+    for (int o = 0; o < gp.g_ny; ++o) {
+        const double* om = a.omega + (long)o * F * D;
+        const double* zw = zrow + (long)o * stride_o;
+        const double scale = sqrt(gp.os[o] / (double)F), os = gp.os[o];
+        const double vn = a.V[(s * gp.g_ny + o) * n + row];
+#pragma unroll 1
+        for (int p = 0; p < a.m; ++p) {
+            const double* xp = a.x + s * a.ss + o * a.so + p * a.sp;
+            double xi[D], val, grad[D];
+            bool fin = true;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                xi[d] = xp[d];
+                fin = fin && pw_finite(xi[d]);
+            }
+            pw_eval_point<D, GRAD>(om, zw, F, lane, scale, os, gp.inv_l2[o], has_row, xr, vn, xi, val, grad);
+            fin = fin && pw_finite(val);
+            double mine = val;                                          // lane c stores component c
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                if (GRAD) fin = fin && pw_finite(grad[d]);
+                if (GRAD && lane == d + 1) mine = grad[d];
+            }
+            if (!fin) info_acc |= GPMPC_INFO_NONFINITE;
+            if (lane < W) a.out[((s * gp.g_ny + o) * a.m + p) * W + lane] = (dead || !fin) ? nan : mine;
+        }
+    }
+    if (lane == 0) a.info[s] = info_acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rollout
+// ---------------------------------------------------------------------------------------------------------------------
+struct PwRollArgs {
+    GpParams gp;
+    EnvParams env;
+    const double *X_r, *omega, *x0, *U, *Z, *V;
+    double *X_traj, *Y;
+    int* info;
+    long Ns, ldz;
+    int M, H, x0_per, u_per;
+};
+
+template <int ENV>
+__global__ __launch_bounds__(256) void pathwise_rollout_kernel(const PwRollArgs a) {
+    constexpr int NX = (ENV == GPMPC_ENV_PENDULUM1D) ? 2 : 4;
+    constexpr int NU = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 2;
+    constexpr int G_NY = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 3;
+    constexpr int D = 2;
+    const GpParams& gp = a.gp;
+    const int n = gp.N_r, F = a.M / 2, stride_o = a.M + n, H = a.H;
+    const int lane = threadIdx.x & 63;
+    const long s = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= a.Ns) return;                                              // (no workgroup barrier below)
+    const double* zrow = a.Z + s * a.ldz;
+    const double nan = __builtin_nan("");
+    const bool has_row = lane < n;
+    const int row = has_row ? lane : n - 1;
+    const double xr[D] = {a.X_r[(long)row * D], a.X_r[(long)row * D + 1]};
+    double vn[G_NY];
+#pragma unroll
+    for (int o = 0; o < G_NY; ++o) vn[o] = a.V[(s * G_NY + o) * n + row];
+
+    double x[NX];
+    bool dead = !(pw_row_finite(zrow, (long)G_NY * stride_o, lane) && pw_row_finite(a.V + s * G_NY * n, (long)G_NY * n, lane));
+#pragma unroll
+    for (int d = 0; d < NX; ++d) {
+        x[d] = a.x0[(a.x0_per ? s * NX : 0) + d];
+        dead = dead || !pw_finite(x[d]);
+    }
+    int info_acc = dead ? GPMPC_INFO_NONFINITE : 0;
+    if (dead) {
+#pragma unroll
+        for (int d = 0; d < NX; ++d) x[d] = nan;
+    }
+    auto store_state = [&](int t) {                                     // lane d stores state dimension d
+        double mine = x[0];
+#pragma unroll
+        for (int d = 1; d < NX; ++d)
+            if (lane == d) mine = x[d];
+        if (lane < NX) a.X_traj[(s * NX + lane) * (H + 1) + t] = mine;
+    };
+
+#pragma unroll 1
+    for (int t = 0; t < H; ++t) {
+        store_state(t);
+        double u[NU], xi[D], xn[NX];
+        bool fin = true;
+#pragma unroll
+        for (int i = 0; i < NU; ++i) {
+            const double ufi = a.U[((a.u_per ? s * H : 0) + t) * NU + i];
+            if (a.env.use_feedback) {                                   // uniform; written as apply_feedback (gpmpc_device.hpp)
+                double acc = 0.0;
+#pragma unroll
+                for (int j = 0; j < NX; ++j) acc += (a.env.x_goal[j] - x[j]) * a.env.K[i][j];
+                u[i] = -acc + ufi;
+            } else {
+                u[i] = ufi;
+            }
+            fin = fin && pw_finite(u[i]);
+        }
+        xi[0] = (ENV == GPMPC_ENV_PENDULUM1D) ? x[0] : x[2];            // gp_input
+        xi[1] = u[0];
+        double g[G_NY], gg[G_NY][D];
+#pragma unroll
+        for (int o = 0; o < G_NY; ++o) {
+            pw_eval_point<D, true>(a.omega + (long)o * F * D, zrow + (long)o * stride_o, F, lane, sqrt(gp.os[o] / (double)F), gp.os[o],
+                                   gp.inv_l2[o], has_row, xr, vn[o], xi, g[o], gg[o]);
+            fin = fin && pw_finite(g[o]) && pw_finite(gg[o][0]) && pw_finite(gg[o][1]);
+        }
+        if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {                    // env_step (gpmpc_device.hpp)
+            xn[0] = x[0] + x[1] * a.env.dt;
+            xn[1] = x[1] + g[0];
+        } else {
+            const double v = x[3];
+            xn[0] = x[0] + v * g[0];
+            xn[1] = x[1] + v * g[1];
+            xn[2] = x[2] + v * g[2];
+            xn[3] = (x[3] + u[1] * a.env.dt);
+        }
+#pragma unroll
+        for (int d = 0; d < NX; ++d) fin = fin && pw_finite(xn[d]);
+        if (!dead && !fin) {
+            dead = true;
+            info_acc |= GPMPC_INFO_NONFINITE;
+        }
+        if (a.Y) {                                                      // lane c stores component c of every output
+#pragma unroll
+            for (int o = 0; o < G_NY; ++o) {
+                const double mine = (lane == 0) ? g[o] : (lane == 1) ? gg[o][0] : gg[o][1];
+                if (lane < 1 + D) a.Y[((s * G_NY + o) * H + t) * (1 + D) + lane] = dead ? nan : mine;
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < NX; ++d) x[d] = dead ? nan : xn[d];
+    }
+    store_state(H);
+    if (lane == 0) a.info[s] = info_acc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------------
+// the checks the three entry points share; `me` names the entry point in the message
+static int pw_check(const std::string& me, const gpmpc_gp_desc_t* gp, int32_t M, int64_t Ns, int64_t ldz) {
+    if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
+    if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    if (Ns < 0) return fail(GPMPC_E_ARG, me + "Ns must be >= 0");
+    if (M < 2 || (M & 1)) return fail(GPMPC_E_ARG, me + "M must be an even number of features >= 2");
+    if (ldz < (int64_t)gp->g_ny * ((int64_t)M + gp->N_r))
+        return fail(GPMPC_E_ARG, me + "ldz must be >= g_ny * (M + N_r)");
+    return GPMPC_OK;
+}
+
+static int pw_supported(const std::string& me, const gpmpc_gp_desc_t* gp, int32_t M, int64_t Ns) {
+    if (gp->real_has_grad) return fail(GPMPC_E_UNSUPPORTED, me + "real_has_grad = 1 is not instantiated (value-only real data)");
+    if (gp->N_r > PW_MAX_ROWS) return fail(GPMPC_E_UNSUPPORTED, me + "more than 64 training rows (N_r) are not instantiated");
+    if (M % PW_M_STEP != 0 || M > PW_MAX_M) return fail(GPMPC_E_UNSUPPORTED, me + "M must be a multiple of 128 and at most 1024");
+    if (Ns > (int64_t)INT_MAX) return fail(GPMPC_E_UNSUPPORTED, me + "Ns must be < 2^31 (split the samples over calls)");
+    return GPMPC_OK;
+}
+
+}  // namespace gpmpc
+
+using namespace gpmpc;
+
+extern "C" {
+
+int gpmpc_pathwise_fit(const gpmpc_gp_desc_t* gp, const void* plan, const double* X_r, const double* Y_r, int32_t M,
+                       const double* omega, int64_t Ns, const double* Z, int64_t ldz, double* Vout, int32_t* info, void* stream) {
+    const std::string me = "gpmpc_pathwise_fit: ";
+    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
+    // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
+    if (Ns > 0 && (!plan || !X_r || !Y_r || !omega || !Z || !Vout || !info))
+        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, Y_r, omega, Z, Vout and info are required)");
+    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (Ns == 0) return GPMPC_OK;
+    PwFitArgs a;
+    a.gp = make_gp_params(gp);
+    a.plan = (const double*)plan, a.X_r = X_r, a.Y_r = Y_r, a.omega = omega, a.Z = Z;
+    a.Vout = Vout, a.info = (int*)info, a.Ns = Ns, a.ldz = ldz, a.M = M;
+    const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    switch (gp->D) {
+        case 1: hipLaunchKernelGGL(pathwise_fit_kernel<1>, grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL(pathwise_fit_kernel<2>, grid, block, 0, st, a); break;
+        case 3: hipLaunchKernelGGL(pathwise_fit_kernel<3>, grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL(pathwise_fit_kernel<4>, grid, block, 0, st, a); break;
+    }
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
+int gpmpc_pathwise_eval(const gpmpc_gp_desc_t* gp, const double* X_r, int32_t M, const double* omega, int64_t Ns, int32_t m,
+                        const double* x, int64_t stride_sample, int64_t stride_output, int64_t stride_point, const double* Z,
+                        int64_t ldz, const double* V, int32_t want_grad, double* out, int32_t* info, void* stream) {
+    const std::string me = "gpmpc_pathwise_eval: ";
+    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
+    if (m < 0) return fail(GPMPC_E_ARG, me + "m must be >= 0");
+    if (stride_sample < 0 || stride_output < 0 || stride_point < 0) return fail(GPMPC_E_ARG, me + "strides must be >= 0");
+    if (Ns > 0 && m > 0 && (!X_r || !omega || !x || !Z || !V || !out || !info))
+        return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x, Z, V, out and info are required)");
+    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (Ns == 0 || m == 0) return GPMPC_OK;
+    PwEvalArgs a;
+    a.gp = make_gp_params(gp);
+    a.X_r = X_r, a.omega = omega, a.x = x, a.Z = Z, a.V = V, a.out = out, a.info = (int*)info;
+    a.Ns = Ns, a.ldz = ldz, a.ss = stride_sample, a.so = stride_output, a.sp = stride_point, a.M = M, a.m = m;
+    const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+#define GPMPC_PW_EVAL(DD)                                                                         \
+    if (want_grad) hipLaunchKernelGGL((pathwise_eval_kernel<DD, true>), grid, block, 0, st, a);   \
+    else hipLaunchKernelGGL((pathwise_eval_kernel<DD, false>), grid, block, 0, st, a)
+    switch (gp->D) {
+        case 1: GPMPC_PW_EVAL(1); break;
+        case 2: GPMPC_PW_EVAL(2); break;
+        case 3: GPMPC_PW_EVAL(3); break;
+        default: GPMPC_PW_EVAL(4); break;
+    }
+#undef GPMPC_PW_EVAL
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
+int gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M, const double* omega,
+                           int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample, const double* U, int32_t u_per_sample,
+                           const double* Z, int64_t ldz, const double* V, double* X_traj, double* Y, int32_t* info, void* stream) {
+    const std::string me = "gpmpc_pathwise_rollout: ";
+    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
+    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
+    if (H < 0) return fail(GPMPC_E_ARG, me + "H must be >= 0");
+    if (Ns > 0 && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && !U)))
+        return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj and info are required)");
+    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
+    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (Ns == 0) return GPMPC_OK;
+    PwRollArgs a;
+    a.gp = make_gp_params(gp);
+    a.env = make_env_params(env);
+    a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.X_traj = X_traj, a.Y = Y, a.info = (int*)info;
+    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per_sample != 0, a.u_per = u_per_sample != 0;
+    const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
+    if (env->env_id == GPMPC_ENV_PENDULUM1D)
+        hipLaunchKernelGGL(pathwise_rollout_kernel<GPMPC_ENV_PENDULUM1D>, grid, block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(pathwise_rollout_kernel<GPMPC_ENV_CAR_RESIDUAL>, grid, block, 0, (hipStream_t)stream, a);
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
+}  // extern "C"

@@ -226,6 +226,14 @@ def make_sharded_agent(agent_cls, params, env_model, group=None, pin_joint_path=
     return agent
 
 
+def sharded_pathwise_samples(agent, n_features: int, seed: int):
+    """This rank's shard of the pathwise samples of a sharded ``agent`` (``make_sharded_agent``): every rank draws the SAME frequencies
+    (``seed``) and the rows ``agent.shard[0] ..`` of the same normal stream, so sample ``s`` is the same function for every world size."""
+    from .pathwise import PathwiseSamples
+    lo = agent.shard[0] if agent.shard else 0
+    return PathwiseSamples.draw(agent, agent.ns, n_features, seed, offset=lo)
+
+
 def filtered_in_all_samples(filt_local: torch.Tensor, group=None) -> torch.Tensor:
     """``filt_local`` (Ns_local, g_ny, m) bool: point filtered for that sample/output.  Returns the (g_ny, m) bool mask
     "filtered in ALL samples" over the GLOBAL sample set (reference ``src/agent.py:186``: ``torch.all(filt, dim=0)``)."""

@@ -1,0 +1,222 @@
+"""Pathwise (weight-space) samples of the real-data GP posterior: fit once, then evaluate or roll out at constant cost.
+
+Every other sampling path of this package makes a dynamics sample behave like ONE function by re-conditioning it on its own earlier
+draws (a factor that grows with the step, the SQP iteration and the MPC step).  Pathwise conditioning - Matheron's update of a
+finite-feature prior sample - fixes the function once per sample instead: a weight vector over ``M`` random Fourier features of the
+RBF kernel plus a correction vector over the real training points (include/gpmpc_hip.h, ``gpmpc_pathwise_*``, has the formulas).
+The reference's ``extra/approx_sampling_mpc/src/agent.py:793-870,938-977`` samples weights once (``sample_weights``) and evaluates
+value and gradients as feature sums (``get_dynamics_grad``); this is the GP form of that scheme.
+
+``PathwiseSamples.draw`` draws the frequencies on the CPU, the normals with ``gpmpc_base_samples`` (one row per GLOBAL sample id) and
+calls ``gpmpc_pathwise_fit``; ``.evaluate`` / ``.rollout`` are one launch each.  ``rff_kernel_error`` checks a frequency draw.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from . import _lib
+
+F64 = torch.float64
+M_STEP, MAX_M, MAX_ROWS = 128, 1024, 64          # include/gpmpc_hip.h, gpmpc_pathwise_*: the limits
+
+
+def draw_omega(ell, n_features: int, seed: int) -> torch.Tensor:
+    """The frequencies ``omega (g_ny, F, D)``, ``F = n_features / 2``: ``z / ell[o][d]`` with ``z ~ N(0, 1)`` from a seeded CPU generator
+    (the spectral density of the RBF kernel with lengthscales ``ell (g_ny, D)``).  A CPU tensor: the same numbers on every machine."""
+    if n_features < 2 or n_features % 2:
+        raise ValueError("n_features must be an even number >= 2")
+    ell = torch.as_tensor(ell, dtype=F64)
+    g = torch.Generator().manual_seed(int(seed))
+    z = torch.randn(ell.shape[0], n_features // 2, ell.shape[1], dtype=F64, generator=g)
+    return z / ell[:, None, :]
+
+
+def rff_kernel_error(omega: torch.Tensor, hyper, X: torch.Tensor) -> float:
+    """``max |Phi Phi^T - K| / outputscale`` over the point set ``X (n, D)`` and the outputs: how well the drawn frequencies reproduce
+    the RBF kernel of ``hyper`` (``ell (g_ny, D)``, ``outputscale (g_ny)``).  Each entry of ``Phi Phi^T / outputscale`` is the mean of
+    ``F`` cosines, so its standard deviation is at most ``1 / sqrt(F)``.  Plain torch on whatever device ``omega`` lives on."""
+    omega = torch.as_tensor(omega, dtype=F64)
+    X = torch.as_tensor(X, dtype=F64).to(omega.device)
+    ell = torch.as_tensor(hyper.ell, dtype=F64).to(omega.device)
+    worst = 0.0
+    for o in range(omega.shape[0]):
+        d = X[:, None, :] - X[None, :, :]                                          # (n, n, D)
+        approx = torch.cos(d @ omega[o].T).mean(-1)                                # Phi Phi^T / outputscale
+        exact = torch.exp(-0.5 * ((d / ell[o]) ** 2).sum(-1))
+        worst = max(worst, float((approx - exact).abs().max()))
+    return worst
+
+
+def _plan_of(agent_or_plan):
+    """(plan, env_desc or None): an Agent gives the plan of its sampling model and its environment descriptor."""
+    if hasattr(agent_or_plan, "_plan") and hasattr(agent_or_plan, "env_desc"):
+        agent = agent_or_plan
+        _lib.require_hip_device(agent.torch_device)
+        return agent._plan(use_grad=(agent.in_dim_y != 1)), agent
+    _lib.require_hip_device(agent_or_plan.X_r.device)
+    return agent_or_plan, None
+
+
+class PathwiseSamples:
+    """``Ns`` pathwise posterior samples of a ``RealDataPlan``'s GP as device tensors: ``omega (g_ny, F, D)``, ``Z (Ns, V)`` (the
+    normals, ``V = g_ny (M + N_r)``) and ``V (Ns, g_ny, N_r)`` (the update vectors); ``info (Ns)`` int32 of the fit."""
+
+    def __init__(self, plan, agent, omega, Z, V, info, n_features, seed=None, offset=0):
+        self.plan, self.agent = plan, agent
+        self.omega, self.Z, self.V, self.info = omega, Z, V, info
+        self.n_features, self.seed, self.offset = int(n_features), seed, int(offset)
+        self.last_info = None
+        self._mean = None
+
+    @property
+    def Ns(self) -> int:
+        return int(self.Z.shape[0])
+
+    @staticmethod
+    def _fit(plan, agent, omega, Z, n_features, seed, offset) -> "PathwiseSamples":
+        lib = _lib.load()
+        dev = plan.X_r.device
+        Ns, d = int(Z.shape[0]), plan.desc
+        V = torch.empty(Ns, d.g_ny, d.N_r, dtype=F64, device=dev)
+        info = torch.zeros(Ns, dtype=torch.int32, device=dev)
+        if not Z.is_cuda:
+            raise _lib.GpmpcError("tensor passed to libgpmpc_hip.so is not on a HIP device")
+        ldz = int(Z.stride(0)) if Ns > 1 else int(Z.shape[1])                 # rows of a wider array are read in place
+        _lib.check(lib.gpmpc_pathwise_fit(d, _lib.dptr(plan.buf), _lib.dptr(plan.X_r), _lib.dptr(plan.Y_r), int(n_features),
+                                          _lib.dptr(omega), Ns, Z.data_ptr(), ldz, _lib.dptr(V),
+                                          _lib.dptr(info), _lib.current_stream_ptr()), "gpmpc_pathwise_fit")
+        return PathwiseSamples(plan, agent, omega, Z, V, info, n_features, seed, offset)
+
+    @staticmethod
+    def draw(agent_or_plan, Ns: int, n_features: int, seed: int, offset: int = 0, omega: Optional[torch.Tensor] = None) -> "PathwiseSamples":
+        """``Ns`` samples with ``n_features`` (a multiple of 128, at most 1024) random Fourier features.  The frequencies come from
+        ``draw_omega(ell, n_features, seed)`` unless given; row ``s`` of the normals is vector ``offset + s`` of the counter stream of
+        ``gpmpc_base_samples(seed, ...)``: a sample is a function of ``(seed, global id)`` alone, whatever ``Ns`` and however a run is
+        cut into calls or ranks.  No host synchronisation after the plan exists."""
+        plan, agent = _plan_of(agent_or_plan)
+        lib = _lib.load()
+        dev = plan.X_r.device
+        d = plan.desc
+        if omega is None:
+            omega = draw_omega(plan.hyper.ell, n_features, seed)
+        omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
+        if tuple(omega.shape) != (d.g_ny, n_features // 2, d.D):
+            raise _lib.GpmpcError(f"omega must be ({d.g_ny}, {n_features // 2}, {d.D})")
+        Vn = d.g_ny * (int(n_features) + d.N_r)
+        Z = torch.empty(int(Ns), Vn, dtype=F64, device=dev)
+        if Ns > 0:
+            with torch.cuda.device(dev):
+                _lib.check(lib.gpmpc_base_samples(int(seed) & ((1 << 64) - 1), 1, 1, int(offset), int(Ns), Vn, float("inf"), _lib.dptr(Z), None,
+                                                  _lib.current_stream_ptr()), "gpmpc_base_samples")
+        return PathwiseSamples._fit(plan, agent, omega, Z, n_features, seed, offset)
+
+    @staticmethod
+    def from_normals(agent_or_plan, omega: torch.Tensor, Z: torch.Tensor) -> "PathwiseSamples":
+        """The samples of given frequencies and normals ``Z (Ns, >= V)`` (a view with a row stride is read in place)."""
+        plan, agent = _plan_of(agent_or_plan)
+        dev = plan.X_r.device
+        omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
+        Z = torch.as_tensor(Z, dtype=F64).to(dev)
+        if Z.dim() != 2 or (Z.shape[0] > 1 and Z.stride(1) != 1):
+            raise _lib.GpmpcError("Z must be (Ns, V) with contiguous rows")
+        d = plan.desc
+        n_features = 2 * int(omega.shape[1])
+        if Z.shape[1] != d.g_ny * (n_features + d.N_r):
+            raise _lib.GpmpcError(f"Z must have V = g_ny (M + N_r) = {d.g_ny * (n_features + d.N_r)} columns")
+        return PathwiseSamples._fit(plan, agent, omega, Z, n_features, None, 0)
+
+    def mean_only(self) -> "PathwiseSamples":
+        """The ``Z = 0`` sample of the same frequencies: its update vector is the plan's ``alpha_r`` and the function the posterior mean."""
+        if self._mean is None:
+            Z = torch.zeros(1, self.Z.shape[1], dtype=F64, device=self.Z.device)
+            self._mean = PathwiseSamples._fit(self.plan, self.agent, self.omega, Z, self.n_features, None, 0)
+        return self._mean
+
+    def _ldz(self) -> int:
+        return int(self.Z.stride(0)) if self.Ns > 1 else int(self.Z.shape[1])
+
+    def evaluate(self, x_input: torch.Tensor, want_grad: bool = True) -> torch.Tensor:
+        """Value (and gradient) of every sample: ``x_input (Ns, g_ny, m, D)`` as ``Agent.sample_gp`` takes it - read in place through its
+        strides, an expanded view costs nothing - or a shared ``(m, D)`` point set.  Returns ``(Ns, g_ny, m, 1 + D)``, or ``(..., 1)``
+        without ``want_grad``: the layout of ``Agent.sample_gp``.  ``self.last_info (Ns)`` int32 carries ``INFO_NONFINITE``."""
+        lib = _lib.load()
+        dev = _lib.require_hip_device(self.Z.device)
+        d = self.plan.desc
+        x = torch.as_tensor(x_input, dtype=F64).to(dev)
+        if x.dim() == 2 and x.shape[1] == d.D:
+            x = x.contiguous()
+            m, strides = int(x.shape[0]), (0, 0, d.D)
+        elif x.dim() == 4 and tuple(x.shape[:2]) == (self.Ns, d.g_ny) and x.shape[3] == d.D:
+            if x.stride(3) != 1 or min(x.stride()) < 0:
+                x = x.contiguous()
+            m, strides = int(x.shape[2]), tuple(int(s) for s in x.stride()[:3])
+        else:
+            raise _lib.GpmpcError(f"x_input must be ({self.Ns}, {d.g_ny}, m, {d.D}) or (m, {d.D})")
+        W = 1 + d.D if want_grad else 1
+        out = torch.empty(self.Ns, d.g_ny, m, W, dtype=F64, device=dev)
+        info = torch.zeros(self.Ns, dtype=torch.int32, device=dev)
+        _lib.check(lib.gpmpc_pathwise_eval(d, _lib.dptr(self.plan.X_r), self.n_features, _lib.dptr(self.omega), self.Ns, m, x.data_ptr(),
+                                           strides[0], strides[1], strides[2], self.Z.data_ptr(), self._ldz(), _lib.dptr(self.V),
+                                           int(bool(want_grad)), _lib.dptr(out), _lib.dptr(info), _lib.current_stream_ptr()),
+                   "gpmpc_pathwise_eval")
+        self.last_info = info
+        return out
+
+    def rollout(self, x0, U, use_feedback: Optional[bool] = None, want_samples: bool = False, env_desc=None):
+        """The tube ``X_traj (Ns, nx, H+1)`` of the samples in one launch (``gpmpc_pathwise_rollout``): ``x0 (nx,)`` or ``(Ns, nx)``,
+        ``U (H, nu)`` or ``(Ns, H, nu)``; environment step and feedback law as ``gpmpc_rollout`` (the descriptor comes from the Agent the
+        samples were drawn for; ``use_feedback`` None: ``agent.feedback.use``).  ``want_samples``: also ``Y (Ns, g_ny, H, 1 + D)``, the
+        sample's value and gradient at every visited point - returned as ``(X_traj, Y)``.  ``self.last_info`` as for ``evaluate``."""
+        lib = _lib.load()
+        dev = _lib.require_hip_device(self.Z.device)
+        if env_desc is None:
+            if self.agent is None:
+                raise _lib.GpmpcError("rollout needs an environment: draw the samples for an Agent or pass env_desc")
+            env_desc = self.agent.env_desc(use_feedback)
+        d = self.plan.desc
+        nx, nu = int(env_desc.nx), int(env_desc.nu)
+        x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
+        U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
+        if x0.dim() not in (1, 2) or x0.shape[-1] != nx or (x0.dim() == 2 and x0.shape[0] != self.Ns):
+            raise _lib.GpmpcError(f"x0 must be ({nx},) or ({self.Ns}, {nx})")
+        if U.dim() not in (2, 3) or U.shape[-1] != nu or (U.dim() == 3 and U.shape[0] != self.Ns):
+            raise _lib.GpmpcError(f"U must be (H, {nu}) or ({self.Ns}, H, {nu})")
+        H = int(U.shape[-2])
+        X = torch.empty(self.Ns, nx, H + 1, dtype=F64, device=dev)
+        Y = torch.empty(self.Ns, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
+        info = torch.zeros(self.Ns, dtype=torch.int32, device=dev)
+        _lib.check(lib.gpmpc_pathwise_rollout(d, env_desc, _lib.dptr(self.plan.X_r), self.n_features, _lib.dptr(self.omega), self.Ns, H,
+                                              _lib.dptr(x0), int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), self.Z.data_ptr(),
+                                              self._ldz(), _lib.dptr(self.V), _lib.dptr(X), _lib.dptr(Y), _lib.dptr(info),
+                                              _lib.current_stream_ptr()), "gpmpc_pathwise_rollout")
+        self.last_info = info
+        return (X, Y) if want_samples else X
+
+
+def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
+    """The arithmetic of ``evaluate`` (value and gradient at a shared ``(m, D)`` point set) in plain torch operations on the samples'
+    device: the comparison ``tools/bench_pathwise.py`` times, and a cross-check.  ``(Ns, g_ny, m, 1 + D)``."""
+    plan, d = samples.plan, samples.plan.desc
+    M, n, F = samples.n_features, d.N_r, samples.n_features // 2
+    Z = samples.Z.reshape(samples.Ns, d.g_ny, M + n)
+    ell = torch.as_tensor(plan.hyper.ell, dtype=F64, device=x.device)
+    osc = torch.as_tensor(plan.hyper.outputscale, dtype=F64, device=x.device)
+    outs = []
+    for o in range(d.g_ny):
+        ang = x @ samples.omega[o].T                                                # (m, F)
+        wc, ws = Z[:, o, 0:M:2], Z[:, o, 1:M:2]                                     # (Ns, F)
+        sc = math.sqrt(float(osc[o]) / F)
+        val = sc * (wc @ torch.cos(ang).T + ws @ torch.sin(ang).T)                 # (Ns, m)
+        t = ws[:, None, :] * torch.cos(ang)[None] - wc[:, None, :] * torch.sin(ang)[None]   # (Ns, m, F)
+        grad = sc * (t @ samples.omega[o])                                         # (Ns, m, D)
+        r = x[:, None, :] - plan.X_r[None, :, :]                                    # (m, n, D)
+        q = r / (ell[o] * ell[o])
+        k = osc[o] * torch.exp(-0.5 * (r * q).sum(-1))                              # (m, n)
+        v = samples.V[:, o, :]                                                      # (Ns, n)
+        val = val + v @ k.T
+        grad = grad - torch.einsum("sn,mn,mnd->smd", v, k, q)
+        outs.append(torch.cat([val[..., None], grad], dim=-1))
+    return torch.stack(outs, dim=1)
