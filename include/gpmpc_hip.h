@@ -646,6 +646,44 @@ int     gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
                              double* A /* (B, H, nx, nx) or NULL */, int32_t* info /* (B) */, void* stream);
 
 /*
+ * gpmpc_moment_rollout_vjp - the reverse-mode derivative (vector-Jacobian product) of the map (x0, U, P0) -> (M, P) that
+ * gpmpc_moment_rollout computes, exactly as that kernel defines it: the variance floor, the feedback path, "P is written mirrored
+ * from its lower triangle" and "of P0 the lower triangle is read" included.  One candidate per lane, one backward sweep t = H-1..0
+ * that reads mu_t and P_t from the forward's M and P (the forward is not run again).  An additive entry point: the ABI version
+ * stays 12.
+ * Replaces: reference extra/zoro_code.py:52-128 (gp_sensitivities_with_prop: three nested torch.autograd.functional.jacobian calls
+ * per step on the host, one nominal trajectory at a time); here the sensitivities of B candidates against any cotangent are one
+ * launch.  Differentiating P+ = A P A^T + G diag(s) G^T needs the Hessian of the posterior mean (A holds its gradient: with
+ * derivative labels third derivatives of the RBF kernel) and the gradient of the posterior variance, -2 (K^-1 k)^T dk / dxi.
+ *   x0, x0_per_candidate, U, u_per_candidate   the forward's inputs (x0 is only checked for non-finite entries: mu_0 is M[:, :, 0])
+ *   M    [dev] (B, nx, H+1), P [dev] (B, H+1, nx, nx)   the forward's outputs, read
+ *   gM   [dev] (B, nx, H+1) or NULL     cotangent of M; NULL is zero
+ *   gP   [dev] (B, H+1, nx, nx) or NULL cotangent of P; NULL is zero.  It need not be symmetric: P[j][i] is a copy of P[i][j], so
+ *                                       the kernel works with (gP + gP^T) / 2
+ *   gx0  [dev] (B, nx) or NULL          out: d / d x0
+ *   gU   [dev] (B, H, nu)               out: d / d U (the feed-forward input)      (may be NULL when H == 0)
+ *   gP0  [dev] (B, nx, nx) or NULL      out: d / d P0 with the whole gradient on the lower triangle (diagonal included: the entry
+ *                                       (i, j), j < i, carries both mirrored copies) and exact zeros above it
+ *   info [dev] (B) int32                out: GPMPC_INFO_VAR_CLAMPED, GPMPC_INFO_NONFINITE
+ * Gradients are always per candidate, also when x0 / U are shared (*_per_candidate == 0): the host sums over B for a shared
+ * input, the kernel needs no cross-lane reduction and no atomics.
+ * Variance floor: where the raw variance is below var_floor its gradient is zero (what clamp_min gives); the floor value itself
+ * still meets d G / d x.  info carries GPMPC_INFO_VAR_CLAMPED as the forward does.
+ * Non-finite values: a candidate whose x0, U, M, P, gM or gP hold a non-finite value, or for which one is computed, has NaN in all
+ * its gradients and GPMPC_INFO_NONFINITE; no other candidate is touched.
+ * Reproducibility: a candidate's gradient bits do not depend on B or on its place in the batch.
+ * Limits and errors are those of gpmpc_moment_rollout: D = 2, both environments, any X_r, at most 64 label rows, B < 2^31;
+ * GPMPC_E_ARG / GPMPC_E_UNSUPPORTED before any device work (required with B > 0: plan, X_r, x0, M, P, info, and U and gU when
+ * H > 0).  B == 0: nothing is launched and the array pointers are not looked at.  H == 0: gx0 = gM[:, :, 0] and gP0 from gP[:, 0].
+ */
+int     gpmpc_moment_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                 int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                                 int32_t u_per_candidate, const double* M /* (B, nx, H+1) */, const double* P /* (B, H+1, nx, nx) */,
+                                 const double* gM /* (B, nx, H+1) or NULL */, const double* gP /* (B, H+1, nx, nx) or NULL */,
+                                 double* gx0 /* (B, nx) or NULL */, double* gU /* (B, H, nu) */,
+                                 double* gP0 /* (B, nx, nx) or NULL */, int32_t* info /* (B) */, void* stream);
+
+/*
  * gpmpc_tube_gram / gpmpc_tube_apply - the two device pieces of the condensed tube QP, the QP step of the
  * sampled-dynamics OCP.  Additive entry points: the ABI version stays 12.
  * Replaces: what reference src/utils/ocp.py / src/utils/model.py:6-95 hand to acados (FULL_CONDENSING_HPIPM): Ns affine models per

@@ -12,7 +12,8 @@ from .small_ball import (SmallBall, reference_grid, posterior_on_grid, sup_devia
                          sup_deviation_quantile, required_samples)
 from .mle import (MarginalLikelihood, FitResult, marginal_likelihood, pack_theta, unpack_theta, theta_from_params,  # noqa: F401
                   theta_to_params, fit_hyperparameters, restarts, rkhs_norm_and_beta)
-from .moments import MomentTube, moment_rollout, moment_rollout_plan    # noqa: F401
+from .moments import (MomentTube, chance_constraint_penalty, moment_rollout, moment_rollout_plan, moment_rollout_vjp,    # noqa: F401
+                      moment_rollout_vjp_plan, plan_inputs, plan_inputs_plan)
 from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, solve_tube_qp  # noqa: F401
 # the wrapper tube_rows.tube_rows is not re-exported: the name is the module's
 from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
@@ -24,6 +25,7 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "HullQuery", "hull_query", "tube_coverage", "SmallBall", "reference_grid", "posterior_on_grid", "sup_deviation",
            "small_ball_probability", "sup_deviation_quantile", "required_samples", "MarginalLikelihood", "FitResult",
            "marginal_likelihood", "pack_theta", "unpack_theta", "theta_from_params", "theta_to_params", "fit_hyperparameters",
-           "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "TubeQP", "TubeQPResult",
+           "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "moment_rollout_vjp", "moment_rollout_vjp_plan",
+           "chance_constraint_penalty", "plan_inputs", "plan_inputs_plan", "TubeQP", "TubeQPResult",
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
            "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error"]

@@ -105,6 +105,8 @@ SYMBOLS = {
     "gpmpc_marginal_likelihood": (C.c_int, [C.POINTER(GpDesc), _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_moment_rollout": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _I64, _I32, _P, _I32, _P, _I32, _P,
                                        _P, _P, _P, _P, _P, _P]),
+    "gpmpc_moment_rollout_vjp": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _I64, _I32, _P, _I32, _P, _I32, _P,
+                                           _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_tube_gram_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32]),
     "gpmpc_tube_gram": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gpmpc_tube_apply": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),

@@ -241,6 +241,26 @@ __device__ __forceinline__ double kern_entry(const double (&q)[D], double k, con
     return k * v;
 }
 
+// Second derivative of the row kern_entry(0, b) of a test point x against label task b, in the test point's coordinates d, e
+// (0-based): d^2 cov(f(x), task_b(x')) / dx_d dx_e.  With q and k as above:
+//   b = 0:       k (q_d q_e - delta_de / l_d^2)
+//   b = c + 1:   k (q_d q_e q_c - delta_dc q_e / l_c^2 - delta_de q_c / l_d^2 - delta_ec q_d / l_c^2)   (a third derivative of k)
+// Its sum against alpha is the Hessian of the posterior mean (moments_grad.hip); kern_entry(d + 1, b) is the first derivative.
+template <int D>
+__host__ __device__ __forceinline__ double kern_entry_hess(const double (&q)[D], double k, const double* inv_l2, int d, int e, int b) {
+    double v = q[d] * q[e];
+    if (b == 0) {
+        if (d == e) v -= inv_l2[d];
+        return k * v;
+    }
+    const int c = b - 1;
+    v *= q[c];
+    if (d == c) v -= inv_l2[c] * q[e];
+    if (d == e) v -= inv_l2[d] * q[c];
+    if (e == c) v -= inv_l2[c] * q[d];
+    return k * v;
+}
+
 // q[d] = r_d / l_d^2 and the scaled squared distance sum_d r_d q_d (kern_scalar without the exponential)
 template <int D>
 __device__ __forceinline__ double kern_sqdist(const double* x, const double* xp, const double* inv_l2, double (&q)[D]) {

@@ -104,14 +104,10 @@ class MomentTube:
         return torch.where(torch.isnan(m2).any(0), torch.full_like(frac, float("nan")), frac)
 
 
-def moment_rollout_plan(plan, env_desc, x0: torch.Tensor, U: torch.Tensor, P0: Optional[torch.Tensor] = None,
-                        want_var: bool = False, want_jac: bool = False) -> MomentTube:
-    """``gpmpc_moment_rollout`` for a ``RealDataPlan`` and an environment descriptor (``moment_rollout`` takes both from an
-    ``Agent``).  ``x0 (nx,)`` or ``(B, nx)``, ``U (H, nu)`` or ``(B, H, nu)``, ``P0 (B, nx, nx)`` or None; ``B`` is taken from
-    whichever argument carries it (1 if none does).  No host synchronisation."""
-    lib = _lib.load()
+def _prepare(plan, env_desc, x0, U, P0):
+    """The argument handling of ``moment_rollout_plan``: -> (device, x0, U, P0, B, H) with float64 contiguous device tensors."""
     dev = _lib.require_hip_device(plan.X_r.device)
-    nx, nu, g_ny = int(env_desc.nx), int(env_desc.nu), int(plan.desc.g_ny)
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
     x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
     U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
     if x0.dim() not in (1, 2) or x0.shape[-1] != nx:
@@ -128,6 +124,12 @@ def moment_rollout_plan(plan, env_desc, x0: torch.Tensor, U: torch.Tensor, P0: O
     if len(sizes) > 1:
         raise _lib.GpmpcError(f"x0, U and P0 disagree on the number of candidates: {sorted(sizes)}")
     B = sizes.pop() if sizes else 1
+    return dev, x0, U, P0, B, H
+
+
+def _forward(plan, env_desc, dev, x0, U, P0, B, H, want_var, want_jac) -> MomentTube:
+    lib = _lib.load()
+    nx, g_ny = int(env_desc.nx), int(plan.desc.g_ny)
     out = MomentTube(mean=torch.empty(B, nx, H + 1, dtype=F64, device=dev), cov=torch.empty(B, H + 1, nx, nx, dtype=F64, device=dev),
                      info=torch.zeros(B, dtype=torch.int32, device=dev),
                      var=torch.empty(B, H, g_ny, dtype=F64, device=dev) if want_var else None,
@@ -139,12 +141,182 @@ def moment_rollout_plan(plan, env_desc, x0: torch.Tensor, U: torch.Tensor, P0: O
     return out
 
 
+def _backward(plan, env_desc, dev, x0, U, P0, B, H, mean, cov, g_mean, g_cov):
+    """One launch of ``gpmpc_moment_rollout_vjp``: per-candidate gradients ``(g_x0 (B, nx), g_U (B, H, nu), g_P0 (B, nx, nx) or None,
+    info (B))``."""
+    lib = _lib.load()
+    dev = x0.device                                                   # with its index, as the tube's tensors carry it
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
+    for name, t, shape in (("tube.mean", mean, (B, nx, H + 1)), ("tube.cov", cov, (B, H + 1, nx, nx)),
+                           ("g_mean", g_mean, (B, nx, H + 1)), ("g_cov", g_cov, (B, H + 1, nx, nx))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
+            raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
+    mean, cov = mean.detach().contiguous(), cov.detach().contiguous()
+    g_mean = None if g_mean is None else g_mean.detach().contiguous()
+    g_cov = None if g_cov is None else g_cov.detach().contiguous()
+    g_x0 = torch.empty(B, nx, dtype=F64, device=dev)
+    g_U = torch.empty(B, H, nu, dtype=F64, device=dev)
+    g_P0 = None if P0 is None else torch.empty(B, nx, nx, dtype=F64, device=dev)
+    info = torch.zeros(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.gpmpc_moment_rollout_vjp(plan.desc, env_desc, _lib.dptr(plan.buf), _lib.dptr(plan.X_r), B, H, _lib.dptr(x0),
+                                            int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), _lib.dptr(mean), _lib.dptr(cov),
+                                            _lib.dptr(g_mean), _lib.dptr(g_cov), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(g_P0),
+                                            _lib.dptr(info), _lib.current_stream_ptr()), "gpmpc_moment_rollout_vjp")
+    return g_x0, g_U, g_P0, info
+
+
+class _MomentRollout(torch.autograd.Function):
+    """``gpmpc_moment_rollout`` with ``gpmpc_moment_rollout_vjp`` as its backward; ``var``, ``jac`` and ``info`` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, U, P0, plan, env_desc, B, H, want_var, want_jac):
+        dev = x0.device
+        out = _forward(plan, env_desc, dev, x0, U, P0, B, H, want_var, want_jac)
+        ctx.plan, ctx.env_desc, ctx.sizes, ctx.has_p0 = plan, env_desc, (B, H), P0 is not None
+        ctx.save_for_backward(x0, U, out.mean, out.cov, *(() if P0 is None else (P0,)))
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (out.info, out.var, out.jac) if t is not None))
+        return out.mean, out.cov, out.info, out.var, out.jac
+
+    @staticmethod
+    def backward(ctx, g_mean, g_cov, *_):
+        x0, U, mean, cov = ctx.saved_tensors[:4]
+        P0 = ctx.saved_tensors[4] if ctx.has_p0 else None
+        B, H = ctx.sizes
+        if g_mean is None and g_cov is None:
+            return (None,) * 9
+        g_x0, g_U, g_P0, _ = _backward(ctx.plan, ctx.env_desc, x0.device, x0, U, P0, B, H, mean, cov, g_mean, g_cov)
+        need = ctx.needs_input_grad
+        return (_like_input(g_x0, x0.dim() == 2) if need[0] else None, _like_input(g_U, U.dim() == 3) if need[1] else None,
+                g_P0 if (need[2] and ctx.has_p0) else None, None, None, None, None, None, None)
+
+
+def _like_input(g, per_candidate):
+    """A shared input's gradient is the sum of the candidates' (the kernel writes per candidate: no atomics)."""
+    return g if per_candidate else g.sum(0)
+
+
+def moment_rollout_plan(plan, env_desc, x0: torch.Tensor, U: torch.Tensor, P0: Optional[torch.Tensor] = None,
+                        want_var: bool = False, want_jac: bool = False, differentiable: bool = False) -> MomentTube:
+    """``gpmpc_moment_rollout`` for a ``RealDataPlan`` and an environment descriptor (``moment_rollout`` takes both from an
+    ``Agent``).  ``x0 (nx,)`` or ``(B, nx)``, ``U (H, nu)`` or ``(B, H, nu)``, ``P0 (B, nx, nx)`` or None; ``B`` is taken from
+    whichever argument carries it (1 if none does).  No host synchronisation.  ``differentiable=True``: ``mean`` and ``cov`` carry
+    a ``grad_fn`` whose backward is one launch of ``gpmpc_moment_rollout_vjp``; ``x0``, ``U`` and ``P0`` receive gradients if they
+    require them (``var``, ``jac`` and ``info`` are not differentiable); the values are those of the default call, bit for bit."""
+    dev, x0, U, P0, B, H = _prepare(plan, env_desc, x0, U, P0)
+    if not differentiable:
+        return _forward(plan, env_desc, dev, x0, U, P0, B, H, want_var, want_jac)
+    mean, cov, info, var, jac = _MomentRollout.apply(x0, U, P0, plan, env_desc, B, H, bool(want_var), bool(want_jac))
+    return MomentTube(mean=mean, cov=cov, info=info, var=var, jac=jac)
+
+
 def moment_rollout(agent, x0, U, P0=None, use_feedback: Optional[bool] = None, want_var: bool = False,
-                   want_jac: bool = False) -> MomentTube:
+                   want_jac: bool = False, differentiable: bool = False) -> MomentTube:
     """The linearised mean / covariance tube of ``B`` candidates under the agent's real-data GP - the value + gradient model
     ``train_hallucinated_dynGP(0)`` builds (``agent._plan(use_grad=True)``) - and its environment (``agent.env_desc(use_feedback)``;
     None: ``agent.feedback.use``).  ``x0 (nx,)`` or ``(B, nx)``; ``U (H, nu)`` or ``(B, H, nu)``; ``P0 (B, nx, nx)`` or None (zero).
     The agent's hallucinated set is neither read nor changed, and nothing synchronises with the host (the plan itself is factorised
-    once, the first time the agent needs it, and that does)."""
+    once, the first time the agent needs it, and that does).  ``differentiable``: see ``moment_rollout_plan``."""
     _lib.require_hip_device(agent.torch_device)
-    return moment_rollout_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U, P0, want_var, want_jac)
+    return moment_rollout_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U, P0, want_var, want_jac, differentiable)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reverse-mode gradient and what it is for
+# ---------------------------------------------------------------------------------------------------------------------
+def moment_rollout_vjp_plan(plan, env_desc, tube: MomentTube, x0, U, P0=None, g_mean=None, g_cov=None):
+    """``gpmpc_moment_rollout_vjp`` (include/gpmpc_hip.h) for a ``RealDataPlan`` and an environment descriptor: the gradients of
+    ``sum(g_mean * tube.mean) + sum(g_cov * tube.cov)`` with respect to the inputs ``tube`` was computed from.  Returns
+    ``(g_x0, g_U, g_P0, info)`` with the shapes of the inputs - summed over the candidates where the input was shared, ``g_P0``
+    None when ``P0`` was (it comes back on the lower triangle, the part of ``P0`` that is read) - and ``info (B)`` int32.  A
+    cotangent that is None is zero.  One launch, no host synchronisation."""
+    dev, x0, U, P0, B, H = _prepare(plan, env_desc, x0, U, P0)
+    g_x0, g_U, g_P0, info = _backward(plan, env_desc, dev, x0, U, P0, B, H, tube.mean, tube.cov, g_mean, g_cov)
+    return _like_input(g_x0, x0.dim() == 2), _like_input(g_U, U.dim() == 3), g_P0, info
+
+
+def moment_rollout_vjp(agent, tube: MomentTube, x0, U, P0=None, g_mean=None, g_cov=None, use_feedback: Optional[bool] = None):
+    """``moment_rollout_vjp_plan`` with the model and environment ``moment_rollout(agent, ...)`` uses (reference
+    ``extra/zoro_code.py:52-128`` computes these sensitivities with three nested autograd Jacobians per step on the host)."""
+    _lib.require_hip_device(agent.torch_device)
+    return moment_rollout_vjp_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), tube, x0, U, P0, g_mean, g_cov)
+
+
+def chance_constraint_penalty(tube: MomentTube, rows, beta: float, eps: float = 1e-12) -> torch.Tensor:
+    """The squared violation of the ``beta``-tightened affine rows of a ``TubeRows`` (``ocp_rows(agent, v)`` gives the reference's)
+    by the moment tube, per candidate ``(B,)``:
+    ``sum_t sum_r relu(E_r mu_t + off_tr + beta sqrt(E_r P_t E_r^T + eps) - hi_tr)^2`` and the lower side likewise, a side that is
+    not finite taking no part.  Plain torch operations on the tube's device, differentiable in ``mean`` and ``cov``; ``eps`` keeps the
+    square root differentiable at ``P_0 = 0``.  Quadric rows are left out (an error if there is nothing else)."""
+    if rows.E is None or int(torch.as_tensor(rows.E).shape[0]) == 0:
+        raise _lib.GpmpcError("chance_constraint_penalty: the rows hold no affine row (quadric rows are not tightened)")
+    r = rows.to(tube.mean.device)
+    nx, T = int(tube.mean.shape[1]), int(tube.mean.shape[2])
+    if int(r.E.shape[1]) != nx or int(r.lo.shape[0]) != T:
+        raise _lib.GpmpcError(f"chance_constraint_penalty: the rows are for nx = {int(r.E.shape[1])} and {int(r.lo.shape[0])} stages, "
+                              f"the tube has nx = {nx} and {T}")
+    n_lin = r.n_lin
+    val = torch.einsum("rd,bdt->btr", r.E, tube.mean)
+    if r.off is not None:
+        val = val + r.off[None]
+    sd = float(beta) * torch.sqrt(torch.einsum("rd,btde,re->btr", r.E, tube.cov, r.E) + float(eps))
+    lo, hi = r.lo[None, :, :n_lin], r.hi[None, :, :n_lin]
+    zero = torch.zeros_like(val)
+    up = torch.where(torch.isfinite(hi), val + sd - torch.where(torch.isfinite(hi), hi, zero), zero)
+    dn = torch.where(torch.isfinite(lo), torch.where(torch.isfinite(lo), lo, zero) - (val - sd), zero)
+    return (torch.relu(up) ** 2 + torch.relu(dn) ** 2).sum(dim=(1, 2))
+
+
+def _check_plan_inputs(U0, cost, steps, lr):
+    if not callable(cost):
+        raise _lib.GpmpcError("plan_inputs: cost must be a function (tube, U) -> (B,)")
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise _lib.GpmpcError("plan_inputs: steps must be an integer >= 0")
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0.0:
+        raise _lib.GpmpcError("plan_inputs: lr must be a positive number")
+    if not torch.is_tensor(U0) or U0.dim() != 3:
+        raise _lib.GpmpcError("plan_inputs: U0 must be a tensor (B, H, nu): the population of input sequences")
+
+
+def plan_inputs_plan(plan, env_desc, x0, U0, cost, steps: int, lr: float, P0=None):
+    """``plan_inputs`` for a ``RealDataPlan`` and an environment descriptor."""
+    _check_plan_inputs(U0, cost, steps, lr)
+    dev = _lib.require_hip_device(plan.X_r.device)
+    U = U0.detach().to(device=dev, dtype=F64).clone()
+    B, steps = int(U.shape[0]), int(steps)
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    m, v = torch.zeros_like(U), torch.zeros_like(U)
+    hist = torch.empty(steps + 1, B, dtype=F64, device=dev)
+
+    def costs(tube, Uc):
+        c = cost(tube, Uc)
+        if not torch.is_tensor(c) or tuple(c.shape) != (B,):
+            raise _lib.GpmpcError(f"plan_inputs: cost must return a tensor ({B},), one value per candidate")
+        return c
+
+    for it in range(1, steps + 1):
+        Uc = U.detach().requires_grad_(True)
+        c = costs(moment_rollout_plan(plan, env_desc, x0, Uc, P0, differentiable=True), Uc)
+        hist[it - 1] = c.detach()
+        g, = torch.autograd.grad(c.sum(), Uc)                        # the candidates are independent: one backward launch for all
+        m = torch.lerp(m, g, 1.0 - b1)                               # the operations of torch.optim.Adam's single-tensor step
+        v = torch.addcmul(v * b2, g, g, value=1.0 - b2)
+        denom = v.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
+        U = torch.addcdiv(U, m, denom, value=-(lr / (1.0 - b1 ** it)))
+    with torch.no_grad():
+        hist[steps] = costs(moment_rollout_plan(plan, env_desc, x0, U, P0), U)
+    final = hist[steps]
+    best = torch.where(torch.isfinite(final), final, torch.full_like(final, float("inf"))).argmin()
+    return U, hist, best
+
+
+def plan_inputs(agent, x0, U0, cost, steps: int, lr: float, P0=None, use_feedback: Optional[bool] = None):
+    """Gradient-based improvement of a whole population of candidate input sequences ``U0 (B, H, nu)`` at once, in the style of
+    ``mle.fit_hyperparameters``: Adam (``torch.optim.Adam``'s update and defaults) on ``cost(tube, U) -> (B,)``, any torch function
+    of the differentiable moment tube of ``moment_rollout(agent, x0, U, P0, differentiable=True)`` and of ``U``
+    (``chance_constraint_penalty`` is one ingredient).  Returns the final ``U (B, H, nu)``, the cost history ``(steps + 1, B)`` - row
+    ``k`` is the cost before update ``k + 1``, the last row that of the result - and the index of the best candidate (0-dim, on the
+    device).  One forward and one backward launch per iteration, no host round trip inside the loop."""
+    _check_plan_inputs(U0, cost, steps, lr)
+    _lib.require_hip_device(agent.torch_device)
+    return plan_inputs_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U0, cost, steps, lr, P0)
