@@ -188,9 +188,11 @@ def make_sharded_agent(agent_cls, params, env_model, group=None, pin_joint_path=
 
     ``pin_joint_path`` (``_lib.JOINT_VALU`` / ``_lib.JOINT_MFMA``; GPU only, process-wide): pins the kernel path of the joint
     draw.  Under the default (``None``: the dispatcher chooses per call) a sample's low-order bits depend on the shard size
-    once the factor cache covers only a prefix of the shard's samples (include/gpmpc_hip.h, factor_cache): pin the path
-    when the sharded run has to reproduce the single-process run BIT for bit (it agrees to 1e-13 / 1e-5 - Cholesky / eigh
-    root - either way).
+    once the factor cache covers only a prefix of the shard's samples (include/gpmpc_hip.h, factor_cache).  Pin the VALU
+    path (``_lib.JOINT_VALU``) when the sharded run has to reproduce the single-process run BIT for bit: there every factor
+    row is the same sequence of FMAs whatever is cached.  The matrix-pipe pin (``_lib.JOINT_MFMA``) only fixes the path: a
+    prefix cache and a whole cache sum the same entries in another grouping and agree to ROUNDING, not bit for bit (the
+    runs agree to 1e-13 / 1e-5 - Cholesky / eigh root - under either pin and without one).
 
     ``agent.base_sample_generator: counter`` (the scalable way): the rank generates exactly its own shard from the
     counter-based stream keyed by global sample id - on its own device, no other shard is ever materialised, and sample

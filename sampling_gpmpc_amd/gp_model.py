@@ -342,7 +342,8 @@ class HipPosterior:
         if whole and os.environ.get("GPMPC_JOINT_PENDING", "1") != "0":
             pend = _lib.PENDING_WRITE | (_lib.PENDING_USE if fcache.pending_ok(mdl, n_ho, n_c) else 0)
         self.used_pending = bool(pend & _lib.PENDING_USE)
-        fcache.pending = None                                      # consumed (or stale) either way
+        self.pending_mask = int(pend)                             # what this launch was told (tests read the call's plan with it)
+        fcache.pending = None                                     # consumed (or stale) either way
 
         def call(lo, hi, cache, mode):
             sl = lambda t: None if t is None else t[lo:hi]

@@ -187,7 +187,14 @@ def test_config5_shard_as_shipped(sg):
             # (120 hallucinated slots >= GPMPC_JOINT_MFMA_FROM); a dispatcher change that silently drops it fails here
             assert raw.gpmpc_joint_last_path() == sg._lib.JOINT_MFMA, k     # (k = 0: no hallucinated slot, joint_real_mfma_kernel)
             sv, sy, su = small.dyn_fg_jacobians(small.get_batch_x_hat(xs, u_h), k)
+            assert raw.gpmpc_joint_last_path() == sg._lib.JOINT_MFMA, k
             mv, my, _ = mid.dyn_fg_jacobians(mid.get_batch_x_hat(xm, u_h), k)
+            assert raw.gpmpc_joint_last_path() == sg._lib.JOINT_MFMA, k
+            # the factor cache IS hit and the pending rows ARE used (nobody assigns these Agents' hallucinated tensors): a facade
+            # change that silently stops either leaves every comparison below green
+            for a in (agent, small, mid):
+                assert a.model_i_call.n_cached_rows == ((k - 1) * 120 if k >= 2 else 0), k
+                assert bool(a.model_i_call.used_pending) == (k >= 2), k
             np.testing.assert_array_equal(gp_val[m0:m0 + msub], mv)
             np.testing.assert_array_equal(y_grad[m0:m0 + msub], my)
             osmall.dyn_fg_jacobians(osmall.get_batch_x_hat(xs, u_h), k)

@@ -488,7 +488,101 @@ def test_joint_draw_matrix_pipe_against_oracle(sg, pname, Ns, H, iters, cache):
         lib.gpmpc_joint_pin_path(sg._lib.JOINT_AUTO)
 
 
-def _joint_draw_against_oracle(sg, pname, Ns, H, iters, expect_path=None, cache=True):
+def joint_draw_comparison_block(agent, oagent, p, it, outs, oouts, tag="", sigma_bound=None):
+    """One joint draw of the HIP Agent against the same draw of the oracle Agent (both have just run ``dyn_fg_jacobians``, whose
+    results are ``outs`` / ``oouts``; ``it``: the SQP iteration, ``agent.mpc_iter``: the MPC step of the base samples): mean, variance,
+    covariance, the samples at the kernel's own jitter level on the oracle's covariance, the legitimacy of a retry, and the Jacobians
+    where both sides took the same level.  ``sigma_bound``: absolute bound on max|Sigma - Sigma_o| (default: 1e-7 max|Sigma_o|).
+    Returns the measured covariance error and its scale."""
+    gp_val, y_grad, u_grad = outs
+    ogp_val, oy_grad, ou_grad = oouts
+    post, opost = agent.model_i_call, oagent.model_i_call
+    Ns = int(opost.mean.shape[0])
+    np.testing.assert_allclose(post.mean.cpu().numpy(), opost.mean.numpy(), rtol=1e-6, atol=1e-9)
+    np.testing.assert_allclose(post.variance.cpu().numpy(), opost.variance.numpy(), rtol=1e-4, atol=1e-12)
+    S, So = post.covariance_matrix.cpu().numpy(), opost.covariance_matrix.numpy()
+    err_S, scale_S = float(np.max(np.abs(S - So))), float(np.max(np.abs(So)))
+    bound_S = 1e-7 * scale_S if sigma_bound is None else float(sigma_bound)
+    print(f"{tag} it={it}: |Sigma - Sigma_o| {err_S:.2e} = {err_S / scale_S:.1e} max|Sigma_o| (bound {bound_S / scale_S:.1e})")
+    assert err_S < bound_S
+    lvl = ((post.last_info.cpu().numpy() >> 1) & 7)
+    ojit = opost.root_info.jitter_added.numpy()
+    olvl = np.where(ojit == 0, 0, np.round(np.log10(np.maximum(ojit, 1e-300) / p["agent"]["Dyn_gp_jitter"])) + 1)
+    same = (lvl == olvl).all(axis=1)
+    print(f"{tag} it={it}: n_h={oagent.model_i.train_inputs[0].shape[2]}, jitter levels agree on "
+          f"{same.sum()}/{Ns} samples; max level {lvl.max()}")
+    # Whether the un-jittered attempt on the numerically singular Sigma passes is a round-off coin flip (+-1e-17
+    # pivots), so the retry LEVEL may differ between LAPACK and the kernel.  What is defined for EVERY sample: given
+    # the level the kernel took, its draw is mu + chol(Sigma + level I) z on the oracle's Sigma (clipped), and a
+    # retry is legitimate only if the level below fails or is borderline (pivot < 1e-12 max|Sigma|) there.
+    jit0 = p["agent"]["Dyn_gp_jitter"]
+    So_t, mu_o, var_o = opost.covariance_matrix, opost.mean, opost.variance
+    n = So_t.shape[-1]
+    eye = torch.eye(n, dtype=F64)
+    lvl_t = torch.as_tensor(lvl.astype(np.int64))
+    jit_k = torch.where(lvl_t == 0, torch.zeros(lvl_t.shape, dtype=F64), jit0 * 10.0 ** (lvl_t.to(F64) - 1))
+    Lk, info_k = torch.linalg.cholesky_ex(So_t + jit_k[..., None, None] * eye)
+    z_it = agent.epistimic_random_vector[agent.mpc_iter][it].cpu().to(F64)
+    y_ref = mu_o + (Lk @ z_it.reshape(Ns, -1, n, 1)).reshape(mu_o.shape)
+    sd = p["agent"]["Dyn_gp_beta"] * var_o.sqrt()
+    y_ref = torch.min(torch.max(y_ref, mu_o - sd), mu_o + sd)
+    ok_k = (info_k == 0)
+    # (a level-0 pass of the kernel on a matrix LAPACK rejects at the same level is the coin flip itself: compare
+    # those samples at the oracle's level instead - they are the `same == False` ones with lvl == 0)
+    cmp = ok_k.all(dim=1).numpy()
+    assert cmp.sum() >= Ns - (~same).sum(), "the kernel's level must factorise on the oracle's matrix"
+    np.testing.assert_allclose(agent.model_i_samples.cpu().numpy()[cmp], y_ref.numpy()[cmp], rtol=2e-5, atol=1e-8)
+    scale_o = So_t.abs().amax(dim=(-1, -2))
+    jit_p = torch.where(lvl_t <= 1, torch.zeros(lvl_t.shape, dtype=F64), jit0 * 10.0 ** (lvl_t.to(F64) - 2))
+    Lp, info_p = torch.linalg.cholesky_ex(So_t + jit_p[..., None, None] * eye)
+    minpiv = (torch.diagonal(Lp, dim1=-1, dim2=-2) ** 2).amin(dim=-1)
+    legit = (lvl_t == 0) | (info_p > 0) | (minpiv < 1e-12 * scale_o)
+    assert bool(legit.all()), "a jitter retry on a matrix that is clearly positive definite one level below"
+    print(f"    all {int(cmp.sum())}/{Ns} samples match mu + chol(Sigma + level I) z at the kernel's own level; retries legitimate")
+    np.testing.assert_allclose(gp_val[same], ogp_val[same], rtol=1e-5, atol=1e-8)
+    np.testing.assert_allclose(y_grad[same], oy_grad[same], rtol=1e-3, atol=1e-6)
+    np.testing.assert_allclose(u_grad[same], ou_grad[same], rtol=1e-3, atol=1e-6)
+    return err_S, scale_S
+
+
+def joint_call_state(sg, agent):
+    """What the joint draw the Agent has just made was given and did, read BEFORE anything repeats the posterior (a later
+    ``covariance_matrix`` is a second launch of the same posterior object and overwrites these attributes): cached rows, the pending
+    mask the facade passed, the path that ran, and the launch plan of that very call (``gpmpc_debug_joint_plan`` with the call's own
+    arguments under the current knobs)."""
+    import ctypes
+    lib = sg._lib.load()
+    post, mdl = agent.model_i_call, agent.model_i
+    fc = agent._ws_cache.get("joint_factor_cache")
+    Ns, _, m, _ = post._x.shape
+    n_ho = int(mdl.h_slots.numel())
+    # (the facade hands the entry point its cache from 16 observed slots on: JointFactorCache.prepare)
+    cache_rows = int(fc.rows) if (fc is not None and fc.enabled and fc.buf is not None and n_ho >= 16) else 0
+    raw = ctypes.CDLL(sg._lib.LIB_PATH)
+    raw.gpmpc_debug_joint_plan.argtypes = [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_int32] * 8 + [ctypes.c_char_p, ctypes.c_size_t]
+
+    def plan(ns, rows, n_c, pend):
+        buf = ctypes.create_string_buffer(512)
+        rc = raw.gpmpc_debug_joint_plan(ctypes.addressof(mdl.plan.desc), int(ns), int(mdl.n_h), n_ho, int(m), rows, n_c, pend, 0, 0, buf, 512)
+        assert rc == 0
+        return buf.value.decode()
+
+    # a cache that holds a prefix of the samples: two launches - the prefix with the cache, the rest without ("plan_rest")
+    n_cs = int(fc.n_samples) if cache_rows else 0
+    prefix = 0 < n_cs < Ns
+    return {"n_cached_rows": int(post.n_cached_rows), "used_pending": bool(post.used_pending), "pending_mask": int(post.pending_mask),
+            "cache_rows": cache_rows, "cache_samples": n_cs, "n_h": int(mdl.n_h), "n_ho": n_ho,
+            "path": int(lib.gpmpc_joint_last_path()), "bits": int(post.last_bits),
+            "plan": plan(n_cs if prefix else Ns, cache_rows, int(post.n_cached_rows), int(post.pending_mask)),
+            "plan_rest": plan(Ns - n_cs, 0, 0, 0) if prefix else None}
+
+
+def _joint_draw_against_oracle(sg, pname, Ns, H, iters, expect_path=None, cache=True, follow="oracle", check_call=None):
+    """``follow``: whose hallucinated tensors both Agents continue from.  "oracle": the HIP Agent is ASSIGNED the oracle's after every
+    iteration - a new hallucinated-set generation (Agent's property setters), so its factor cache is never hit.  "hip": the oracle adopts
+    the HIP Agent's, whose attributes are never assigned: its generation survives, the cache is hit from the third iteration on and the
+    draws use their predecessors' pending rows.  ``check_call(it, state)``: called with ``joint_call_state`` of every draw."""
+    assert follow in ("oracle", "hip")
     p = load_params(pname)
     p["agent"]["num_dyn_samples"], p["optimizer"]["H"] = Ns, H
     p["agent"]["true_dyn_as_sample"] = False
@@ -512,55 +606,74 @@ def _joint_draw_against_oracle(sg, pname, Ns, H, iters, expect_path=None, cache=
             off = JointFactorCache()
             off.enabled = False
             agent._ws_cache["joint_factor_cache"] = off
-        gp_val, y_grad, u_grad = agent.dyn_fg_jacobians(bx, it)
+        outs = agent.dyn_fg_jacobians(bx, it)
         if expect_path is not None and it >= 1:
             assert sg._lib.load().gpmpc_joint_last_path() == expect_path, "the pinned joint path did not run"
-        ogp_val, oy_grad, ou_grad = oagent.dyn_fg_jacobians(obx, it)
-        post, opost = agent.model_i_call, oagent.model_i_call
-        np.testing.assert_allclose(post.mean.cpu().numpy(), opost.mean.numpy(), rtol=1e-6, atol=1e-9)
-        np.testing.assert_allclose(post.variance.cpu().numpy(), opost.variance.numpy(), rtol=1e-4, atol=1e-12)
-        S, So = post.covariance_matrix.cpu().numpy(), opost.covariance_matrix.numpy()
-        assert np.max(np.abs(S - So)) < 1e-7 * np.max(np.abs(So))
-        lvl = ((post.last_info.cpu().numpy() >> 1) & 7)
-        ojit = opost.root_info.jitter_added.numpy()
-        olvl = np.where(ojit == 0, 0, np.round(np.log10(np.maximum(ojit, 1e-300) / p["agent"]["Dyn_gp_jitter"])) + 1)
-        same = (lvl == olvl).all(axis=1)
-        print(f"{pname} it={it}: n_h={oagent.model_i.train_inputs[0].shape[2]}, jitter levels agree on "
-              f"{same.sum()}/{Ns} samples; max level {lvl.max()}")
-        # Whether the un-jittered attempt on the numerically singular Sigma passes is a round-off coin flip (+-1e-17
-        # pivots), so the retry LEVEL may differ between LAPACK and the kernel.  What is defined for EVERY sample: given
-        # the level the kernel took, its draw is mu + chol(Sigma + level I) z on the oracle's Sigma (clipped), and a
-        # retry is legitimate only if the level below fails or is borderline (pivot < 1e-12 max|Sigma|) there.
-        jit0 = p["agent"]["Dyn_gp_jitter"]
-        So_t, mu_o, var_o = opost.covariance_matrix, opost.mean, opost.variance
-        n = So_t.shape[-1]
-        eye = torch.eye(n, dtype=F64)
-        lvl_t = torch.as_tensor(lvl.astype(np.int64))
-        jit_k = torch.where(lvl_t == 0, torch.zeros(lvl_t.shape, dtype=F64), jit0 * 10.0 ** (lvl_t.to(F64) - 1))
-        Lk, info_k = torch.linalg.cholesky_ex(So_t + jit_k[..., None, None] * eye)
-        z_it = agent.epistimic_random_vector[0][it].cpu().to(F64)
-        y_ref = mu_o + (Lk @ z_it.reshape(Ns, -1, n, 1)).reshape(mu_o.shape)
-        sd = p["agent"]["Dyn_gp_beta"] * var_o.sqrt()
-        y_ref = torch.min(torch.max(y_ref, mu_o - sd), mu_o + sd)
-        ok_k = (info_k == 0)
-        # (a level-0 pass of the kernel on a matrix LAPACK rejects at the same level is the coin flip itself: compare
-        # those samples at the oracle's level instead - they are the `same == False` ones with lvl == 0)
-        cmp = ok_k.all(dim=1).numpy()
-        assert cmp.sum() >= Ns - (~same).sum(), "the kernel's level must factorise on the oracle's matrix"
-        np.testing.assert_allclose(agent.model_i_samples.cpu().numpy()[cmp], y_ref.numpy()[cmp], rtol=2e-5, atol=1e-8)
-        scale_o = So_t.abs().amax(dim=(-1, -2))
-        jit_p = torch.where(lvl_t <= 1, torch.zeros(lvl_t.shape, dtype=F64), jit0 * 10.0 ** (lvl_t.to(F64) - 2))
-        Lp, info_p = torch.linalg.cholesky_ex(So_t + jit_p[..., None, None] * eye)
-        minpiv = (torch.diagonal(Lp, dim1=-1, dim2=-2) ** 2).amin(dim=-1)
-        legit = (lvl_t == 0) | (info_p > 0) | (minpiv < 1e-12 * scale_o)
-        assert bool(legit.all()), "a jitter retry on a matrix that is clearly positive definite one level below"
-        print(f"    all {int(cmp.sum())}/{Ns} samples match mu + chol(Sigma + level I) z at the kernel's own level; retries legitimate")
-        np.testing.assert_allclose(gp_val[same], ogp_val[same], rtol=1e-5, atol=1e-8)
-        np.testing.assert_allclose(y_grad[same], oy_grad[same], rtol=1e-3, atol=1e-6)
-        np.testing.assert_allclose(u_grad[same], ou_grad[same], rtol=1e-3, atol=1e-6)
+        if check_call is not None:
+            state = joint_call_state(sg, agent)
+            print(f"{pname} it={it}: cached rows {state['n_cached_rows']} of {state['n_ho']}, pending mask {state['pending_mask']}, "
+                  f"used_pending {state['used_pending']}; {state['plan']}")
+            check_call(it, state)
+        oouts = oagent.dyn_fg_jacobians(obx, it)
+        joint_draw_comparison_block(agent, oagent, p, it, outs, oouts, tag=pname)
         # keep both agents on the SAME hallucinated data for the next iteration
-        agent.Hallcinated_X_train = oagent.Hallcinated_X_train.to(agent.torch_device)
-        agent.Hallcinated_Y_train = oagent.Hallcinated_Y_train.to(agent.torch_device)
+        if follow == "oracle":
+            agent.Hallcinated_X_train = oagent.Hallcinated_X_train.to(agent.torch_device)
+            agent.Hallcinated_Y_train = oagent.Hallcinated_Y_train.to(agent.torch_device)
+        else:
+            oagent.Hallcinated_X_train = agent.Hallcinated_X_train.cpu()
+            oagent.Hallcinated_Y_train = agent.Hallcinated_Y_train.cpu()
+
+
+CACHE_HIT_SHAPES = [
+    ("params_car_residual", 8, 40, 4),            # 45 + 360 slots at it = 3: 26 tiles, 121 columns = 8 column tiles
+    ("params_pendulum1D_samples", 16, 30, 4),     # 36 real slots, 91 columns = 6 column tiles
+    ("params_car_residual", 8, 12, 3),            # 37 columns: 3 column tiles, a ragged last slot tile at every iteration
+    ("params_car_residual", 4, 40, 5),            # it = 4: 45 + 480 = 525 slots, TOP + BOTTOM behind 360 cached rows
+    ("params_pendulum1D_samples", 6, 30, 6),      # it = 4: 36 + 360 = 396 slots, the one-launch limit; it = 5: 486 slots, ragged bottom tile
+]
+
+
+@pytest.mark.parametrize("pending", ["1", "0"])
+@pytest.mark.parametrize("pname,Ns,H,iters", CACHE_HIT_SHAPES)
+def test_joint_draw_matrix_pipe_cache_hit_against_oracle(sg, pname, Ns, H, iters, pending, monkeypatch):
+    """The cached shapes of test_joint_draw_matrix_pipe_against_oracle with the factor cache HIT: the oracle follows the kernel, so the
+    HIP Agent's hallucinated-set generation survives and from the third iteration on a draw reuses the cached factor rows
+    (``n_cached_rows == (it - 1) H T``).  With pending rows (GPMPC_JOINT_PENDING=1) it only factorises in place the X^T / S block its
+    predecessor left behind - joint_chol_mfma_kernel(pend_use), joint_test_mfma_kernel(TEST, pend_write, Sv=cache),
+    joint_tail_mfma_kernel(Sv=cache); without them the new rows are joint_test_mfma_kernel(FACTOR) against the cached columns; beyond 416
+    slots the test rows are TOP + BOTTOM behind the hit cache.  The launch plan of every call is read with the call's own arguments and
+    must contain the steps named here; the comparison is the one of the other joint-draw tests, at its tolerances (the oracle's own
+    result moves by at most 8e-10 max|Sigma| under a reversal of its conditioning set at these scattered points)."""
+    monkeypatch.setenv("GPMPC_JOINT_PENDING", pending)
+    on, T = pending == "1", 3
+    seen = set()
+
+    def check_call(it, st):
+        plan = st["plan"].split("|")[1].strip()
+        assert st["path"] == sg._lib.JOINT_MFMA and st["plan"].startswith("path=2 batches=1 ")
+        assert st["n_cached_rows"] == (0 if it <= 1 else (it - 1) * H * T)
+        assert st["used_pending"] == (on and it >= 2)
+        assert "joint_kernel(" not in plan
+        split = "TEST_TOP" in plan
+        assert split == (st["n_ho"] + (45 if "car" in pname else 36) > 416)
+        if split:
+            assert "joint_test_mfma(TEST_TOP) joint_test_mfma(TEST_BOTTOM)" in plan
+        if it >= 2:
+            assert plan.startswith("joint_chol_mfma(pend_use) " if on else "joint_test_mfma(FACTOR) joint_chol_mfma() ")
+        if on and it >= 1 and not split:
+            assert "joint_test_mfma(TEST,pend_write,Sv=cache)" in plan and "Sv=cache)" in plan.split("joint_tail_mfma(")[1]
+        seen.update(s.split(")")[0] + ")" for s in plan.split(" "))
+
+    lib = sg._lib.load()
+    lib.gpmpc_joint_pin_path(sg._lib.JOINT_MFMA)
+    try:
+        _joint_draw_against_oracle(sg, pname, Ns, H, iters, expect_path=sg._lib.JOINT_MFMA, follow="hip", check_call=check_call)
+    finally:
+        lib.gpmpc_joint_pin_path(sg._lib.JOINT_AUTO)
+    assert ("joint_chol_mfma(pend_use)" if on else "joint_test_mfma(FACTOR)") in seen
+    if iters >= 5:
+        assert "joint_test_mfma(TEST_TOP)" in seen and "joint_test_mfma(TEST_BOTTOM)" in seen
 
 
 def test_joint_draw_eigh_fallback_distribution(sg):

@@ -1,7 +1,8 @@
 """CPU: the joint draw's launch plan (plan_joint_draw, csrc/joint_plan.hpp) through gpmpc_debug_joint_plan, for the closed loops'
 shapes and the paths the knobs select.  Each expected line is the kernel sequence the dispatcher launched for the same call before
 it was split into a plan and an executor (kernel trace of that build; one batch's steps, repeated `batches` times, then the eigh
-launches)."""
+launches).  The rows of the cache-hit oracle comparisons (small batches behind a hit cache, a covariance-only repeat, a prefix cache) are
+read off plan_joint_draw's branches instead; the GPU tests that make those calls assert the steps named there on the call's own plan."""
 import ctypes
 
 import pytest
@@ -85,6 +86,35 @@ PLANS = [
     # m T = 135 > 128: the VALU path in one launch
     (CAR, 256, 45, 135, 45, 384, 0, 2, 0, 100, '',
      'path=1 batches=1 | joint_kernel(ALL,nrow=271) | eigh=full pending_written=0'),
+    # (new rows go to the END of the table: a row's position is part of its test id)
+    # the calls of the cache-hit oracle comparisons (tests/test_hip_parity.py, tests/test_hip_joint_cache_parity.py)
+    # pendulum 16 x 30, k = 2 with pending rows: the in-place Cholesky of the block the k = 1 draw left, nothing else in front of the test rows
+    (PEND, 16, 60, 180, 30, 384, 90, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # the same call allowed to WRITE pending rows only (the previous draw left none): the new rows against the cached columns
+    (PEND, 16, 60, 180, 30, 384, 90, 2, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # ... and with pending rows off (GPMPC_JOINT_PENDING=0)
+    (PEND, 16, 60, 180, 30, 384, 90, 0, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # a covariance-only repeat of that posterior (every row cached): no factor step, the pending rows are written again
+    (PEND, 16, 60, 180, 30, 384, 180, 2, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # pendulum 6 x 30, k = 5: 36 + 450 = 486 slots, TOP / BOTTOM behind 360 cached rows and a pending block
+    (PEND, 6, 150, 450, 30, 640, 360, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST_TOP) joint_test_mfma(TEST_BOTTOM) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # ... with pending rows off
+    (PEND, 6, 150, 450, 30, 640, 360, 0, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST_TOP) joint_test_mfma(TEST_BOTTOM) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # pendulum, MPC step 1, k = 0 behind a 384-row cache: 396 slots in one launch, no room for pending rows behind the 360 slots
+    (PEND, 16, 120, 360, 30, 384, 270, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # a cache that holds a prefix of the samples (3 of 7), k = 2: the cached samples without pending rows ...
+    (PEND, 3, 60, 180, 30, 384, 90, 0, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # ... and the other four through the workspace's temporary cache
+    (PEND, 4, 60, 180, 30, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_kernel(FACTOR,nrow=180) joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
 ]
 
 
