@@ -233,7 +233,7 @@ __device__ __forceinline__ double wave_sum_shfl(double v) {
 //   cov(task_a(x), task_b(x')):  (0,0) k ; (0,b) +k q_b ; (a,0) -k q_a ; (a,b) k (delta_ab / l_a^2 - q_a q_b)
 // ---------------------------------------------------------------------------------------------------------------
 template <int D>
-__device__ __forceinline__ double kern_entry(const double (&q)[D], double k, const double* inv_l2, int a, int b) {
+__host__ __device__ __forceinline__ double kern_entry(const double (&q)[D], double k, const double* inv_l2, int a, int b) {
     if (a == 0) return (b == 0) ? k : k * q[b - 1];
     if (b == 0) return -k * q[a - 1];
     double v = -q[a - 1] * q[b - 1];

@@ -11,82 +11,32 @@
 //   * pass 2: w_j = (L^-T acc)_j = column j of the SAME packed triangle dotted with acc[j..] (no second table), and
 //     d s / d xi_d = -2 sum_j w_j d k_j / d xi_d.  The kernel rows are formed again (one exponential per real point): keeping them
 //     would cost NRP more registers per lane next to acc[NRP].
-// Then the adjoint of one step, with A_t rebuilt exactly as the forward builds it:
+// Then the adjoint of one step, with A_t from the function the forward builds it with (moments_step.hpp):
 //   Abar = 2 Lambda A P,  Pbar = A^T Lambda A,  sbar_o = Lambda_ii G_io^2 (zero where the variance was raised to the floor),
 //   mbar / vbar / the input cotangent from env_step, gbar (cotangent of grad m) and further mbar / vbar terms from the entries of A,
 //   xibar = sum_o (mbar_o grad m_o + Hess m_o gbar_o + sbar_o grad s_o) scattered through d xi / d x and the feedback gain,
 //   lambda_t = xbar + gM[:, t],  Lambda_t = Pbar + sym(gP[:, t]).
 // Gradients are per candidate (no cross-lane reduction, no atomics).  The step body is a __host__ __device__ function so that the
 // same arithmetic can be compiled for the host and compared with autograd without a GPU.
-#include "gpmpc_host.hpp"
+#include "moments_step.hpp"
 
-#include <climits>
 #include <cmath>
 
 namespace gpmpc {
 
-constexpr int MGV_MAX_ROWS = 64;           // label rows, as MOM_MAX_ROWS (moments.hip)
-
-typedef double double2_g __attribute__((ext_vector_type(2)));
-
-struct MomentGradArgs {
-    GpParams gp;
-    EnvParams env;
-    const double* plan;
-    const double* X_r;
-    long B;
-    int H, x0_per, u_per;
-    const double *x0, *U, *M, *P, *gM, *gP;
+struct MomentGradArgs : MomentStepArgs {
+    const double *M, *P, *gM, *gP;
     double *gx0, *gU, *gP0;
     int* info;
 };
-
-// packed lower triangle, column-major, every column start 16-byte aligned: the layout of mom_col_ofs (moments.hip)
-template <int NRP>
-__host__ __device__ constexpr int mgv_col_ofs(int j) {
-    static_assert(NRP % 2 == 0, "even row count: a column of odd length is padded by one entry");
-    return j * NRP - j * (j - 1) / 2 + j / 2;
-}
-
-// the staging of moments.hip: thread tid of nt fills its share of the three tables
-template <int NRP, int G_NY>
-__host__ __device__ inline void mgv_stage(const MomentGradArgs& a, double* Ltri, double* alpha_s, double* xr_s, int tid, int nt) {
-    constexpr int TRI = mgv_col_ofs<NRP>(NRP);
-    const GpParams& gp = a.gp;
-    const int n = gp.n_r;
-    for (int e = tid; e < G_NY * NRP * NRP; e += nt) {
-        const int o = e / (NRP * NRP), rem = e - o * NRP * NRP, j = rem / NRP, i = rem - j * NRP;
-        if (i >= j)
-            Ltri[o * TRI + mgv_col_ofs<NRP>(j) + (i - j)] = (i < n) ? a.plan[o * gp.plan_stride + (long)n * n + (long)j * n + i] : 0.0;
-    }
-    for (int e = tid; e < G_NY * NRP; e += nt) {
-        const int o = e / NRP, i = e - o * NRP;
-        alpha_s[e] = (i < n) ? a.plan[o * gp.plan_stride + 2L * n * n + n + i] : 0.0;
-    }
-    for (int e = tid; e < 2 * NRP; e += nt) xr_s[e] = (e < 2 * gp.N_r) ? a.X_r[e] : 0.0;
-}
-
-__host__ __device__ __forceinline__ bool mgv_finite(double abs_sum) { return abs_sum < __builtin_inf(); }   // false for NaN and inf
-
-// row a of the kernel block of a test point against label task b (kern_entry, gpmpc_device.hpp, for both compilations)
-__host__ __device__ __forceinline__ double mgv_row(const double (&q)[2], double k, const double* il, int a, int b) {
-    if (a == 0) return (b == 0) ? k : k * q[b - 1];
-    if (b == 0) return -k * q[a - 1];
-    double v = -q[a - 1] * q[b - 1];
-    if (a == b) v += il[a - 1];
-    return k * v;
-}
 
 // The whole backward sweep of candidate b.  Ltri / alpha_s / xr_s: the staged tables (LDS on the device).
 template <int ENV, int NRP, bool HG>
 __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, const double* Ltri, const double* alpha_s,
                                                         const double* xr_s, const long b, const bool active) {
-    constexpr int NX = (ENV == GPMPC_ENV_PENDULUM1D) ? 2 : 4;
-    constexpr int NU = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 2;
-    constexpr int G_NY = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 3;
-    constexpr int SEL = (ENV == GPMPC_ENV_PENDULUM1D) ? 0 : 2;        // the state the GP input reads
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY, SEL = EnvDims<ENV>::SEL;
     constexpr int TR = HG ? 3 : 1;
-    constexpr int TRI = mgv_col_ofs<NRP>(NRP);
+    constexpr int TRI = mom_col_ofs<NRP>(NRP);
     const GpParams& gp = a.gp;
     const int n = gp.n_r;
     const int H = a.H;
@@ -123,24 +73,9 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
             x[d] = a.M[(b * NX + d) * (H + 1) + t];
             chk += fabs(x[d]);
         }
-        {
-            const double* uf = a.U + ((a.u_per ? b * H : 0) + t) * NU;
+        env_input_ct<ENV>(a.env, x, a.U + ((a.u_per ? b * H : 0) + t) * NU, u, xi);
 #pragma unroll
-            for (int i = 0; i < NU; ++i) {
-                const double ufi = uf[i];
-                if (use_fb) {
-                    double acc = 0.0;
-#pragma unroll
-                    for (int j = 0; j < NX; ++j) acc += (a.env.x_goal[j] - x[j]) * a.env.K[i][j];
-                    u[i] = -acc + ufi;
-                } else {
-                    u[i] = ufi;
-                }
-                chk += fabs(u[i]);
-            }
-            xi[0] = x[SEL];
-            xi[1] = u[0];
-        }
+        for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
 
         // ---- the GP at xi: mean, gradient, Hessian, variance and its gradient per output ----------------------------------------
         double gm[G_NY], gs[G_NY], gd[G_NY][2], gh[G_NY][3], ge[G_NY][2];   // gh: H00, H01, H11; ge: d s / d xi (0 where clamped)
@@ -150,111 +85,48 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
             const double os = gp.os[o];
             const double* LT = Ltri + o * TRI;
             const double* al = alpha_s + o * NRP;
-            double acc[NRP];
+            double acc[MOM_ACC<NRP>];
 #pragma unroll
             for (int i = 0; i < NRP; ++i) acc[i] = 0.0;
-            double m = 0.0, d0 = 0.0, d1 = 0.0, h00 = 0.0, h01 = 0.0, h11 = 0.0, k = 0.0, q[2] = {0.0, 0.0};
-#pragma unroll
-            for (int j = 0; j < NRP; ++j) {
-                if (j < n) {                                           // uniform
-                    const int tb = j % TR;
-                    if (tb == 0) {
-                        const double r0 = xi[0] - xr_s[2 * (j / TR)], r1 = xi[1] - xr_s[2 * (j / TR) + 1];
-                        q[0] = r0 * il[0];
-                        q[1] = r1 * il[1];
-                        k = os * exp(-0.5 * (r0 * q[0] + r1 * q[1]));
-                    }
-                    const double kj = mgv_row(q, k, il, 0, tb);
-                    const double aj = al[j];
-                    m = fma(kj, aj, m);
-                    d0 = fma(mgv_row(q, k, il, 1, tb), aj, d0);
-                    d1 = fma(mgv_row(q, k, il, 2, tb), aj, d1);
-                    h00 = fma(kern_entry_hess<2>(q, k, il, 0, 0, tb), aj, h00);
-                    h01 = fma(kern_entry_hess<2>(q, k, il, 0, 1, tb), aj, h01);
-                    h11 = fma(kern_entry_hess<2>(q, k, il, 1, 1, tb), aj, h11);
-                    const double* col = LT + mgv_col_ofs<NRP>(j);
-#pragma unroll
-                    for (int i = j; i + 1 < NRP; i += 2) {
-                        const double2_g l = *reinterpret_cast<const double2_g*>(col + (i - j));
-                        acc[i] = fma(l.x, kj, acc[i]);
-                        acc[i + 1] = fma(l.y, kj, acc[i + 1]);
-                    }
-                    if ((NRP - j) & 1) acc[NRP - 1] = fma(col[NRP - 1 - j], kj, acc[NRP - 1]);
-                    asm volatile("" ::: "memory");                     // one column of LDS loads in flight (moments.hip)
-                }
-            }
-            double ss = 0.0;
-#pragma unroll
-            for (int i = 0; i < NRP; ++i) ss = fma(acc[i], acc[i], ss);
-            double s = os - ss;
-            const bool clamped = s < gp.var_floor;                     // (NaN: not clamped, the candidate is non-finite)
-            if (clamped) {
-                s = gp.var_floor;
-                info_acc |= GPMPC_INFO_VAR_CLAMPED;
-            }
+            MomGpSums g;                                               // pass 1: the forward's column loop, with the Hessian sums
+            const double ss = mom_gp_pass1<NRP, HG, true>(LT, al, xr_s, n, il, os, xi, acc, g);
+            double s, k = 0.0, q[2] = {0.0, 0.0};
+            const bool clamped = mom_variance(gp, os, ss, s, info_acc);
             // pass 2: w = L^-T acc column by column, d s / d xi_d = -2 sum_j w_j d k_j / d xi_d
             double e0 = 0.0, e1 = 0.0;
 #pragma unroll
             for (int j = 0; j < NRP; ++j) {
                 if (j < n) {
                     const int tb = j % TR;
-                    if (tb == 0) {
-                        const double r0 = xi[0] - xr_s[2 * (j / TR)], r1 = xi[1] - xr_s[2 * (j / TR) + 1];
-                        q[0] = r0 * il[0];
-                        q[1] = r1 * il[1];
-                        k = os * exp(-0.5 * (r0 * q[0] + r1 * q[1]));
-                    }
-                    const double* col = LT + mgv_col_ofs<NRP>(j);
+                    if (tb == 0) mom_kernel_point(xi, xr_s, j / TR, il, os, q, k);
+                    const double* col = LT + mom_col_ofs<NRP>(j);
                     double wa = 0.0, wb = 0.0;                         // two chains: the even and the odd entries of the column
 #pragma unroll
                     for (int i = j; i + 1 < NRP; i += 2) {
-                        const double2_g l = *reinterpret_cast<const double2_g*>(col + (i - j));
+                        const double2_m l = *reinterpret_cast<const double2_m*>(col + (i - j));
                         wa = fma(l.x, acc[i], wa);
                         wb = fma(l.y, acc[i + 1], wb);
                     }
                     if ((NRP - j) & 1) wa = fma(col[NRP - 1 - j], acc[NRP - 1], wa);
                     const double w = wa + wb;
-                    e0 = fma(w, mgv_row(q, k, il, 1, tb), e0);
-                    e1 = fma(w, mgv_row(q, k, il, 2, tb), e1);
+                    e0 = fma(w, kern_entry<2>(q, k, il, 1, tb), e0);
+                    e1 = fma(w, kern_entry<2>(q, k, il, 2, tb), e1);
                     asm volatile("" ::: "memory");
                 }
             }
             e0 = clamped ? 0.0 : -2.0 * e0;
             e1 = clamped ? 0.0 : -2.0 * e1;
-            chk += fabs(m) + fabs(s) + fabs(d0) + fabs(d1) + fabs(h00) + fabs(h01) + fabs(h11) + fabs(e0) + fabs(e1);
+            chk += fabs(g.m) + fabs(s) + fabs(g.d0) + fabs(g.d1) + fabs(g.h00) + fabs(g.h01) + fabs(g.h11) + fabs(e0) + fabs(e1);
 #pragma unroll
             for (int oo = 0; oo < G_NY; ++oo)
                 if (oo == o) {
-                    gm[oo] = m, gs[oo] = s, gd[oo][0] = d0, gd[oo][1] = d1;
-                    gh[oo][0] = h00, gh[oo][1] = h01, gh[oo][2] = h11, ge[oo][0] = e0, ge[oo][1] = e1;
+                    gm[oo] = g.m, gs[oo] = s, gd[oo][0] = g.d0, gd[oo][1] = g.d1;
+                    gh[oo][0] = g.h00, gh[oo][1] = g.h01, gh[oo][2] = g.h11, ge[oo][0] = e0, ge[oo][1] = e1;
                 }
         }
 
-        // ---- A_t as the forward builds it ------------------------------------------------------------------------------------------
-        double dxi[2][NX];
-#pragma unroll
-        for (int c = 0; c < NX; ++c) {
-            dxi[0][c] = (c == SEL) ? 1.0 : 0.0;
-            dxi[1][c] = use_fb ? a.env.K[0][c] : 0.0;
-        }
-        double A[NX][NX];
-        if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
-            A[0][0] = 1.0, A[0][1] = a.env.dt;
-            A[1][0] = 0.0, A[1][1] = 1.0;
-#pragma unroll
-            for (int c = 0; c < NX; ++c) A[1][c] += gd[0][0] * dxi[0][c] + gd[0][1] * dxi[1][c];
-        } else {
-            const double v = x[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int c = 0; c < NX; ++c) {
-                    A[i][c] = ((i == c) ? 1.0 : 0.0) + v * (gd[i][0] * dxi[0][c] + gd[i][1] * dxi[1][c]);
-                    if (c == 3) A[i][c] += gm[i];
-                }
-#pragma unroll
-            for (int c = 0; c < NX; ++c) A[3][c] = ((c == 3) ? 1.0 : 0.0) + (use_fb ? a.env.dt * a.env.K[1][c] : 0.0);
-        }
+        double dxi[2][NX], A[NX][NX];                                  // d xi / d x and A_t
+        env_jacobian_ct<ENV>(a.env, x, gm, gd, dxi, A);
 
         // ---- Abar = 2 Lambda A P,  Pbar = A^T Lambda A (lower triangle) ----------------------------------------------------------------
         double Abar[NX][NX], Pbar[NX][NX];
@@ -371,7 +243,7 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
     }
 #undef MGV_LAM
 
-    const bool dead = !mgv_finite(chk);
+    const bool dead = !mom_finite(chk);
     if (dead) info_acc |= GPMPC_INFO_NONFINITE;
     if (!active) return;
     if (a.gx0) {
@@ -393,12 +265,12 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
 
 template <int ENV, int NRP, bool HG>
 __global__ __launch_bounds__(64) void moment_rollout_vjp_kernel(const MomentGradArgs a) {
-    constexpr int G_NY = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 3;
-    constexpr int TRI = mgv_col_ofs<NRP>(NRP);
+    constexpr int G_NY = EnvDims<ENV>::G_NY;
+    constexpr int TRI = mom_col_ofs<NRP>(NRP);
     __shared__ __attribute__((aligned(16))) double Ltri[G_NY * TRI];
     __shared__ double alpha_s[G_NY * NRP];
     __shared__ double xr_s[2 * NRP];
-    mgv_stage<NRP, G_NY>(a, Ltri, alpha_s, xr_s, threadIdx.x, blockDim.x);
+    mom_stage<NRP, G_NY>(a, Ltri, alpha_s, xr_s, threadIdx.x, blockDim.x);
     __syncthreads();
     const long braw = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = braw < a.B;
@@ -413,25 +285,6 @@ static int mgv_launch(const MomentGradArgs& a, hipStream_t st) {
     return GPMPC_OK;
 }
 
-template <int ENV>
-static int mgv_dispatch(const MomentGradArgs& a, hipStream_t st) {          // the instantiation set of moment_dispatch (moments.hip)
-    const int n = a.gp.n_r;
-    if (a.gp.real_has_grad) {
-        if (n <= 16) return mgv_launch<ENV, 16, true>(a, st);
-        if (n <= 32) return mgv_launch<ENV, 32, true>(a, st);
-        if (n <= 48) return mgv_launch<ENV, 48, true>(a, st);
-        return mgv_launch<ENV, 64, true>(a, st);
-    }
-    if (n <= 8) return mgv_launch<ENV, 8, false>(a, st);
-    if (n <= 16) return mgv_launch<ENV, 16, false>(a, st);
-    if (n <= 24) return mgv_launch<ENV, 24, false>(a, st);
-    if (n <= 32) return mgv_launch<ENV, 32, false>(a, st);
-    if (n <= 40) return mgv_launch<ENV, 40, false>(a, st);
-    if (n <= 48) return mgv_launch<ENV, 48, false>(a, st);
-    if (n <= 56) return mgv_launch<ENV, 56, false>(a, st);
-    return mgv_launch<ENV, 64, false>(a, st);
-}
-
 }  // namespace gpmpc
 
 using namespace gpmpc;
@@ -442,32 +295,10 @@ int gpmpc_moment_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
                              int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                              const double* M, const double* P, const double* gM, const double* gP, double* gx0, double* gU,
                              double* gP0, int32_t* info, void* stream) {
-    const std::string me = "gpmpc_moment_rollout_vjp: ";
-    if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
-    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
-    if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    if (B < 0 || H < 0) return fail(GPMPC_E_ARG, me + "B and H must be >= 0");
-    // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
-    if (B > 0 && (!plan || !X_r || !x0 || !M || !P || !info || (H > 0 && (!U || !gU))))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, x0, U, M, P, gU and info are required)");
-    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
-    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    const long n = (long)gp->N_r * (gp->real_has_grad ? gp->T : 1);
-    if (n > MGV_MAX_ROWS)
-        return fail(GPMPC_E_UNSUPPORTED, me + "more than 64 label rows (N_r value-only, N_r * T with real_has_grad) are not instantiated");
-    if (B > (int64_t)INT_MAX) return fail(GPMPC_E_UNSUPPORTED, me + "B must be < 2^31 (split the candidates over calls)");
+    if (int rc = mom_check_args("gpmpc_moment_rollout_vjp: ", gp, env, plan, X_r, B, H, x0, U, M, P, info, true, gU)) return rc;
     if (B == 0) return GPMPC_OK;
     MomentGradArgs a;
-    a.gp = make_gp_params(gp);
-    a.env = make_env_params(env);
-    a.plan = (const double*)plan;
-    a.X_r = X_r;
-    a.B = B;
-    a.H = H;
-    a.x0_per = x0_per_candidate != 0;
-    a.u_per = u_per_candidate != 0;
-    a.x0 = x0;
-    a.U = U;
+    mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
     a.M = M;
     a.P = P;
     a.gM = gM;
@@ -476,8 +307,9 @@ int gpmpc_moment_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
     a.gU = gU;
     a.gP0 = gP0;
     a.info = (int*)info;
-    if (env->env_id == GPMPC_ENV_PENDULUM1D) return mgv_dispatch<GPMPC_ENV_PENDULUM1D>(a, (hipStream_t)stream);
-    return mgv_dispatch<GPMPC_ENV_CAR_RESIDUAL>(a, (hipStream_t)stream);
+    return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
+        return mgv_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

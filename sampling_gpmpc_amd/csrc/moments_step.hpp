@@ -1,0 +1,294 @@
+// One step of the moment rollout, defined once: moment_rollout_kernel (moments.hip) runs it forwards, moment_rollout_vjp_kernel
+// (moments_grad.hip) rebuilds it from the stored mu_t, P_t and differentiates it.  The VJP's u_t, xi_t, GP mean / gradient /
+// variance, clamp decision and A_t are the forward's because both kernels call the functions below; so are the packed-triangle
+// layout, the staging, the instantiation set and the argument checks.  pathwise_rollout_kernel (pathwise.hip) takes the environment
+// facts and env_step_ct from here.  Everything is __host__ __device__ (the VJP's candidate body compiles for the host) or constexpr.
+#pragma once
+#include "gpmpc_host.hpp"
+
+#include <climits>
+#include <type_traits>
+
+namespace gpmpc {
+
+// ---------------------------------------------------------------------------------------------------------------
+// the environments at compile time (the run-time apply_feedback / gp_input / env_step of gpmpc_device.hpp serve the generic kernels)
+// ---------------------------------------------------------------------------------------------------------------
+template <int ENV>
+struct EnvDims {
+    static_assert(ENV == GPMPC_ENV_PENDULUM1D || ENV == GPMPC_ENV_CAR_RESIDUAL, "unknown environment");
+    static constexpr int NX = (ENV == GPMPC_ENV_PENDULUM1D) ? 2 : 4;
+    static constexpr int NU = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 2;
+    static constexpr int G_NY = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 3;
+    static constexpr int SEL = (ENV == GPMPC_ENV_PENDULUM1D) ? 0 : 2;   // the state the GP input reads: g_idx_inputs = [SEL, nx]
+};
+
+// the step's input u = -((x_goal - x) K^T) + u_ff (or u_ff), written as apply_feedback, and the GP input xi = (x[SEL], u[0])
+template <int ENV>
+__host__ __device__ __forceinline__ void env_input_ct(const EnvParams& e, const double (&x)[EnvDims<ENV>::NX], const double* u_ff,
+                                                      double (&u)[EnvDims<ENV>::NU], double (&xi)[2]) {
+#pragma unroll
+    for (int i = 0; i < EnvDims<ENV>::NU; ++i) {
+        const double ufi = u_ff[i];
+        if (e.use_feedback) {                                          // uniform
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < EnvDims<ENV>::NX; ++j) acc += (e.x_goal[j] - x[j]) * e.K[i][j];
+            u[i] = -acc + ufi;
+        } else {
+            u[i] = ufi;
+        }
+    }
+    xi[0] = x[EnvDims<ENV>::SEL];
+    xi[1] = u[0];
+}
+
+// x+ = f(x, u) + B_d(x) g, written as env_step: B_d = [0, 1]^T (pendulum), v I_{4x3} (car)
+template <int ENV>
+__host__ __device__ __forceinline__ void env_step_ct(const EnvParams& e, const double (&x)[EnvDims<ENV>::NX],
+                                                     const double (&u)[EnvDims<ENV>::NU], const double (&g)[EnvDims<ENV>::G_NY],
+                                                     double (&xn)[EnvDims<ENV>::NX]) {
+    if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
+        xn[0] = x[0] + x[1] * e.dt;
+        xn[1] = x[1] + g[0];
+    } else {
+        const double v = x[3];
+        xn[0] = x[0] + v * g[0];
+        xn[1] = x[1] + v * g[1];
+        xn[2] = x[2] + v * g[2];
+        xn[3] = (x[3] + u[1] * e.dt);
+    }
+}
+
+// the diagonal of B_d diag(s) B_d^T
+template <int ENV>
+__host__ __device__ __forceinline__ void env_noise_diag_ct(const double (&x)[EnvDims<ENV>::NX], const double (&gs)[EnvDims<ENV>::G_NY],
+                                                           double (&gdiag)[EnvDims<ENV>::NX]) {
+    if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
+        gdiag[0] = 0.0, gdiag[1] = gs[0];
+    } else {
+        const double v = x[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gdiag[i] = v * v * gs[i];
+        gdiag[3] = 0.0;
+    }
+}
+
+// d xi / d x and A_t, the Jacobian of x -> env_step(x, fb(x), m(xi(x, fb(x)))) at mu_t; gm / gd: the GP's mean and its gradient
+template <int ENV>
+__host__ __device__ __forceinline__ void env_jacobian_ct(const EnvParams& e, const double (&x)[EnvDims<ENV>::NX],
+                                                         const double (&gm)[EnvDims<ENV>::G_NY], const double (&gd)[EnvDims<ENV>::G_NY][2],
+                                                         double (&dxi)[2][EnvDims<ENV>::NX],
+                                                         double (&A)[EnvDims<ENV>::NX][EnvDims<ENV>::NX]) {
+    constexpr int NX = EnvDims<ENV>::NX;
+    const bool use_fb = e.use_feedback != 0;
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {
+        dxi[0][c] = (c == EnvDims<ENV>::SEL) ? 1.0 : 0.0;
+        dxi[1][c] = use_fb ? e.K[0][c] : 0.0;
+    }
+    if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
+        A[0][0] = 1.0, A[0][1] = e.dt;                                 // known part: theta + omega dt, omega
+        A[1][0] = 0.0, A[1][1] = 1.0;
+#pragma unroll
+        for (int c = 0; c < NX; ++c) A[1][c] += gd[0][0] * dxi[0][c] + gd[0][1] * dxi[1][c];   // B_d = [0, 1]^T
+    } else {
+        const double v = x[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < NX; ++c) {
+                A[i][c] = ((i == c) ? 1.0 : 0.0) + v * (gd[i][0] * dxi[0][c] + gd[i][1] * dxi[1][c]);   // B_d grad m
+                if (c == 3) A[i][c] += gm[i];                          // d B_d / d v . m, B_d = v I_{4x3}
+            }
+#pragma unroll
+        for (int c = 0; c < NX; ++c) A[3][c] = ((c == 3) ? 1.0 : 0.0) + (use_fb ? e.dt * e.K[1][c] : 0.0);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// arguments, the packed triangle and its staging
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int MOM_MAX_ROWS = 64;           // label rows n_r = N_r (value-only) or N_r * T (real_has_grad)
+
+typedef double double2_m __attribute__((ext_vector_type(2)));
+
+struct MomentStepArgs {                    // what the forward and the VJP share; MomentArgs / MomentGradArgs add their arrays
+    GpParams gp;
+    EnvParams env;
+    const double* plan;
+    const double* X_r;
+    long B;
+    int H, x0_per, u_per;
+    const double *x0, *U;
+};
+
+__host__ __device__ __forceinline__ bool mom_finite(double abs_sum) { return abs_sum < __builtin_inf(); }   // false for NaN and inf
+
+// packed lower triangle, column-major, every column start 16-byte aligned (NRP even): column j holds rows j..NRP-1
+template <int NRP>
+__host__ __device__ constexpr int mom_col_ofs(int j) {
+    static_assert(NRP % 2 == 0, "even row count: a column of odd length is padded by one entry");
+    return j * NRP - j * (j - 1) / 2 + j / 2;
+}
+
+// thread tid of nt fills its share of the three tables (LDS on the device): the zero-padded triangles of L_rr^-1, alpha, X_r
+// (the pad entry behind a column of odd length is never read: such a column's last row is read alone)
+template <int NRP, int G_NY>
+__host__ __device__ __forceinline__ void mom_stage(const MomentStepArgs& a, double* Ltri, double* alpha_s, double* xr_s, int tid, int nt) {
+    constexpr int TRI = mom_col_ofs<NRP>(NRP);
+    const GpParams& gp = a.gp;
+    const int n = gp.n_r;                                              // <= NRP (host)
+    for (int e = tid; e < G_NY * NRP * NRP; e += nt) {
+        const int o = e / (NRP * NRP), rem = e - o * NRP * NRP, j = rem / NRP, i = rem - j * NRP;
+        if (i >= j)
+            Ltri[o * TRI + mom_col_ofs<NRP>(j) + (i - j)] = (i < n) ? a.plan[o * gp.plan_stride + (long)n * n + (long)j * n + i] : 0.0;
+    }
+    for (int e = tid; e < G_NY * NRP; e += nt) {
+        const int o = e / NRP, i = e - o * NRP;
+        alpha_s[e] = (i < n) ? a.plan[o * gp.plan_stride + 2L * n * n + n + i] : 0.0;
+    }
+    for (int e = tid; e < 2 * NRP; e += nt) xr_s[e] = (e < 2 * gp.N_r) ? a.X_r[e] : 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the GP of one output at xi
+// ---------------------------------------------------------------------------------------------------------------
+// q and k of the test point against real point p (r = xi - x_p: the test point is the kernel's first argument)
+__host__ __device__ __forceinline__ void mom_kernel_point(const double (&xi)[2], const double* xr_s, int p, const double (&il)[2],
+                                                          double os, double (&q)[2], double& k) {
+    const double r0 = xi[0] - xr_s[2 * p], r1 = xi[1] - xr_s[2 * p + 1];
+    q[0] = r0 * il[0];
+    q[1] = r1 * il[1];
+    k = os * exp(-0.5 * (r0 * q[0] + r1 * q[1]));
+}
+
+// Length of the accumulator array acc = L^-1 k of the column loop: NRP, but never 16 or fewer.  The compiler turns a private
+// array of up to 16 elements into ONE vector value when it meets it indexed by constants - which is how acc arrives in the
+// kernels, mom_gp_pass1 being unrolled before it is inlined - and every update then copies the whole register tuple
+// (NRP = 16: 116 -> 138 VGPRs, 13 % more instructions).  A longer array is split into NRP scalars; the spare entries are never touched.
+template <int NRP>
+constexpr int MOM_ACC = NRP > 16 ? NRP : 17;
+
+struct MomGpSums {                         // label sums against alpha: the mean, its gradient and (HESS) its Hessian H00, H01, H11
+    double m = 0.0, d0 = 0.0, d1 = 0.0, h00 = 0.0, h01 = 0.0, h11 = 0.0;
+};
+
+// Pass 1, the column loop: for each label row j < n the kernel row k_j, the sums of g and acc += L^-1[:, j] k_j (acc: zero on
+// entry, L^-1 k on return; by reference, the VJP's second pass reads it).  Returns |L^-1 k|^2.
+//   LT: the output's packed triangle;  al: its alpha;  TR = 3 label rows per real point with derivative labels (HG), else 1
+template <int NRP, bool HG, bool HESS>
+__host__ __device__ __forceinline__ double mom_gp_pass1(const double* LT, const double* al, const double* xr_s, int n,
+                                                        const double (&il)[2], double os, const double (&xi)[2], double (&acc)[MOM_ACC<NRP>],
+                                                        MomGpSums& g) {
+    constexpr int TR = HG ? 3 : 1;
+    double k = 0.0, q[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < NRP; ++j) {
+        if (j < n) {                                                   // uniform
+            const int tb = j % TR;                                     // the label's task (compile time)
+            if (tb == 0) mom_kernel_point(xi, xr_s, j / TR, il, os, q, k);
+            const double kj = kern_entry<2>(q, k, il, 0, tb);          // value row of the test point
+            const double aj = al[j];
+            g.m = fma(kj, aj, g.m);
+            g.d0 = fma(kern_entry<2>(q, k, il, 1, tb), aj, g.d0);      // derivative rows of the test point
+            g.d1 = fma(kern_entry<2>(q, k, il, 2, tb), aj, g.d1);
+            if constexpr (HESS) {
+                g.h00 = fma(kern_entry_hess<2>(q, k, il, 0, 0, tb), aj, g.h00);
+                g.h01 = fma(kern_entry_hess<2>(q, k, il, 0, 1, tb), aj, g.h01);
+                g.h11 = fma(kern_entry_hess<2>(q, k, il, 1, 1, tb), aj, g.h11);
+            }
+            const double* col = LT + mom_col_ofs<NRP>(j);              // rows j.. of column j, 16-byte aligned
+#pragma unroll
+            for (int i = j; i + 1 < NRP; i += 2) {
+                const double2_m l = *reinterpret_cast<const double2_m*>(col + (i - j));
+                acc[i] = fma(l.x, kj, acc[i]);
+                acc[i + 1] = fma(l.y, kj, acc[i + 1]);
+            }
+            if ((NRP - j) & 1) acc[NRP - 1] = fma(col[NRP - 1 - j], kj, acc[NRP - 1]);
+            // at most one column of LDS loads in flight (rollout_indep.hip: otherwise the scheduler hoists hundreds of
+            // ds_read_b128 ahead of their FMAs and spills the accumulators); the same after every column of the VJP's pass 2
+            asm volatile("" ::: "memory");
+        }
+    }
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < NRP; ++i) ss = fma(acc[i], acc[i], ss);
+    return ss;
+}
+
+// s = outputscale - |L^-1 k|^2, raised to the floor; returns whether it was (NaN: not clamped, the candidate is non-finite)
+__host__ __device__ __forceinline__ bool mom_variance(const GpParams& gp, double os, double ss, double& s, int& info_acc) {
+    s = os - ss;
+    const bool clamped = s < gp.var_floor;
+    if (clamped) {
+        s = gp.var_floor;
+        info_acc |= GPMPC_INFO_VAR_CLAMPED;
+    }
+    return clamped;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host: the instantiation set, the argument block and the argument checks of the two entry points
+// ---------------------------------------------------------------------------------------------------------------
+// launch(env, nrp, hg) with integral constants: n_r rounded up to a multiple of 8 (16 with derivative labels)
+template <class Launch>
+int mom_dispatch(int env_id, int n, bool real_has_grad, Launch&& launch) {
+    auto rows = [&](auto env) {
+        using F = std::false_type;
+        using T = std::true_type;
+        if (real_has_grad) {
+            if (n <= 16) return launch(env, std::integral_constant<int, 16>{}, T{});
+            if (n <= 32) return launch(env, std::integral_constant<int, 32>{}, T{});
+            if (n <= 48) return launch(env, std::integral_constant<int, 48>{}, T{});
+            return launch(env, std::integral_constant<int, 64>{}, T{});
+        }
+        if (n <= 8) return launch(env, std::integral_constant<int, 8>{}, F{});
+        if (n <= 16) return launch(env, std::integral_constant<int, 16>{}, F{});
+        if (n <= 24) return launch(env, std::integral_constant<int, 24>{}, F{});
+        if (n <= 32) return launch(env, std::integral_constant<int, 32>{}, F{});
+        if (n <= 40) return launch(env, std::integral_constant<int, 40>{}, F{});
+        if (n <= 48) return launch(env, std::integral_constant<int, 48>{}, F{});
+        if (n <= 56) return launch(env, std::integral_constant<int, 56>{}, F{});
+        return launch(env, std::integral_constant<int, 64>{}, F{});
+    };
+    if (env_id == GPMPC_ENV_PENDULUM1D) return rows(std::integral_constant<int, GPMPC_ENV_PENDULUM1D>{});
+    return rows(std::integral_constant<int, GPMPC_ENV_CAR_RESIDUAL>{});
+}
+
+// The checks of gpmpc_moment_rollout and gpmpc_moment_rollout_vjp; `me` names the entry point in the message.  M and P are the
+// forward's outputs and the VJP's inputs; the VJP (need_gU) also requires gU when there are steps.
+inline int mom_check_args(const std::string& me, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan,
+                          const double* X_r, int64_t B, int32_t H, const double* x0, const double* U, const double* M, const double* P,
+                          const int32_t* info, bool need_gU, const double* gU) {
+    if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
+    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
+    if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    if (B < 0 || H < 0) return fail(GPMPC_E_ARG, me + "B and H must be >= 0");
+    // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
+    if (B > 0 && (!plan || !X_r || !x0 || !M || !P || !info || (H > 0 && (!U || (need_gU && !gU)))))
+        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, x0, U, M, P" + (need_gU ? ", gU" : "") + " and info are required)");
+    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
+    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    const long n = (long)gp->N_r * (gp->real_has_grad ? gp->T : 1);      // in 64 bits: N_r is the caller's
+    if (n > MOM_MAX_ROWS)
+        return fail(GPMPC_E_UNSUPPORTED, me + "more than 64 label rows (N_r value-only, N_r * T with real_has_grad) are not instantiated");
+    if (B > (int64_t)INT_MAX) return fail(GPMPC_E_UNSUPPORTED, me + "B must be < 2^31 (split the candidates over calls)");
+    return GPMPC_OK;
+}
+
+inline void mom_fill_args(MomentStepArgs& a, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                          int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate) {
+    a.gp = make_gp_params(gp);
+    a.env = make_env_params(env);
+    a.plan = (const double*)plan;
+    a.X_r = X_r;
+    a.B = B;
+    a.H = H;
+    a.x0_per = x0_per_candidate != 0;
+    a.u_per = u_per_candidate != 0;
+    a.x0 = x0;
+    a.U = U;
+}
+
+}  // namespace gpmpc

@@ -15,7 +15,7 @@
 // instantiation, so the rollout's Y is bit-equal to an evaluation at the rollout's own point.
 // The fit forms r = y - g(X_r) - sqrt(noise) e with pw_prior_lane at the training points, applies L_rr^-1 twice from LDS in the order
 // gpmpc_plan_build forms alpha_r, and refines once against the plan's factor L_rr.  Four samples share a workgroup's copy of both.
-#include "gpmpc_host.hpp"
+#include "moments_step.hpp"
 
 #include <climits>
 #include <cmath>
@@ -269,9 +269,7 @@ struct PwRollArgs {
 
 template <int ENV>
 __global__ __launch_bounds__(256) void pathwise_rollout_kernel(const PwRollArgs a) {
-    constexpr int NX = (ENV == GPMPC_ENV_PENDULUM1D) ? 2 : 4;
-    constexpr int NU = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 2;
-    constexpr int G_NY = (ENV == GPMPC_ENV_PENDULUM1D) ? 1 : 3;
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
     constexpr int D = 2;
     const GpParams& gp = a.gp;
     const int n = gp.N_r, F = a.M / 2, stride_o = a.M + n, H = a.H;
@@ -312,10 +310,12 @@ __global__ __launch_bounds__(256) void pathwise_rollout_kernel(const PwRollArgs 
         store_state(t);
         double u[NU], xi[D], xn[NX];
         bool fin = true;
+        // the step input, written as env_input_ct (moments_step.hpp) and not a call of it: called, its loads of the feedback gain
+        // and goal move in front of the step loop and are spilled to VGPR lanes (pendulum1D: +47 instructions, +3 % per rollout, measured)
 #pragma unroll
         for (int i = 0; i < NU; ++i) {
             const double ufi = a.U[((a.u_per ? s * H : 0) + t) * NU + i];
-            if (a.env.use_feedback) {                                   // uniform; written as apply_feedback (gpmpc_device.hpp)
+            if (a.env.use_feedback) {                                   // uniform
                 double acc = 0.0;
 #pragma unroll
                 for (int j = 0; j < NX; ++j) acc += (a.env.x_goal[j] - x[j]) * a.env.K[i][j];
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void pathwise_rollout_kernel(const PwRollArgs 
             }
             fin = fin && pw_finite(u[i]);
         }
-        xi[0] = (ENV == GPMPC_ENV_PENDULUM1D) ? x[0] : x[2];            // gp_input
+        xi[0] = x[EnvDims<ENV>::SEL];
         xi[1] = u[0];
         double g[G_NY], gg[G_NY][D];
 #pragma unroll
@@ -334,16 +334,7 @@ __global__ __launch_bounds__(256) void pathwise_rollout_kernel(const PwRollArgs 
                                    gp.inv_l2[o], has_row, xr, vn[o], xi, g[o], gg[o]);
             fin = fin && pw_finite(g[o]) && pw_finite(gg[o][0]) && pw_finite(gg[o][1]);
         }
-        if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {                    // env_step (gpmpc_device.hpp)
-            xn[0] = x[0] + x[1] * a.env.dt;
-            xn[1] = x[1] + g[0];
-        } else {
-            const double v = x[3];
-            xn[0] = x[0] + v * g[0];
-            xn[1] = x[1] + v * g[1];
-            xn[2] = x[2] + v * g[2];
-            xn[3] = (x[3] + u[1] * a.env.dt);
-        }
+        env_step_ct<ENV>(a.env, x, u, g, xn);
 #pragma unroll
         for (int d = 0; d < NX; ++d) fin = fin && pw_finite(xn[d]);
         if (!dead && !fin) {

@@ -41,7 +41,7 @@ def test_header_carries_the_declaration_the_citations_and_the_limits():
         assert cite in doc, cite
     for text in ("at most 64 label rows", "ABI version stays 12", "exactly symmetric", "B == 0: nothing is launched"):
         assert text in doc, text
-    src = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "moments.hip")).read()
+    src = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "moments_step.hpp")).read()
     assert "MOM_MAX_ROWS = 64" in src
     build = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "build.py")).read()
     assert '"moments.hip"' in build
