@@ -850,6 +850,66 @@ int     gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t
                                double* X_traj /* (Ns, nx, H+1) */, double* Y /* (Ns, g_ny, H, 1+D) or NULL */, int32_t* info,
                                void* stream);
 
+/*
+ * gpmpc_pathwise_tube_stats (ABI 12) - statistics of the tube of Ns pathwise samples WITHOUT the tube: per stage and state dimension
+ * the largest deviation from a centre trajectory, the sample that attains it and the box of the samples; per sample the scaled
+ * sup-norm deviation over the horizon, and how many samples stay within eps.  Normals, update vectors and trajectories of a sample
+ * exist only inside the kernel: what leaves the device is (H+1) nx numbers per output, the counts, and 8 bytes per sample when sup
+ * is asked for.  Additive entry points: the ABI version stays 12.
+ * Replaces: the sample-based constraint tightening of reference extra/approx_sampling_mpc/src/solver.py:77-135
+ * (compute_approx_tightening: draw num_samples_tightening weight samples - agent.py:850-870 -, roll every sample and the mean model
+ * out under the optimised inputs, tilde_eps[t, d] = max_i |x^i_{t,d} - xbar_{t,d}|, shape (H+1, nx)) - that is dev_max - and the
+ * trajectory-level form of the small-ball question of gpmpc_sup_deviation (how many sampled trajectories stay within eps of the
+ * centre over the whole horizon) at 10^5 .. 10^7 samples.
+ *
+ * The contract.  Sample s < Ns is the pathwise sample of GLOBAL id offset + s: its normals are the entries e < V = g_ny (M + N_r) of the
+ * counter stream, exactly what gpmpc_base_samples(seed, 1, 1, offset, Ns, V, beta = +inf, ...) writes; its update vectors are those of
+ * gpmpc_pathwise_fit; its trajectory is that of gpmpc_pathwise_rollout with x0 and U shared by the samples.
+ * Bit-equality with the unfused path: the trajectory of sample s inside the kernel has the bits of gpmpc_base_samples ->
+ * gpmpc_pathwise_fit -> gpmpc_pathwise_rollout (the kernels call the same device functions for the fit of an output and for the
+ * step), so every output equals the reduction of that tube bit for bit.
+ *   plan, X_r, Y_r, M, omega   as gpmpc_pathwise_fit
+ *   seed, offset >= 0, Ns      the stream and the range of global ids
+ *   x0     [dev] (nx);  U [dev] (H, nu) (may be NULL when H == 0)
+ *   centre [dev] (nx, H+1)     the layout of one sample of X_traj (the caller's xbar: e.g. the rollout of the Z = 0 sample)
+ *   scale  [HOST] (nx) > 0 or NULL = 1;  eps [HOST] (n_eps) >= 0 or NULL, n_eps <= 16
+ *   dev_max [dev] (H+1, nx) out: max_s |x^s_{t,d} - centre[d][t]|, t = 0..H
+ *   dev_arg [dev] (H+1, nx) int64 out or NULL: the LOWEST global id (offset + s) that attains the maximum
+ *   box_lo, box_hi [dev] (H+1, nx) out or NULL: min_s / max_s of x^s_{t,d}
+ *   sup     [dev] (Ns) out or NULL: max_{t,d} |x^s_{t,d} - centre[d][t]| / scale[d]
+ *   n_within [dev] (n_eps) int64 out or NULL: the number of samples with sup[s] <= eps[j]
+ *   n_nonfinite [dev] (1) int64 out: the number of samples that carry GPMPC_INFO_NONFINITE under the rules of gpmpc_pathwise_rollout
+ *   max_groups   the kernel runs PERSISTENT waves on a grid of at most max_groups workgroups of four waves (<= 0: the library chooses,
+ *                512; at most 4096): wave w walks the samples w, w + n_waves, ... and keeps running results for its own samples
+ *   workspace [dev], workspace_bytes >= gpmpc_pathwise_tube_stats_workspace_bytes(gp, M, H, nx, n_eps, max_groups) with the same
+ *                max_groups: a row of V normals and a record of 4 (H+1) nx entries per wave - proportional to the grid, not to Ns.
+ *                No memory proportional to Ns is used apart from sup, and only when sup is asked for.
+ * Non-finite rule: a non-finite state is never ignored.  From the first stage at which a sample's state is not finite, dev_max is
+ * +inf, box_lo -inf and box_hi +inf at every (t, d) of that stage and of all later stages, dev_arg is the lowest such id, and the
+ * sample's sup is +inf (it is within no threshold).  A non-finite entry of scale or eps (host arrays) is GPMPC_E_ARG; a non-finite
+ * entry of centre (a device array: not read on the host) makes dev_max +inf at its (t, d) and every sample's sup +inf.
+ * Reproducibility: every output is a maximum, a minimum, a lowest id or an integer count over per-sample values that depend on (seed,
+ * global id) alone, combined per wave and then by a finishing kernel - no atomics - so all outputs are bit-identical for any
+ * max_groups, and a run cut into calls with different offset merges to the same bits (max, min, sum; on a tie the lower id).
+ * Limits (the contract): those of gpmpc_pathwise_rollout - real_has_grad == 0; N_r <= 64; M a multiple of 128 and at most 1024;
+ * Ns < 2^31; D = 2 and the two environments.  GPMPC_E_UNSUPPORTED beyond, before any device work.  GPMPC_E_ARG (before any device
+ * work): NULL gp or env; a bad gp descriptor; Ns, H, offset or n_eps < 0; n_eps > 16; M < 2 or odd; eps NULL with n_eps > 0; env.nx /
+ * env.nu / g_ny that do not belong to env.env_id; workspace_bytes below the size function's value; with Ns > 0 a NULL array other
+ * than the optional outputs (U only when H > 0).  Ns == 0: nothing is launched, and the array pointers are not looked at.
+ * No hidden allocation, no host round trip, everything goes to `stream`.
+ */
+size_t  gpmpc_pathwise_tube_stats_workspace_bytes(const gpmpc_gp_desc_t* gp, int32_t M, int32_t H, int32_t nx, int32_t n_eps,
+                                                  int32_t max_groups);
+int     gpmpc_pathwise_tube_stats(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                  const double* Y_r, int32_t M, const double* omega, uint64_t seed, int64_t offset, int64_t Ns,
+                                  int32_t H, const double* x0 /* (nx) */, const double* U /* (H, nu) */,
+                                  const double* centre /* (nx, H+1) */, const double* scale /* host (nx) or NULL */, int32_t n_eps,
+                                  const double* eps /* host (n_eps) or NULL */, double* dev_max /* (H+1, nx) */,
+                                  int64_t* dev_arg /* (H+1, nx) or NULL */, double* box_lo, double* box_hi /* (H+1, nx) or NULL */,
+                                  double* sup /* (Ns) or NULL */, int64_t* n_within /* (n_eps) or NULL */,
+                                  int64_t* n_nonfinite /* (1) */, int32_t max_groups, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, sol
 # the wrapper tube_rows.tube_rows is not re-exported: the name is the module's
 from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
-from .pathwise import PathwiseSamples, draw_omega, rff_kernel_error  # noqa: F401
+from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats, pathwise_tube_stats, merge_tube_stats,  # noqa: F401
+                       tube_stats_of)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
@@ -28,4 +29,5 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "restarts", "rkhs_norm_and_beta", "MomentTube", "moment_rollout", "moment_rollout_plan", "moment_rollout_vjp", "moment_rollout_vjp_plan",
            "chance_constraint_penalty", "plan_inputs", "plan_inputs_plan", "TubeQP", "TubeQPResult",
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
-           "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error"]
+           "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error",
+           "TubeStats", "pathwise_tube_stats", "merge_tube_stats", "tube_stats_of"]

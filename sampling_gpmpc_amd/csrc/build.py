@@ -14,11 +14,12 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "rollout_one.hip", "rollout_indep.hip", "joint.hip",
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
-           "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip"]
+           "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
+           "pathwise_stats.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce
-HEADERS = ["gpmpc_device.hpp", "gpmpc_host.hpp", "rollout_args.hpp", "rollout_plan.hpp", "joint_args.hpp", "joint_eigh.hpp", "joint_plan.hpp", "hull_geom.hpp", "base_stream.hpp", "moments_step.hpp",
+HEADERS = ["gpmpc_device.hpp", "gpmpc_host.hpp", "rollout_args.hpp", "rollout_plan.hpp", "joint_args.hpp", "joint_eigh.hpp", "joint_plan.hpp", "hull_geom.hpp", "base_stream.hpp", "moments_step.hpp", "pathwise_step.hpp",
            "rollout_one_gen.inc", "rollout_tiles_mfma.inc", "joint_mfma_gen.inc",
            os.path.join(REPO, "include", "gpmpc_hip.h")]
 GENERATED = {"rollout_one_gen.inc": os.path.join(REPO, "tools", "gen_rollout_one.py"),
@@ -51,7 +52,10 @@ EXTRA_FLAGS = {"rollout_fast.hip": os.environ.get("GPMPC_FAST_FLAGS", "-mllvm -d
                # write in 13 of the blocks)
                "rollout_one.hip": os.environ.get("GPMPC_ONE_FLAGS", "-mllvm -disable-machine-licm -mllvm -amdgpu-load-store-vectorizer=0").split(),
                "rollout_indep.hip": os.environ.get("GPMPC_INDEP_FLAGS", "").split(),
-               "joint_mfma.hip": os.environ.get("GPMPC_JOINT_MFMA_FLAGS", "").split()}
+               "joint_mfma.hip": os.environ.get("GPMPC_JOINT_MFMA_FLAGS", "").split(),
+               # the fused pathwise kernel: with machine-LICM the invariants of the sample loop are hoisted over the fit and the
+               # rollout (222 / 265 registers, the car at one wave per SIMD); without it 157 / 201 VGPRs, two waves per SIMD
+               "pathwise_stats.hip": os.environ.get("GPMPC_PATHWISE_STATS_FLAGS", "-mllvm -disable-machine-licm").split()}
 
 
 STAMP = os.path.join(OBJDIR, "flags.stamp")

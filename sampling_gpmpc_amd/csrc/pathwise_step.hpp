@@ -1,0 +1,244 @@
+// The device code of the pathwise GP samples that more than one kernel runs, defined once: the evaluation of a sample at a point, the
+// fit of one output's update vector and one step of the rollout.  pathwise_fit_kernel / pathwise_eval_kernel / pathwise_rollout_kernel
+// (pathwise.hip) and pathwise_tube_stats_kernel (pathwise_stats.hip) call the functions below, so the fused kernel's update vectors
+// and trajectories have the bits of the unfused path by construction.  The limits and the argument checks the entry points share
+// live here too.
+#pragma once
+#include "moments_step.hpp"
+
+#include <climits>
+#include <cmath>
+
+namespace gpmpc {
+
+constexpr int PW_MAX_ROWS = 64;            // N_r: one training row per lane
+constexpr int PW_M_STEP = 128;             // M is a multiple of 128: every lane owns M / 128 (cos, sin) pairs
+constexpr int PW_MAX_M = 1024;
+constexpr int PW_LS = PW_MAX_ROWS + 1;     // LDS row stride of L_rr^-1 (odd: row-wise and column-wise reads are both conflict-free)
+
+__device__ __forceinline__ bool pw_finite(double v) { return fabs(v) < __builtin_inf(); }   // false for NaN and inf
+
+// the lane's share of the UNSCALED prior sample and of its gradient at xi: frequencies lane, lane + 64, ...
+//   om [F][D]: the output's frequencies;  zw [M]: the sample's feature weights of the output (w_2f with cos, w_2f+1 with sin)
+template <int D, bool GRAD>
+__device__ __forceinline__ void pw_prior_lane(const double* __restrict__ om, const double* __restrict__ zw, int F, int lane,
+                                              const double (&xi)[D], double& v, double (&g)[D]) {
+    v = 0.0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) g[d] = 0.0;
+#pragma unroll 2
+    for (int f = lane; f < F; f += kWave) {
+        double w[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) w[d] = om[(long)f * D + d];
+        const double wc = zw[2 * f], ws = zw[2 * f + 1];
+        double ang = w[0] * xi[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) ang = fma(w[d], xi[d], ang);
+        double sn, cs;
+        sincos(ang, &sn, &cs);
+        v = fma(wc, cs, v);
+        v = fma(ws, sn, v);
+        if (GRAD) {
+            const double t = fma(ws, cs, -(wc * sn));
+#pragma unroll
+            for (int d = 0; d < D; ++d) g[d] = fma(w[d], t, g[d]);
+        }
+    }
+}
+
+// The posterior sample and its gradient at xi (uniform over the wave), returned to every lane.
+//   scale = sqrt(os / F);  has_row: this lane owns training row xr with update weight vn
+template <int D, bool GRAD>
+__device__ __forceinline__ void pw_eval_point(const double* __restrict__ om, const double* __restrict__ zw, int F, int lane,
+                                              double scale, double os, const double* inv_l2, bool has_row, const double (&xr)[D],
+                                              double vn, const double (&xi)[D], double& val, double (&grad)[D]) {
+    double v, g[D];
+    pw_prior_lane<D, GRAD>(om, zw, F, lane, xi, v, g);
+    v *= scale;
+#pragma unroll
+    for (int d = 0; d < D; ++d) g[d] *= scale;
+    if (has_row) {
+        double q[D];                                                   // r = xi - X_n: the test point is the kernel's first argument
+        const double kv = kern_scalar<D>(xi, xr, inv_l2, os, q) * vn;
+        v += kv;
+        if (GRAD) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) g[d] = fma(-kv, q[d], g[d]);    // derivative row d of the test point: -k q_d
+        }
+    }
+    val = wave_sum(v);
+#pragma unroll
+    for (int d = 0; d < D; ++d) grad[d] = GRAD ? wave_sum(g[d]) : 0.0;
+}
+
+// every entry of a sample's row of n doubles is finite (wave-uniform answer)
+__device__ __forceinline__ bool pw_row_finite(const double* __restrict__ row, long n, int lane) {
+    bool ok = true;
+    for (long e = lane; e < n; e += kWave) ok = ok && pw_finite(row[e]);
+    return __all(ok);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fit: one output's update vector of one sample per wave; four waves share the workgroup's copy of the two triangles
+// ---------------------------------------------------------------------------------------------------------------------
+struct PwFitLds {
+    double Li[PW_MAX_ROWS * PW_LS];                                     // Li[j * PW_LS + i] = L^-1[i][j]
+    double L[PW_MAX_ROWS * PW_LS];                                      // L[i * PW_LS + k] = L[i][k]
+    double a[4][PW_MAX_ROWS], b[4][PW_MAX_ROWS];                        // a wave's two vectors (no other wave touches its row)
+};
+
+// stage output o's L_rr and L_rr^-T of the plan (all threads of the workgroup; the caller's barriers order it against the reads)
+__device__ __forceinline__ void pw_fit_stage(PwFitLds& lds, const GpParams& gp, const double* __restrict__ plan, int o) {
+    const int n = gp.N_r;
+    const double* L = plan + o * gp.plan_stride;
+    const double* LinvT = L + (long)n * n;
+    for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
+        const int j = e / n, i = e - j * n;
+        lds.Li[j * PW_LS + i] = LinvT[e];
+        lds.L[j * PW_LS + i] = L[e];
+    }
+}
+
+// The update weight of this lane's training row (lanes >= N_r: unused) for output o of the sample whose normals of the output are zw
+// [M + N_r]: r = y - g(X_r) - sqrt(noise) e, v = (K + Sigma)^-1 r through the staged triangles and one step of refinement.  Holds
+// workgroup barriers: all four waves call it together, right after pw_fit_stage (its first barrier also covers the staging).
+template <int D>
+__device__ __forceinline__ double pw_fit_output(PwFitLds& lds, const GpParams& gp, int o, const double* X_r,
+                                                const double* Y_r, const double* om, const double* zw, int M, int wave,
+                                                int lane) {
+    const int n = gp.N_r, F = M / 2;
+    const bool has_row = lane < n;
+    const int row = has_row ? lane : n - 1;
+    const double sd_noise = sqrt(gp.noise[0]);
+
+    // (K + Sigma)^-1 rhs = L^-T (L^-1 rhs) for this wave's vector, one row per lane, in the order gpmpc_plan_build forms alpha_r
+    auto apply_inverse = [&](double rhs) {
+        lds.a[wave][lane] = has_row ? rhs : 0.0;
+        __syncthreads();
+        double w = 0.0;                                                 // w = L^-1 rhs, row `lane`, columns in ascending order
+        for (int j = 0; j < n; ++j) {
+            const double l = lds.Li[j * PW_LS + row];
+            if (j <= lane) w = fma(l, lds.a[wave][j], w);
+        }
+        lds.b[wave][lane] = has_row ? w : 0.0;
+        __syncthreads();
+        double v = 0.0;                                                 // v = L^-T w, row `lane`
+        for (int i = 0; i < n; ++i) {
+            const double l = lds.Li[row * PW_LS + i];
+            if (i >= lane) v = fma(l, lds.b[wave][i], v);
+        }
+        __syncthreads();                                                // a / b may be written again
+        return v;
+    };
+
+    const double scale = sqrt(gp.os[o] / (double)F);
+    double g_own = 0.0;                                                 // the prior sample at this lane's training row
+#pragma unroll 1
+    for (int p = 0; p < n; ++p) {
+        double xi[D], v, g[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) xi[d] = X_r[(long)p * D + d];
+        pw_prior_lane<D, false>(om, zw, F, lane, xi, v, g);
+        const double tot = wave_sum(v * scale);
+        if (lane == p) g_own = tot;
+    }
+    const double y = Y_r[((long)o * n + row) * gp.T];
+    const double r = (y - g_own) - sd_noise * zw[M + row];
+    double v = apply_inverse(r);                                        // (the barrier inside also covers the staging)
+    // One step of iterative refinement against the plan's own factor: rho = r - L (L^T v), v += (K + Sigma)^-1 rho.  Applying
+    // the explicit inverse is not backward stable: its residual is ~cond(L) times that of a triangular solve, and the
+    // prediction k(xi, X)^T v sees the residual, not the forward error of v (measured: the value's error 7 x that of Cholesky
+    // solves without this step, level with them after it; a second step changes nothing).
+    lds.a[wave][lane] = has_row ? v : 0.0;
+    __syncthreads();
+    double t = 0.0;                                                     // t = L^T v, row `lane`
+    for (int i = 0; i < n; ++i) {
+        const double l = lds.L[i * PW_LS + row];
+        if (i >= lane) t = fma(l, lds.a[wave][i], t);
+    }
+    lds.b[wave][lane] = has_row ? t : 0.0;
+    __syncthreads();
+    double rho = r;                                                     // rho = r - L t
+    for (int k = 0; k < n; ++k) {
+        const double l = lds.L[row * PW_LS + k];
+        if (k <= lane) rho = fma(-l, lds.b[wave][k], rho);
+    }
+    __syncthreads();
+    v += apply_inverse(rho);
+    return v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rollout: one step of one sample (uniform over its wave)
+// ---------------------------------------------------------------------------------------------------------------------
+// x_t -> x_t+1 under the step's feed-forward input ut [NU]: the sample's value g and gradient gg at (x_t[SEL], u_t[0]) for every
+// output, then the environment step.  When the input or anything computed is not finite the sample dies: `dead` is set, `info`
+// takes GPMPC_INFO_NONFINITE and x is NaN from here on.  zrow: the sample's normals, vn: its update weights at this lane's row.
+template <int ENV>
+__device__ __forceinline__ void pw_rollout_step(const GpParams& gp, const EnvParams& env, const double* omega, const double* zrow, int F,
+                                                int stride_o, int lane, bool has_row, const double (&xr)[2],
+                                                const double (&vn)[EnvDims<ENV>::G_NY], const double* ut,
+                                                double (&x)[EnvDims<ENV>::NX], bool& dead, int& info,
+                                                double (&g)[EnvDims<ENV>::G_NY], double (&gg)[EnvDims<ENV>::G_NY][2]) {
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
+    constexpr int D = 2;
+    const double nan = __builtin_nan("");
+    double u[NU], xi[D], xn[NX];
+    bool fin = true;
+    // the step input, written as env_input_ct (moments_step.hpp) and not a call of it: called, its loads of the feedback gain
+    // and goal move in front of the step loop and are spilled to VGPR lanes (pendulum1D: +47 instructions, +3 % per rollout, measured)
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        const double ufi = ut[i];
+        if (env.use_feedback) {                                         // uniform
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) acc += (env.x_goal[j] - x[j]) * env.K[i][j];
+            u[i] = -acc + ufi;
+        } else {
+            u[i] = ufi;
+        }
+        fin = fin && pw_finite(u[i]);
+    }
+    xi[0] = x[EnvDims<ENV>::SEL];
+    xi[1] = u[0];
+#pragma unroll
+    for (int o = 0; o < G_NY; ++o) {
+        pw_eval_point<D, true>(omega + (long)o * F * D, zrow + (long)o * stride_o, F, lane, sqrt(gp.os[o] / (double)F), gp.os[o],
+                               gp.inv_l2[o], has_row, xr, vn[o], xi, g[o], gg[o]);
+        fin = fin && pw_finite(g[o]) && pw_finite(gg[o][0]) && pw_finite(gg[o][1]);
+    }
+    env_step_ct<ENV>(env, x, u, g, xn);
+#pragma unroll
+    for (int d = 0; d < NX; ++d) fin = fin && pw_finite(xn[d]);
+    if (!dead && !fin) {
+        dead = true;
+        info |= GPMPC_INFO_NONFINITE;
+    }
+#pragma unroll
+    for (int d = 0; d < NX; ++d) x[d] = dead ? nan : xn[d];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host: the checks the entry points share; `me` names the entry point in the message
+// ---------------------------------------------------------------------------------------------------------------------
+inline int pw_check(const std::string& me, const gpmpc_gp_desc_t* gp, int32_t M, int64_t Ns, int64_t ldz) {
+    if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
+    if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    if (Ns < 0) return fail(GPMPC_E_ARG, me + "Ns must be >= 0");
+    if (M < 2 || (M & 1)) return fail(GPMPC_E_ARG, me + "M must be an even number of features >= 2");
+    if (ldz < (int64_t)gp->g_ny * ((int64_t)M + gp->N_r))
+        return fail(GPMPC_E_ARG, me + "ldz must be >= g_ny * (M + N_r)");
+    return GPMPC_OK;
+}
+
+inline int pw_supported(const std::string& me, const gpmpc_gp_desc_t* gp, int32_t M, int64_t Ns) {
+    if (gp->real_has_grad) return fail(GPMPC_E_UNSUPPORTED, me + "real_has_grad = 1 is not instantiated (value-only real data)");
+    if (gp->N_r > PW_MAX_ROWS) return fail(GPMPC_E_UNSUPPORTED, me + "more than 64 training rows (N_r) are not instantiated");
+    if (M % PW_M_STEP != 0 || M > PW_MAX_M) return fail(GPMPC_E_UNSUPPORTED, me + "M must be a multiple of 128 and at most 1024");
+    if (Ns > (int64_t)INT_MAX) return fail(GPMPC_E_UNSUPPORTED, me + "Ns must be < 2^31 (split the samples over calls)");
+    return GPMPC_OK;
+}
+
+}  // namespace gpmpc

@@ -448,3 +448,32 @@ def all_reduce_small_ball(result, group=None):
             out[name] = packed[at:at + t.numel()].reshape(t.shape).to(t.dtype)
             at += t.numel()
     return dataclasses.replace(result, Ns=int(packed[0].item()), **out)
+
+
+def all_reduce_tube_stats(stats, group=None):
+    """The ``pathwise.TubeStats`` of a run whose global sample ids are spread over the ranks (each rank called ``pathwise_tube_stats``
+    with its own ``offset`` slice): what ``merge_tube_stats`` of the ranks' parts gives, on every rank - ``dev_max`` / ``box_hi`` by
+    MAX, ``box_lo`` by MIN, ``dev_arg`` the lowest id among the ranks that attain the maximum, ``Ns`` and the counts by SUM.  Packed as
+    ``all_reduce_small_ball`` packs (one float64 vector, one int64 vector per operation); ``sup`` stays local.  Every rank must have
+    used the same thresholds.  Works on the tensors' own device (CPU tensors under gloo)."""
+    import dataclasses
+    E = stats.dev_max.numel()
+    dev = stats.dev_max.device
+    packed = torch.cat([stats.dev_max.reshape(-1), stats.box_hi.reshape(-1), -stats.box_lo.reshape(-1)])
+    dist.all_reduce(packed, op=dist.ReduceOp.MAX, group=group)
+    dev_max = packed[:E].reshape(stats.dev_max.shape)
+    no_id = torch.iinfo(torch.int64).max
+    arg = torch.where(stats.dev_max == dev_max, stats.dev_arg, torch.full_like(stats.dev_arg, no_id)).reshape(-1)
+    arg = torch.cat([arg, torch.tensor([int(stats.offset)], dtype=torch.int64, device=dev)])
+    dist.all_reduce(arg, op=dist.ReduceOp.MIN, group=group)
+    counts = [torch.tensor([int(stats.Ns)], dtype=torch.int64, device=dev), stats.n_nonfinite.reshape(-1).to(torch.int64)]
+    if stats.n_within is not None:
+        counts.append(stats.n_within.reshape(-1).to(torch.int64))
+    counts = torch.cat(counts)
+    dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=group)
+    _lib.host_wait(counts)
+    return dataclasses.replace(
+        stats, Ns=int(counts[0].item()), offset=int(arg[E].item()), dev_max=dev_max, dev_arg=arg[:E].reshape(stats.dev_arg.shape),
+        box_hi=packed[E:2 * E].reshape(stats.box_hi.shape), box_lo=-packed[2 * E:].reshape(stats.box_lo.shape),
+        n_nonfinite=counts[1:2].reshape(stats.n_nonfinite.shape),
+        n_within=None if stats.n_within is None else counts[2:].reshape(stats.n_within.shape))

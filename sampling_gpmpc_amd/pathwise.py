@@ -9,11 +9,19 @@ value and gradients as feature sums (``get_dynamics_grad``); this is the GP form
 
 ``PathwiseSamples.draw`` draws the frequencies on the CPU, the normals with ``gpmpc_base_samples`` (one row per GLOBAL sample id) and
 calls ``gpmpc_pathwise_fit``; ``.evaluate`` / ``.rollout`` are one launch each.  ``rff_kernel_error`` checks a frequency draw.
+
+``pathwise_tube_stats`` answers what the tube of 10^5 .. 10^7 such samples looks like - the sample-based constraint tightening of the
+reference's ``extra/approx_sampling_mpc/src/solver.py:77-135`` (``compute_approx_tightening``) and the trajectory-level small-ball
+count - in one launch of ``gpmpc_pathwise_tube_stats`` that stores neither the normals nor the tube; ``merge_tube_stats`` combines the
+results of disjoint id ranges.
 """
 from __future__ import annotations
 
+import ctypes as C
+import dataclasses
 import math
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import torch
 
@@ -21,6 +29,7 @@ from . import _lib
 
 F64 = torch.float64
 M_STEP, MAX_M, MAX_ROWS = 128, 1024, 64          # include/gpmpc_hip.h, gpmpc_pathwise_*: the limits
+MAX_EPS = 16                                     # gpmpc_pathwise_tube_stats: n_eps
 
 
 def draw_omega(ell, n_features: int, seed: int) -> torch.Tensor:
@@ -220,3 +229,148 @@ def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
         grad = grad - torch.einsum("sn,mn,mnd->smd", v, k, q)
         outs.append(torch.cat([val[..., None], grad], dim=-1))
     return torch.stack(outs, dim=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# statistics of the tube without the tube
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class TubeStats:
+    """Result of ``pathwise_tube_stats`` for the global sample ids ``offset .. offset + Ns`` (after ``merge_tube_stats``: ``Ns`` samples
+    in all, ``offset`` the lowest id).  ``dev_max``, ``box_lo``, ``box_hi (H+1, nx)`` float64 and ``dev_arg (H+1, nx)`` int64: the largest
+    deviation from the centre per stage and dimension, the lowest global id that attains it, and the box of the samples;
+    ``sup (Ns)`` the per-sample scaled sup-norm deviation (``None`` unless asked for); ``n_within (n_eps)`` int64 the number of samples
+    with ``sup <= eps[j]`` (``None`` without thresholds); ``n_nonfinite (1)`` int64.  Tensors live on the device of the run."""
+    Ns: int
+    offset: int
+    dev_max: torch.Tensor
+    dev_arg: torch.Tensor
+    box_lo: torch.Tensor
+    box_hi: torch.Tensor
+    sup: Optional[torch.Tensor]
+    eps: tuple
+    n_within: Optional[torch.Tensor]
+    n_nonfinite: torch.Tensor
+
+    def tightening(self) -> torch.Tensor:
+        """``dev_max``: the reference's ``tilde_eps (H+1, nx)`` (``solver.py:77-135``)."""
+        return self.dev_max
+
+    def probability(self) -> Optional[torch.Tensor]:
+        """``n_within / Ns`` per threshold (float64, on the counts' device)."""
+        return None if self.n_within is None else self.n_within.to(F64) / float(self.Ns)
+
+
+def pathwise_tube_stats(agent_or_plan, x0, U, Ns: int, n_features: int, seed: int, offset: int = 0, omega: Optional[torch.Tensor] = None,
+                        centre: Optional[torch.Tensor] = None, scale=None, eps: Sequence[float] = (), want_sup: bool = False,
+                        use_feedback: Optional[bool] = None, env_desc=None, max_groups: Optional[int] = None) -> TubeStats:
+    """The statistics of the tube ``PathwiseSamples.draw(agent_or_plan, Ns, n_features, seed, offset, omega).rollout(x0, U)`` in ONE call
+    of ``gpmpc_pathwise_tube_stats``: the normals, the update vectors and the trajectories exist only inside the kernel, and every
+    output has the bits of the torch reduction of that tube (include/gpmpc_hip.h).  ``x0 (nx,)`` and ``U (H, nu)`` are shared by the
+    samples; ``omega`` defaults to ``draw_omega(ell, n_features, seed)`` as in ``PathwiseSamples.draw``.
+
+    ``centre (nx, H+1)``: the trajectory deviations are taken from; ``None`` is the trajectory of the ``Z = 0`` sample of the same
+    frequencies - the posterior-mean function, the construction of ``PathwiseSamples.mean_only``, rolled out with the existing kernel.
+    (The reference rolls out the AVERAGE of its sampled weights instead, ``solver.py:101``: an estimate of the same mean function that
+    changes with the draw.)  ``scale (nx)`` divides the deviations of ``sup``; ``eps`` (at most 16 thresholds) are counted against
+    ``sup``; ``want_sup`` returns ``sup (Ns)``, the only output proportional to ``Ns``.  ``max_groups`` bounds the grid of persistent
+    workgroups (``None``: the library chooses); the results do not depend on it."""
+    plan, agent = _plan_of(agent_or_plan)
+    lib = _lib.load()
+    dev = plan.X_r.device
+    d = plan.desc
+    if env_desc is None:
+        if agent is None:
+            raise _lib.GpmpcError("pathwise_tube_stats needs an environment: pass an Agent or env_desc")
+        env_desc = agent.env_desc(use_feedback)
+    Ns, M, offset = int(Ns), int(n_features), int(offset)
+    if Ns < 1:
+        raise _lib.GpmpcError("pathwise_tube_stats needs Ns >= 1")
+    if omega is None:
+        omega = draw_omega(plan.hyper.ell, M, seed)
+    omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
+    if tuple(omega.shape) != (d.g_ny, M // 2, d.D):
+        raise _lib.GpmpcError(f"omega must be ({d.g_ny}, {M // 2}, {d.D})")
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
+    x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
+    U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
+    if tuple(x0.shape) != (nx,) or U.dim() != 2 or U.shape[1] != nu:
+        raise _lib.GpmpcError(f"x0 must be ({nx},) and U (H, {nu}): shared by the samples")
+    H = int(U.shape[0])
+    if centre is None:
+        Z0 = torch.zeros(1, d.g_ny * (M + d.N_r), dtype=F64, device=dev)
+        centre = PathwiseSamples._fit(plan, agent, omega, Z0, M, None, 0).rollout(x0, U, env_desc=env_desc)[0]
+    centre = torch.as_tensor(centre, dtype=F64).to(dev).contiguous()
+    if tuple(centre.shape) != (nx, H + 1):
+        raise _lib.GpmpcError(f"centre must be ({nx}, {H + 1}): the layout of one sample of the tube")
+    eps = tuple(float(e) for e in eps)
+    if len(eps) > MAX_EPS:
+        raise _lib.GpmpcError(f"at most {MAX_EPS} thresholds per call")
+    c_eps = (C.c_double * len(eps))(*eps) if eps else None
+    c_scale = None
+    if scale is not None:
+        scale = [float(v) for v in torch.as_tensor(scale, dtype=F64).reshape(-1).tolist()]
+        if len(scale) != nx:
+            raise _lib.GpmpcError(f"scale must have {nx} entries")
+        c_scale = (C.c_double * nx)(*scale)
+    groups = 0 if max_groups is None else int(max_groups)
+    if max_groups is not None and groups < 1:
+        raise _lib.GpmpcError("max_groups must be >= 1 (or None)")
+    out = lambda dt: torch.empty(H + 1, nx, dtype=dt, device=dev)
+    dev_max, dev_arg, box_lo, box_hi = out(F64), out(torch.int64), out(F64), out(F64)
+    sup = torch.empty(Ns, dtype=F64, device=dev) if want_sup else None
+    n_within = torch.zeros(len(eps), dtype=torch.int64, device=dev) if eps else None
+    n_nonfinite = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws_bytes = int(lib.gpmpc_pathwise_tube_stats_workspace_bytes(d, M, H, nx, len(eps), groups))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.gpmpc_pathwise_tube_stats(d, env_desc, _lib.dptr(plan.buf), _lib.dptr(plan.X_r), _lib.dptr(plan.Y_r), M,
+                                                 _lib.dptr(omega), int(seed) & ((1 << 64) - 1), offset, Ns, H, _lib.dptr(x0), _lib.dptr(U),
+                                                 _lib.dptr(centre), c_scale, len(eps), c_eps, _lib.dptr(dev_max), _lib.dptr(dev_arg),
+                                                 _lib.dptr(box_lo), _lib.dptr(box_hi), _lib.dptr(sup), _lib.dptr(n_within),
+                                                 _lib.dptr(n_nonfinite), groups, _lib.dptr(ws), ws_bytes, _lib.current_stream_ptr()),
+                   "gpmpc_pathwise_tube_stats")
+    return TubeStats(Ns, offset, dev_max, dev_arg, box_lo, box_hi, sup, eps, n_within, n_nonfinite)
+
+
+def tube_stats_of(X: torch.Tensor, centre: torch.Tensor, offset: int = 0, scale=None, eps: Sequence[float] = (),
+                  want_sup: bool = False) -> TubeStats:
+    """The same statistics of a tube ``X (Ns, nx, H+1)`` that exists (``PathwiseSamples.rollout``), by torch reductions on its device: the
+    chunked path ``tools/bench_pathwise_stats.py`` times, and the statement the device tests compare with bit for bit."""
+    X = torch.as_tensor(X, dtype=F64)
+    centre = torch.as_tensor(centre, dtype=F64).to(X.device)
+    inf = float("inf")
+    bad = ~torch.isfinite(X)
+    dev = (X - centre[None]).abs()
+    dev = torch.where(torch.isfinite(dev), dev, torch.full_like(dev, inf))
+    dev_max, arg = dev.max(dim=0)
+    first = (dev == dev_max[None]).to(torch.int64).argmax(dim=0)                     # the lowest index among ties
+    box_lo = torch.where(bad, torch.full_like(X, -inf), X).amin(dim=0)
+    box_hi = torch.where(bad, torch.full_like(X, inf), X).amax(dim=0)
+    sc = torch.ones(X.shape[1], dtype=F64, device=X.device) if scale is None else torch.as_tensor(scale, dtype=F64).to(X.device)
+    sup = (dev / sc[None, :, None]).amax(dim=(1, 2))
+    eps = tuple(float(e) for e in eps)
+    n_within = torch.stack([(sup <= e).sum() for e in eps]).to(torch.int64) if eps else None
+    n_nonfinite = bad.any(dim=2).any(dim=1).sum().to(torch.int64).reshape(1)
+    return TubeStats(int(X.shape[0]), int(offset), dev_max.T.contiguous(), (first + int(offset)).T.contiguous(), box_lo.T.contiguous(),
+                     box_hi.T.contiguous(), sup if want_sup else None, eps, n_within, n_nonfinite)
+
+
+def merge_tube_stats(parts: Sequence[TubeStats]) -> TubeStats:
+    """The statistics of the union of disjoint global id ranges: max, min and sum, on a tie of ``dev_max`` the lower id - the same bits
+    as one call over the union.  ``sup`` is the concatenation in the order of ``offset`` (``None`` unless every part has it); the
+    thresholds must agree."""
+    parts = sorted(parts, key=lambda p: p.offset)
+    if not parts:
+        raise ValueError("merge_tube_stats needs at least one part")
+    acc = parts[0]
+    for p in parts[1:]:
+        if p.eps != acc.eps:
+            raise ValueError("merge_tube_stats: the parts were counted against different thresholds")
+        take = (p.dev_max > acc.dev_max) | ((p.dev_max == acc.dev_max) & (p.dev_arg < acc.dev_arg))
+        acc = dataclasses.replace(
+            acc, Ns=acc.Ns + p.Ns, dev_max=torch.where(take, p.dev_max, acc.dev_max), dev_arg=torch.where(take, p.dev_arg, acc.dev_arg),
+            box_lo=torch.minimum(acc.box_lo, p.box_lo), box_hi=torch.maximum(acc.box_hi, p.box_hi),
+            sup=None if acc.sup is None or p.sup is None else torch.cat([acc.sup, p.sup]),
+            n_within=None if acc.n_within is None else acc.n_within + p.n_within, n_nonfinite=acc.n_nonfinite + p.n_nonfinite)
+    return acc
