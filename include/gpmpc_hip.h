@@ -851,6 +851,46 @@ int     gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t
                                void* stream);
 
 /*
+ * gpmpc_pathwise_rollout_vjp - the reverse-mode derivative (vector-Jacobian product) of the map (x0, U) -> X_traj that
+ * gpmpc_pathwise_rollout computes, exactly as that kernel defines it: the feedback law, the GP input selection and the environment
+ * step included.  One sample per wave, one backward sweep t = H-1..0 that reads x_t from the forward's X_traj (the forward is not run
+ * again).  An additive entry point: the ABI version stays 12.
+ * Replaces: nothing the reference has on the device - its sampled-dynamics problem (one input sequence against Ns sampled dynamics,
+ * extra/approx_sampling_mpc/src/solver.py) reaches the inputs through casadi's derivatives inside acados; here the gradient of any
+ * function of the sampled tube with respect to the inputs is one launch of the forward's cost: M + N_r evaluations per step and output.
+ * With lam = gX[s, :, H], for t = H-1 .. 0:  gU[s, t] = B_t^T lam,  lam = A_t^T lam + gX[s, :, t];  then gx0[s] = lam.  u_t and
+ * xi_t = (x_t[SEL], u_t[0]) are formed from X_traj[s, :, t] and U[t] with the forward's statements; A_t is the Jacobian of
+ * x -> env_step(x, fb(x), f(xi(x, fb(x)))) (the feedback path is in A_t), B_t = d x_t+1 / d U[t]: pendulum1D B[1][0] = df_0 / dxi_1;
+ * car B[i][0] = x_t[3] df_i / dxi_1 for i < 3, B[3][1] = dt; zero elsewhere.
+ *   X_r, M, omega, Z, ldz, V, x0, x0_per_sample, U, u_per_sample   the forward's inputs (x0 is only checked for non-finite entries:
+ *                                       x_0 is X_traj[:, :, 0])
+ *   X_traj [dev] (Ns, nx, H+1)          the forward's output, read
+ *   Y    [dev] (Ns, g_ny, H, 1 + D) or NULL   the forward's Y, read: the sample's value and gradient at every visited point.  NULL: they
+ *                                       are evaluated again with the forward's device function.  Y given or NULL gives the same
+ *                                       gradient bits (the rollout's Y is bit-equal to an evaluation at its own point).  Y is not
+ *                                       differentiated: it has no cotangent, which would need the samples' Hessians
+ *   gX   [dev] (Ns, nx, H+1) or NULL    cotangent of X_traj; NULL is zero: all gradients are then exact zeros
+ *   gx0  [dev] (Ns, nx) or NULL         out: d / d x0
+ *   gU   [dev] (Ns, H, nu)              out: d / d U (the feed-forward input)      (may be NULL when H == 0)
+ *   info [dev] (Ns) int32               out: 0 or GPMPC_INFO_NONFINITE
+ * Gradients are always per sample, also when x0 / U are shared (*_per_sample == 0): the host sums over Ns for a shared input, the
+ * kernel needs no cross-wave reduction and no atomics.
+ * Non-finite rule: a sample whose Z row, V, x0, U, X_traj, gX or (given) Y holds a non-finite entry, or for which a non-finite value is
+ * computed, has NaN in all its gradients and GPMPC_INFO_NONFINITE; no other sample is touched.
+ * Reproducibility: a sample's gradient bits do not depend on Ns or on its place in the batch.
+ * Limits and errors are those of gpmpc_pathwise_rollout: real_has_grad == 0; N_r <= 64; M a multiple of 128 and at most 1024; D = 2;
+ * the two environments; Ns < 2^31; GPMPC_E_UNSUPPORTED / GPMPC_E_ARG before any device work (required with Ns > 0: X_r, omega, x0, Z,
+ * V, X_traj, info, and U and gU when H > 0).  Ns == 0: nothing is launched and the array pointers are not looked at.  H == 0:
+ * gx0 = gX[:, :, 0].  No workspace, no hidden allocation, no host round trip, everything goes to `stream`.
+ */
+int     gpmpc_pathwise_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M,
+                                   const double* omega, int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample,
+                                   const double* U, int32_t u_per_sample, const double* Z, int64_t ldz, const double* V,
+                                   const double* X_traj /* (Ns, nx, H+1) */, const double* Y /* (Ns, g_ny, H, 1+D) or NULL */,
+                                   const double* gX /* (Ns, nx, H+1) or NULL */, double* gx0 /* (Ns, nx) or NULL */,
+                                   double* gU /* (Ns, H, nu) */, int32_t* info /* (Ns) */, void* stream);
+
+/*
  * gpmpc_pathwise_tube_stats (ABI 12) - statistics of the tube of Ns pathwise samples WITHOUT the tube: per stage and state dimension
  * the largest deviation from a centre trajectory, the sample that attains it and the box of the samples; per sample the scaled
  * sup-norm deviation over the horizon, and how many samples stay within eps.  Normals, update vectors and trajectories of a sample

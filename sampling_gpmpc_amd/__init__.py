@@ -19,7 +19,7 @@ from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, sol
 from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
 from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats, pathwise_tube_stats, merge_tube_stats,  # noqa: F401
-                       tube_stats_of)
+                       tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
@@ -30,4 +30,5 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "chance_constraint_penalty", "plan_inputs", "plan_inputs_plan", "TubeQP", "TubeQPResult",
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
            "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error",
-           "TubeStats", "pathwise_tube_stats", "merge_tube_stats", "tube_stats_of"]
+           "TubeStats", "pathwise_tube_stats", "merge_tube_stats", "tube_stats_of", "pathwise_rollout_vjp", "sampled_tube_penalty",
+           "plan_inputs_sampled"]

@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "rollout_one.hip", "rollout_indep.hip", "joint.hip",
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
            "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
-           "pathwise_stats.hip"]
+           "pathwise_stats.hip", "pathwise_grad.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce
@@ -55,7 +55,11 @@ EXTRA_FLAGS = {"rollout_fast.hip": os.environ.get("GPMPC_FAST_FLAGS", "-mllvm -d
                "joint_mfma.hip": os.environ.get("GPMPC_JOINT_MFMA_FLAGS", "").split(),
                # the fused pathwise kernel: with machine-LICM the invariants of the sample loop are hoisted over the fit and the
                # rollout (222 / 265 registers, the car at one wave per SIMD); without it 157 / 201 VGPRs, two waves per SIMD
-               "pathwise_stats.hip": os.environ.get("GPMPC_PATHWISE_STATS_FLAGS", "-mllvm -disable-machine-licm").split()}
+               "pathwise_stats.hip": os.environ.get("GPMPC_PATHWISE_STATS_FLAGS", "-mllvm -disable-machine-licm").split(),
+               # the pathwise VJP: with machine-LICM the step-invariant descriptor loads are hoisted over the backward sweep (161 / 241
+               # VGPRs, 3 / 2 waves per SIMD); without it 120 / 201 VGPRs, 4 / 2 waves per SIMD, no scratch either way; measured on the
+               # loop before its loads moved a step ahead: the car 3 - 6 % faster without, the pendulum 2 - 10 % slower
+               "pathwise_grad.hip": os.environ.get("GPMPC_PATHWISE_GRAD_FLAGS", "-mllvm -disable-machine-licm").split()}
 
 
 STAMP = os.path.join(OBJDIR, "flags.stamp")

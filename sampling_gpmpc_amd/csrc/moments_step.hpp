@@ -106,6 +106,26 @@ __host__ __device__ __forceinline__ void env_jacobian_ct(const EnvParams& e, con
     }
 }
 
+// B_t = d x+ / d u_ff at fixed x, the Jacobian of u_ff -> env_step(x, fb(x) + u_ff, f(xi(x, fb(x) + u_ff))); gd: the gradient of f at
+// xi.  The feedback path is a function of x and lives in A; u_ff reaches x+ through xi[1] = u[0] and, for the car, through u[1] dt.
+template <int ENV>
+__host__ __device__ __forceinline__ void env_input_jacobian_ct(const EnvParams& e, const double (&x)[EnvDims<ENV>::NX],
+                                                               const double (&gd)[EnvDims<ENV>::G_NY][2],
+                                                               double (&B)[EnvDims<ENV>::NX][EnvDims<ENV>::NU]) {
+#pragma unroll
+    for (int r = 0; r < EnvDims<ENV>::NX; ++r)
+#pragma unroll
+        for (int i = 0; i < EnvDims<ENV>::NU; ++i) B[r][i] = 0.0;
+    if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
+        B[1][0] = gd[0][1];                                            // B_d = [0, 1]^T
+    } else {
+        const double v = x[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) B[i][0] = v * gd[i][1];            // B_d = v I_{4x3}
+        B[3][1] = e.dt;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // arguments, the packed triangle and its staging
 // ---------------------------------------------------------------------------------------------------------------

@@ -174,11 +174,28 @@ class PathwiseSamples:
         self.last_info = info
         return out
 
-    def rollout(self, x0, U, use_feedback: Optional[bool] = None, want_samples: bool = False, env_desc=None):
+    def _env_desc(self, use_feedback, env_desc):
+        if env_desc is None:
+            if self.agent is None:
+                raise _lib.GpmpcError("rollout needs an environment: draw the samples for an Agent or pass env_desc")
+            env_desc = self.agent.env_desc(use_feedback)
+        return env_desc
+
+    def rollout(self, x0, U, use_feedback: Optional[bool] = None, want_samples: bool = False, env_desc=None, differentiable: bool = False):
         """The tube ``X_traj (Ns, nx, H+1)`` of the samples in one launch (``gpmpc_pathwise_rollout``): ``x0 (nx,)`` or ``(Ns, nx)``,
         ``U (H, nu)`` or ``(Ns, H, nu)``; environment step and feedback law as ``gpmpc_rollout`` (the descriptor comes from the Agent the
         samples were drawn for; ``use_feedback`` None: ``agent.feedback.use``).  ``want_samples``: also ``Y (Ns, g_ny, H, 1 + D)``, the
-        sample's value and gradient at every visited point - returned as ``(X_traj, Y)``.  ``self.last_info`` as for ``evaluate``."""
+        sample's value and gradient at every visited point - returned as ``(X_traj, Y)``.  ``self.last_info`` as for ``evaluate``.
+        ``differentiable=True``: ``X_traj`` carries a ``grad_fn`` whose backward is one launch of ``gpmpc_pathwise_rollout_vjp``; ``x0`` and
+        ``U`` receive gradients if they require them (``Y`` and ``info`` are not differentiable; ``Y`` is kept for the backward when
+        ``want_samples``, else evaluated again there); the values are those of the default call, bit for bit."""
+        if differentiable:
+            dev = _lib.require_hip_device(self.Z.device)
+            env_desc = self._env_desc(use_feedback, env_desc)
+            x0, U = _rollout_inputs(self, env_desc, dev, x0, U)
+            X, Y, info = _PathwiseRollout.apply(x0, U, self, env_desc, bool(want_samples))
+            self.last_info = info
+            return (X, Y) if want_samples else X
         lib = _lib.load()
         dev = _lib.require_hip_device(self.Z.device)
         if env_desc is None:
@@ -229,6 +246,201 @@ def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
         grad = grad - torch.einsum("sn,mn,mnd->smd", v, k, q)
         outs.append(torch.cat([val[..., None], grad], dim=-1))
     return torch.stack(outs, dim=1)
+
+
+def torch_rollout(samples: PathwiseSamples, x0: torch.Tensor, U: torch.Tensor, env_desc) -> torch.Tensor:
+    """The arithmetic of ``rollout`` - ``torch_evaluate``'s, at one point per sample and step - as batched torch operations on the
+    samples' device, differentiable in ``x0`` and ``U`` by ``torch.autograd``: what stands in for ``gpmpc_pathwise_rollout_vjp`` without
+    it, the comparison ``tools/bench_pathwise_grad.py`` times, and a cross-check.  ``X_traj (Ns, nx, H+1)``."""
+    plan, d = samples.plan, samples.plan.desc
+    Ns, M, n, F = samples.Ns, samples.n_features, d.N_r, samples.n_features // 2
+    dev = samples.Z.device
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
+    Z = samples.Z[:, :d.g_ny * (M + n)].reshape(Ns, d.g_ny, M + n)
+    ell = torch.as_tensor(plan.hyper.ell, dtype=F64, device=dev)
+    osc = [float(v) for v in torch.as_tensor(plan.hyper.outputscale, dtype=F64).tolist()]
+    K = torch.tensor([[env_desc.K[i][j] for j in range(nx)] for i in range(nu)], dtype=F64, device=dev)
+    goal = torch.tensor([env_desc.x_goal[j] for j in range(nx)], dtype=F64, device=dev)
+    dt, pend = float(env_desc.dt), int(env_desc.env_id) == _lib.ENV_PENDULUM1D
+    x = x0.expand(Ns, nx) if x0.dim() == 1 else x0
+    Xs = [x]
+    for t in range(int(U.shape[-2])):
+        u = (U[t].expand(Ns, nu) if U.dim() == 2 else U[:, t])
+        if env_desc.use_feedback:
+            u = u + (x - goal) @ K.T
+        xi = torch.stack([x[:, 0 if pend else 2], u[:, 0]], dim=1)                  # (Ns, 2)
+        g = []
+        for o in range(d.g_ny):
+            ang = xi @ samples.omega[o].T                                           # (Ns, F)
+            val = math.sqrt(osc[o] / F) * ((Z[:, o, 0:M:2] * torch.cos(ang)).sum(1) + (Z[:, o, 1:M:2] * torch.sin(ang)).sum(1))
+            r = xi[:, None, :] - plan.X_r[None, :, :]                               # (Ns, n, 2)
+            k = osc[o] * torch.exp(-0.5 * (r * r / (ell[o] * ell[o])).sum(-1))
+            g.append(val + (samples.V[:, o, :] * k).sum(1))
+        if pend:
+            x = torch.stack([x[:, 0] + x[:, 1] * dt, x[:, 1] + g[0]], dim=1)
+        else:
+            v = x[:, 3]
+            x = torch.stack([x[:, 0] + v * g[0], x[:, 1] + v * g[1], x[:, 2] + v * g[2], v + u[:, 1] * dt], dim=1)
+        Xs.append(x)
+    return torch.stack(Xs, dim=2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reverse-mode gradient of the rollout and what it is for
+# ---------------------------------------------------------------------------------------------------------------------
+def _rollout_inputs(samples: PathwiseSamples, env_desc, dev, x0, U):
+    """The argument handling of ``rollout``: float64 contiguous device tensors (the conversions keep an autograd graph)."""
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
+    x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
+    U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
+    if x0.dim() not in (1, 2) or x0.shape[-1] != nx or (x0.dim() == 2 and x0.shape[0] != samples.Ns):
+        raise _lib.GpmpcError(f"x0 must be ({nx},) or ({samples.Ns}, {nx})")
+    if U.dim() not in (2, 3) or U.shape[-1] != nu or (U.dim() == 3 and U.shape[0] != samples.Ns):
+        raise _lib.GpmpcError(f"U must be (H, {nu}) or ({samples.Ns}, H, {nu})")
+    return x0, U
+
+
+def _rollout_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
+    """One launch of ``gpmpc_pathwise_rollout_vjp``: per-sample gradients ``(g_x0 (Ns, nx), g_U (Ns, H, nu), info (Ns))``."""
+    lib = _lib.load()
+    dev = samples.Z.device
+    d = samples.plan.desc
+    Ns, nx, nu, H = samples.Ns, int(env_desc.nx), int(env_desc.nu), int(U.shape[-2])
+    for name, t, shape in (("X_traj", X_traj, (Ns, nx, H + 1)), ("g_X", g_X, (Ns, nx, H + 1)), ("Y", Y, (Ns, d.g_ny, H, 1 + d.D))):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
+            raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
+    X_traj = X_traj.detach().contiguous()
+    Y = None if Y is None else Y.detach().contiguous()
+    g_X = None if g_X is None else g_X.detach().contiguous()
+    g_x0 = torch.empty(Ns, nx, dtype=F64, device=dev)
+    g_U = torch.empty(Ns, H, nu, dtype=F64, device=dev)
+    info = torch.zeros(Ns, dtype=torch.int32, device=dev)
+    _lib.check(lib.gpmpc_pathwise_rollout_vjp(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, H,
+                                              _lib.dptr(x0.detach()), int(x0.dim() == 2), _lib.dptr(U.detach()), int(U.dim() == 3),
+                                              samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X_traj), _lib.dptr(Y),
+                                              _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info), _lib.current_stream_ptr()),
+               "gpmpc_pathwise_rollout_vjp")
+    return g_x0, g_U, info
+
+
+def _like_input(g, per_sample):
+    """A shared input's gradient is the sum of the samples' (the kernel writes per sample: no atomics)."""
+    return g if per_sample else g.sum(0)
+
+
+class _PathwiseRollout(torch.autograd.Function):
+    """``gpmpc_pathwise_rollout`` with ``gpmpc_pathwise_rollout_vjp`` as its backward; ``Y`` and ``info`` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, U, samples, env_desc, want_samples):
+        out = samples.rollout(x0, U, want_samples=want_samples, env_desc=env_desc)
+        X, Y = out if want_samples else (out, None)
+        info = samples.last_info
+        ctx.samples, ctx.env_desc, ctx.has_y = samples, env_desc, Y is not None
+        ctx.save_for_backward(x0, U, X, *(() if Y is None else (Y,)))
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (Y, info) if t is not None))
+        return X, Y, info
+
+    @staticmethod
+    def backward(ctx, g_X, *_):
+        if g_X is None:
+            return (None,) * 5
+        x0, U, X = ctx.saved_tensors[:3]
+        Y = ctx.saved_tensors[3] if ctx.has_y else None
+        g_x0, g_U, _ = _rollout_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X)
+        need = ctx.needs_input_grad
+        return (_like_input(g_x0, x0.dim() == 2) if need[0] else None, _like_input(g_U, U.dim() == 3) if need[1] else None,
+                None, None, None)
+
+
+def pathwise_rollout_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, use_feedback: Optional[bool] = None, env_desc=None):
+    """``gpmpc_pathwise_rollout_vjp`` (include/gpmpc_hip.h): the gradients of ``sum(g_X * X_traj)`` with respect to the inputs the tube
+    ``X_traj = samples.rollout(x0, U)`` was computed from.  Returns ``(g_x0, g_U, info)``: the gradients have the shapes of ``x0`` and
+    ``U`` - summed over the samples where the input was shared - and ``info (Ns)`` is int32.  ``Y``: the rollout's samples
+    (``want_samples=True``) spare their evaluation; the gradient bits are the same without.  ``g_X`` None is zero.  One launch, no host
+    synchronisation."""
+    dev = _lib.require_hip_device(samples.Z.device)
+    env_desc = samples._env_desc(use_feedback, env_desc)
+    x0, U = _rollout_inputs(samples, env_desc, dev, x0, U)
+    if not torch.is_tensor(X_traj):
+        raise _lib.GpmpcError("X_traj must be the tensor samples.rollout returned")
+    g_x0, g_U, info = _rollout_backward(samples, env_desc, x0, U, X_traj, Y, g_X)
+    return _like_input(g_x0, x0.dim() == 2), _like_input(g_U, U.dim() == 3), info
+
+
+def sampled_tube_penalty(X_traj: torch.Tensor, rows) -> torch.Tensor:
+    """The squared violation of every row of a ``TubeRows`` (``ocp_rows(agent, v)`` gives the reference's) by every sample of a tube
+    ``X_traj (Ns, nx, H+1)``, per sample ``(Ns,)``: ``sum_t sum_r relu(val_tr - hi_tr)^2 + relu(lo_tr - val_tr)^2`` with the affine rows
+    ``val = E_r x_t + off_tr`` and the quadric rows ``val = (x_t - c_q)^T M_q (x_t - c_q)``; a side that is not finite takes no part.  Plain
+    torch operations on the tube's device, differentiable in ``X_traj``: the sampled counterpart of ``chance_constraint_penalty`` - no
+    tightening, every sample meets the rows itself - and here the quadric rows are included."""
+    if not torch.is_tensor(X_traj) or X_traj.dim() != 3:
+        raise _lib.GpmpcError("sampled_tube_penalty takes a tube (Ns, nx, H+1)")
+    r = rows.to(X_traj.device)
+    nx, T = int(X_traj.shape[1]), int(X_traj.shape[2])
+    rnx = int(r.E.shape[1]) if r.E is not None else int(r.M.shape[1])
+    if rnx != nx or int(r.lo.shape[0]) != T:
+        raise _lib.GpmpcError(f"sampled_tube_penalty: the rows are for nx = {rnx} and {int(r.lo.shape[0])} stages, the tube has nx = {nx} "
+                              f"and {T}")
+    vals = []
+    if r.E is not None:
+        lin = torch.einsum("rd,sdt->str", r.E, X_traj)
+        vals.append(lin if r.off is None else lin + r.off[None])
+    if r.M is not None:
+        dq = X_traj.permute(0, 2, 1)[:, :, None, :] - r.c[None, None]                 # (Ns, T, n_quad, nx)
+        vals.append(torch.einsum("stqi,qij,stqj->stq", dq, r.M, dq))
+    val = torch.cat(vals, dim=2)                                                     # (Ns, T, n_rows)
+    lo, hi = r.lo[None], r.hi[None]
+    zero = torch.zeros_like(val)
+    up = torch.where(torch.isfinite(hi), val - torch.where(torch.isfinite(hi), hi, zero), zero)
+    dn = torch.where(torch.isfinite(lo), torch.where(torch.isfinite(lo), lo, zero) - val, zero)
+    return (torch.relu(up) ** 2 + torch.relu(dn) ** 2).sum(dim=(1, 2))
+
+
+def plan_inputs_sampled(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: float, use_feedback: Optional[bool] = None, env_desc=None):
+    """Gradient-based improvement of ONE input sequence ``U0 (H, nu)`` shared by all samples against the sampled tube - the reference's
+    problem (one input sequence, ``Ns`` sampled dynamics) - with the update of ``plan_inputs``: Adam (``torch.optim.Adam``'s update and
+    defaults) on the mean over the samples of ``cost(X_traj, U) -> (Ns,)``, any torch function of the differentiable tube
+    ``samples.rollout(x0, U, differentiable=True)`` and of ``U`` (``sampled_tube_penalty`` is one ingredient).  Returns the final
+    ``U (H, nu)`` and the cost history ``(steps + 1,)`` - entry ``k`` is the cost before update ``k + 1``, the last that of the result
+    (there is one sequence, so no index of a best one).  One forward and one backward launch per iteration, no host round trip inside
+    the loop."""
+    if not callable(cost):
+        raise _lib.GpmpcError("plan_inputs_sampled: cost must be a function (X_traj, U) -> (Ns,)")
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
+        raise _lib.GpmpcError("plan_inputs_sampled: steps must be an integer >= 0")
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0.0:
+        raise _lib.GpmpcError("plan_inputs_sampled: lr must be a positive number")
+    if not torch.is_tensor(U0) or U0.dim() != 2:
+        raise _lib.GpmpcError("plan_inputs_sampled: U0 must be a tensor (H, nu): one input sequence shared by the samples")
+    dev = _lib.require_hip_device(samples.Z.device)
+    env_desc = samples._env_desc(use_feedback, env_desc)
+    U = U0.detach().to(device=dev, dtype=F64).clone()
+    Ns = samples.Ns
+    b1, b2, eps = 0.9, 0.999, 1e-8
+    m, v = torch.zeros_like(U), torch.zeros_like(U)
+    hist = torch.empty(steps + 1, dtype=F64, device=dev)
+
+    def mean_cost(X, Uc):
+        c = cost(X, Uc)
+        if not torch.is_tensor(c) or tuple(c.shape) != (Ns,):
+            raise _lib.GpmpcError(f"plan_inputs_sampled: cost must return a tensor ({Ns},), one value per sample")
+        return c.mean()
+
+    for it in range(1, steps + 1):
+        Uc = U.detach().requires_grad_(True)
+        # with the samples kept: the backward then evaluates nothing again (same gradient bits, a fraction of the time: DESIGN 4.13c)
+        c = mean_cost(samples.rollout(x0, Uc, want_samples=True, env_desc=env_desc, differentiable=True)[0], Uc)
+        hist[it - 1] = c.detach()
+        g, = torch.autograd.grad(c, Uc)                                # one backward launch; the sum over the samples is torch's
+        m = torch.lerp(m, g, 1.0 - b1)                                 # the operations of torch.optim.Adam's single-tensor step
+        v = torch.addcmul(v * b2, g, g, value=1.0 - b2)
+        denom = v.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
+        U = torch.addcdiv(U, m, denom, value=-(lr / (1.0 - b1 ** it)))
+    with torch.no_grad():
+        hist[steps] = mean_cost(samples.rollout(x0, U, env_desc=env_desc), U)
+    return U, hist
 
 
 # ---------------------------------------------------------------------------------------------------------------------
