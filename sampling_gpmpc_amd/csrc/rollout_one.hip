@@ -112,11 +112,13 @@ __device__ __forceinline__ void one_for(F&& f) {
         one_for<B + 1, E>(f);
     }
 }
-// f(integral_constant<i>) for the i in [B, E) that equals the (uniform) v, by bisection; nothing if v is outside
+// f(integral_constant<i>) for the i in [B, E) that equals the (uniform) v, by bisection.  v IS in [B, E) - the caller's
+// invariant: the last level is not tested, so no path leaves without a block and what the blocks write needs no copy of
+// the old value for it
 template <int B, int E, class F>
 __device__ __forceinline__ void one_pick_row(int v, F&& f) {
     if constexpr (E - B == 1) {
-        if (v == B) f(std::integral_constant<int, B>{});
+        f(std::integral_constant<int, B>{});
     } else if constexpr (E - B > 1) {
         constexpr int M = (B + E) / 2;
         if (v < M) one_pick_row<B, M>(v, f);
@@ -149,6 +151,12 @@ __device__ __forceinline__ double one_bpermute(double v, int addr) {
     const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(v));
     const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(v));
     return __hiloint2double(hi, lo);
+}
+// m = fmin(m, a, b, c), three v_min_f64 in place: a, b and c are results of v_add_f64 (never signalling) - the library's fmin
+// canonicalises its operands by hand (v_max_f64 x, x, x).  Same value for non-NaN operands; nothing in the step branches on m
+// (the uniformity analysis takes an asm's VGPR result for divergent).
+__device__ __forceinline__ void one_min3(double& m, double a, double b, double c) {
+    asm("v_min_f64 %0, %0, %1\n\tv_min_f64 %0, %0, %2\n\tv_min_f64 %0, %0, %3" : "+v"(m) : "v"(a), "v"(b), "v"(c));
 }
 // exp(x), x <= 0: the algorithm of expn_neg (gpmpc_device.hpp: Cody-Waite reduction, degree-11 polynomial in Estrin form)
 // with its thirteen constants in registers that live across the step loop.  This file is compiled without machine-LICM
@@ -345,6 +353,7 @@ __device__ __forceinline__ void one_chol_rest(const double (&A)[3][3], const dou
 }
 
 typedef const __attribute__((address_space(4))) RolloutArgs* OneArgsPtr;
+typedef __attribute__((address_space(3))) double* OneLdsRow;
 // (opaque to the optimiser: a load through the result stays where it is written)
 __device__ __forceinline__ OneArgsPtr one_cold_args(OneArgsPtr p) {
     asm volatile("" : "+s"(p));
@@ -408,7 +417,12 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     // axis lanes: lane j < N0 holds axis-0 point j (real point N1 j), lane N0 + j axis-1 point j
     const bool g_ax0 = lane < N0;
     const int g_pt = g_ax0 ? lane * N1 : ((lane < N0 + N1) ? lane - N0 : 0);
-    const double g_x = a.X_r[g_pt * D + (g_ax0 ? 0 : 1)], g_il2 = g_ax0 ? il0 : il1;
+    // ONE exponent formula for both roles of a lane (ent_a): an axis lane keeps its grid coordinate in xh[0] (only the lanes
+    // of appended points are ever overwritten) and measures it against the GP input's own axis (g_sel0: coordinate 0) with
+    // its axis' inverse length scale, the second term switched off by a zero scale; a point lane has both terms
+    const bool g_axis = lane < N0 + N1, g_sel0 = g_ax0 || !g_axis;
+    const double g_x = a.X_r[g_pt * D + (g_ax0 ? 0 : 1)];
+    const double il0_lane = g_axis ? (g_ax0 ? il0 : il1) : il0, il1_lane = g_axis ? 0.0 : il1;
     const int bp_addr = (lane & 15) << 2;                         // ds_bpermute address of "my lane of DPP row 0"
     // appended point j lives in lane kPt0 + j: behind the N0 + N1 axis lanes, so that ONE exponential per step serves both roles
     constexpr int kPt0 = N0 + N1;
@@ -419,6 +433,10 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     // natural-map reads of the lane-map converters (doubles): unified tile 4 g + bm, row kq, column jq
     const int vr_rd = (4 * bm + kq) * kOneRS + jq;                // + 16 g RS (g = 0, 1), group 2: block 0 only
     const int hs_rd = (4 * (bm - NKT) + kq) * kOneRS + jq;        // + 16 g RS; blocks of real-data tiles are clamped to row 0
+    // LDS byte addresses of the lane's converter rows (ent_c_put): the rows 3 jpt .. 3 jpt + 2 of HS (lanes in front of the
+    // appended points get an address below the buffer and are never enabled), row `lane` of VR
+    unsigned hs_wr = (unsigned)(size_t)(OneLdsRow)(HSb + 3 * jpt * kOneRS), vr_wr = (unsigned)(size_t)(OneLdsRow)(VRb + lane * kOneRS);
+    asm volatile("" : "+v"(hs_wr), "+v"(vr_wr));                  // (computed once: the add of the LDS base stays out of the step)
     const int rA = 4 * bm + jq;                                   // row of this lane's diagonal-tile entry inside its group
 
     double x[NX];
@@ -429,11 +447,14 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #pragma unroll
     for (int c = 0; c < T; ++c) zq[c] = (lane < H) ? a.z[(long)lane * a.z_step_stride + s * T + c] : 0.0;
     uq = (lane < H) ? a.u_ff[lane] : 0.0;
-    double xh[D] = {0.0, 0.0}, yt[T] = {0.0, 0.0, 0.0};           // lane = appended point: its GP input and labels
+    double xh[D] = {g_axis ? g_x : 0.0, 0.0}, yt[T] = {0.0, 0.0, 0.0};           // lane = appended point: its GP input and labels
     // the diagonal tiles of the group being appended to (one tile per block): L^T in the natural map and 1 / diag along its
     // rows / columns; the same for the next group (rows that wrap into it)
     double ud = Inat, drow = 1.0, dcol = 1.0, ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
     int info_acc = 0;
+    // INFO_VAR_CLAMPED: "some step's variance was below the floor" == "the least variance of the launch is": a running minimum
+    // in the step, ONE test behind the loop
+    double s_min = __builtin_inf();
     int n_h = 0, t = 0;
 
     double* const Y_s = a.Y ? a.Y + s * H * T : nullptr;          // this sample's rows of the optional outputs
@@ -471,15 +492,15 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #pragma unroll
             for (int d = 0; d < D; ++d) Xi_s[tn * D + d] = xi[d];
         }
-        const double gr = g_x - (g_ax0 ? xi[0] : xi[1]), gq = gr * g_il2;
-        const double d0 = xh[0] - xi[0], d1 = xh[1] - xi[1], q0 = d0 * il0, q1 = d1 * il1;
-        return (lane < kPt0) ? -0.5 * gr * gq : -0.5 * (d0 * q0 + d1 * q1);
+        // (axis lanes: d1 * q1 is an exact zero, so the sum is round(d0 * q0) and the scaling by -0.5 is exact in either order)
+        const double d0 = xh[0] - (g_sel0 ? xi[0] : xi[1]), d1 = xh[1] - xi[1], q0 = d0 * il0_lane, q1 = d1 * il1_lane;
+        return -0.5 * (d0 * q0 + d1 * q1);
     };
     // (b) the factor of the tn existing points, and the axis factors to all DPP rows (requested here, used in (c))
-    // (gq, q0, q1 are two instructions each from the GP input (xi0, xi1): computed again where they are used rather than
+    // (q0, q1 are two instructions each from the GP input (xi0, xi1): computed again where they are used rather than
     // carried across the roots - this kernel has no register to spare)
     auto ent_b = [&](int tn, double ea, double xi0, double xi1, double& kk, double& Rq0, double& Rq1) {
-        const double gr = g_x - (g_ax0 ? xi0 : xi1), gq = gr * g_il2;
+        const double gq = (xh[0] - (g_sel0 ? xi0 : xi1)) * il0_lane;   // (an axis lane's q0)
         kk = (jpt >= 0 && jpt < tn) ? os * ea : 0.0;
         Rq0 = one_bpermute(ea, bp_addr);
         Rq1 = one_bpermute(ea * gq, bp_addr);
@@ -517,28 +538,49 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     };
     constexpr unsigned long long kPtLanes = ((1ull << 32) - 1) << kPt0;    // the lanes of the 32 appended points
     constexpr unsigned long long kRealLanes = (1ull << NR) - 1;           // the lanes of the real points
+    // The writes are ONE statement under literal EXEC masks: EXEC is all ones here (64 lanes launched, uniform control flow), so
+    // nothing is saved and nothing tested - left to hipcc each `if (lane mask)` is s_and_saveexec + s_cbranch_execz + the
+    // address add of the dynamic LDS base (zero) + s_or.  Row (3 jpt + aa) of HS: columns 0 .. 3 from hs_wr + 5 aa doubles;
+    // the step's column rotation picks WHICH value stands in a column, at compile time.  (LDS executes a wave's instructions in
+    // order: the reads at the next step's head follow these writes without a wait.)
+    static_assert(kPtLanes == 0x00001fffffffe000ull && kRealLanes == 0x0000000fffffffffull, "the EXEC literals of ent_c_put");
     auto ent_c_put = [&](auto nhc, const OneEntC& e) {
         constexpr int nh = decltype(nhc)::value;
         constexpr int i0 = nh & 3, ycol = (i0 + 3) & 3;
         constexpr int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
+        const unsigned ha = hs_wr, va = vr_wr;
+        double vr4[4];                                            // rows of v_r, task column c at (i0 + c) & 3, whitened label beside
+        vr4[cb0] = e.vr[0], vr4[cb1] = e.vr[1], vr4[cb2] = e.vr[2], vr4[ycol] = w_lane;
         if constexpr (nh > 0) {
-            if (__builtin_amdgcn_inverse_ballot_w64(kPtLanes)) {
+            double h4[T][4];
 #pragma unroll
-                for (int aa = 0; aa < T; ++aa) {
-                    double* dst = HSb + (3 * jpt + aa) * kOneRS;
-                    dst[cb0] = e.hs[aa][0];
-                    dst[cb1] = e.hs[aa][1];
-                    dst[cb2] = e.hs[aa][2];
-                    dst[ycol] = yt[aa];                           // (zero until the lane's point exists)
-                }
-            }
-        }
-        if (__builtin_amdgcn_inverse_ballot_w64(kRealLanes)) {    // rows of v_r, task column c at (i0 + c) & 3, whitened label beside
-            double* dst = VRb + lane * kOneRS;
-            dst[cb0] = e.vr[0];
-            dst[cb1] = e.vr[1];
-            dst[cb2] = e.vr[2];
-            dst[ycol] = w_lane;
+            for (int aa = 0; aa < T; ++aa)                        // (the label is zero until the lane's point exists)
+                h4[aa][cb0] = e.hs[aa][0], h4[aa][cb1] = e.hs[aa][1], h4[aa][cb2] = e.hs[aa][2], h4[aa][ycol] = yt[aa];
+            asm volatile("s_mov_b32 exec_lo, 0xffffe000\n\ts_mov_b32 exec_hi, 0x1fff\n\t"      // kPtLanes
+                         "ds_write2_b64 %[ha], %[a0], %[a1] offset1:1\n\t"
+                         "ds_write2_b64 %[ha], %[a2], %[a3] offset0:2 offset1:3\n\t"
+                         "ds_write2_b64 %[ha], %[b0], %[b1] offset0:5 offset1:6\n\t"
+                         "ds_write2_b64 %[ha], %[b2], %[b3] offset0:7 offset1:8\n\t"
+                         "ds_write2_b64 %[ha], %[c0], %[c1] offset0:10 offset1:11\n\t"
+                         "ds_write2_b64 %[ha], %[c2], %[c3] offset0:12 offset1:13\n\t"
+                         "s_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, 0xf\n\t"                // kRealLanes
+                         "ds_write2_b64 %[va], %[v0], %[v1] offset1:1\n\t"
+                         "ds_write2_b64 %[va], %[v2], %[v3] offset0:2 offset1:3\n\t"
+                         "s_mov_b64 exec, -1"
+                         :
+                         : [ha] "v"(ha), [va] "v"(va), [a0] "v"(h4[0][0]), [a1] "v"(h4[0][1]), [a2] "v"(h4[0][2]), [a3] "v"(h4[0][3]),
+                           [b0] "v"(h4[1][0]), [b1] "v"(h4[1][1]), [b2] "v"(h4[1][2]), [b3] "v"(h4[1][3]), [c0] "v"(h4[2][0]),
+                           [c1] "v"(h4[2][1]), [c2] "v"(h4[2][2]), [c3] "v"(h4[2][3]), [v0] "v"(vr4[0]), [v1] "v"(vr4[1]), [v2] "v"(vr4[2]),
+                           [v3] "v"(vr4[3])
+                         : "memory");
+        } else {
+            asm volatile("s_mov_b32 exec_lo, -1\n\ts_mov_b32 exec_hi, 0xf\n\t"                // kRealLanes
+                         "ds_write2_b64 %[va], %[v0], %[v1] offset1:1\n\t"
+                         "ds_write2_b64 %[va], %[v2], %[v3] offset0:2 offset1:3\n\t"
+                         "s_mov_b64 exec, -1"
+                         :
+                         : [va] "v"(va), [v0] "v"(vr4[0]), [v1] "v"(vr4[1]), [v2] "v"(vr4[2]), [v3] "v"(vr4[3])
+                         : "memory");
         }
     };
 
@@ -592,7 +634,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         OPH(2);
 
         // ---- S' = sum_g Vu[g]^T Vu[g] (each block sums its own tiles), summed over the blocks; entry [k][j] in lane 16 k + j ---
-        double mu[T], S[T][T], var[T], zt[T];
+        double mu[T], S[T][T], zt[T];
         const double Stot = one_block_sum(S0 + S1);
         ODBG(6, Stot);
         const int cb[T] = {cb0, cb1, cb2};
@@ -605,9 +647,10 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 S[bq][c] = val;
                 S[c][bq] = val;
             }
-            // variance floor (as sample_gp, src/agent.py:629-708)
-            var[bq] = fmax(S[bq][bq], gp.var_floor);
         };
+        // variance floor (as sample_gp, src/agent.py:629-708).  OFF THE SPINE: the floored variance bounds the clip interval and
+        // nothing else, and the step's clip test may use the raw variance - see draw()
+        auto var = [&](int bq) { return fmax(S[bq][bq], gp.var_floor); };
         // (the mean and the base sample of a slot are fetched where its draw is formed: SGPRs are as scarce as VGPRs here)
         auto fetch = [&](auto bc) {
             constexpr int bq = decltype(bc)::value;
@@ -640,10 +683,10 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         }
         extract(std::integral_constant<int, 1>{});
         extract(std::integral_constant<int, 2>{});
-        if (fmin(fmin(S[0][0], S[1][1]), S[2][2]) < gp.var_floor) info_acc |= GPMPC_INFO_VAR_CLAMPED;
+        one_min3(s_min, S[0][0], S[1][1], S[2][2]);
         // the variance-is-zero replacement (src/agent.py:646-660) is off (threshold < 0) in the shipped configurations: uniform branch
         bool all_zero = false;
-        if (!LEAN && a.var_zero_thr >= 0.0) all_zero = (var[0] <= a.var_zero_thr) && (var[1] <= a.var_zero_thr) && (var[2] <= a.var_zero_thr);
+        if (!LEAN && a.var_zero_thr >= 0.0) all_zero = (var(0) <= a.var_zero_thr) && (var(1) <= a.var_zero_thr) && (var(2) <= a.var_zero_thr);
         // ---- (iii) + (iv) pivots 2 and 3 with the next step's exponential as a third stream of their levels ------------------
         double Rt[T][T], C[T][T], cinv[T];
         bool c_ok, r_ok;
@@ -661,6 +704,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         double y[T];
         bool clip;                                                // ONE branch for the three slots and every rare path: a taken
         auto draw = [&]() {                                       // branch of a lone wave costs an instruction fetch (~30 cycles)
+            // The test that sends the step into the cold block uses the RAW variance: var = max(S, floor) >= S, so whatever
+            // the floored bound clips this one catches (a NaN S fails the root and gets there by !r_ok); the cold block repeats
+            // the test per slot with the floored variance and decides.  The three maxima leave the spine.
             clip = false;
 #pragma unroll
             for (int bq = 0; bq < T; ++bq) {
@@ -669,7 +715,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 for (int c = 0; c <= bq; ++c) acc = fma(Rt[bq][c], zt[c], acc);
                 const double yb = acc + mu[bq];
                 const double dlt = yb - mu[bq];
-                clip = clip || (dlt * dlt > a.beta * a.beta * var[bq]);
+                clip = clip || (dlt * dlt > a.beta * a.beta * S[bq][bq]);
                 y[bq] = yb;
             }
         };
@@ -686,8 +732,8 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #pragma unroll
                 for (int bq = 0; bq < T; ++bq) {
                     const double dlt = y[bq] - mu[bq];
-                    if (dlt * dlt > a.beta * a.beta * var[bq]) {
-                        const double sd = a.beta * sqrt(var[bq]);
+                    if (dlt * dlt > a.beta * a.beta * var(bq)) {
+                        const double sd = a.beta * sqrt(var(bq));
                         y[bq] = fmin(fmax(y[bq], mu[bq] - sd), mu[bq] + sd);
                     }
                 }
@@ -778,7 +824,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 const double Gt = inverse_tiles(ud, drow, dcol);
                 ODBG(8, ud);
                 ODBG(9, Gt);
-                one_set_gd<K>(P, ~0ull, Gt);
+                one_put_gd<K>(P, Gt);
             }
             n_h += T;
         }
@@ -800,6 +846,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
     });
 
+    if (s_min < gp.var_floor) info_acc |= GPMPC_INFO_VAR_CLAMPED;
     // (the output pointers and the sample index are fetched again here: held in SGPRs across the step loop they would be
     // spilled - the loop leaves no scalar register free)
     {

@@ -315,19 +315,36 @@ def set_stmt(items, mask="mask"):
 def hidden_set_stmt(items, mask):
     """the same masked update WITHOUT naming the panels as operands: for use under a C++ branch (a tied physical-register
     operand defined inside a branch makes hipcc carry the panel in a virtual register across it); one_touch() afterwards tells
-    the compiler that the panels may have changed."""
+    the compiler that the panels may have changed.  EXEC IS ALL ONES where these stand (the kernel is launched 64 lanes wide
+    and the step's control flow is uniform): nothing is saved, EXEC is restored to -1."""
     k = len(items)
-    lines = ['"s_mov_b64 %0, exec\\n\\t"', '"s_mov_b64 exec, %1\\n\\t"']
+    lines = ['"s_mov_b64 exec, %0\\n\\t"']
     ins = [f'"s"({mask})']
     for i, (areg, val) in enumerate(items):
-        lo = 2 + 2 * i
+        lo = 1 + 2 * i
         lines.append(f'"v_accvgpr_write_b32 a{areg}, %{lo}\\n\\t"')
         lines.append(f'"v_accvgpr_write_b32 a{areg + 1}, %{lo + 1}\\n\\t"')
         ins.append(f'"v"(__double2loint({val}))')
         ins.append(f'"v"(__double2hiint({val}))')
-    lines.append('"s_mov_b64 exec, %0"')
+    lines.append('"s_mov_b64 exec, -1"')
     body = "\n        ".join(lines)
-    return f"    asm volatile({body}\n        : \"=&s\"(sv_)\n        : {', '.join(ins)});\n"
+    return f"    asm volatile({body}\n        :\n        : {', '.join(ins)});\n"
+
+
+def put_stmt(items):
+    """items: list of (areg, member_expr, value_expr): every lane of up to 6 panels - no EXEC handling at all (EXEC is all ones)"""
+    lines, outs, ins = [], [], []
+    k = len(items)
+    for i, (areg, member, val) in enumerate(items):
+        outs.append(f'"+{{a[{areg}:{areg + 1}]}}"({member})')
+        lo = k + 2 * i
+        lines.append(f'"v_accvgpr_write_b32 a{areg}, %{lo}\\n\\t"')
+        lines.append(f'"v_accvgpr_write_b32 a{areg + 1}, %{lo + 1}\\n\\t"')
+        ins.append(f'"v"(__double2loint({val}))')
+        ins.append(f'"v"(__double2hiint({val}))')
+    lines[-1] = lines[-1][:-5] + '"'
+    body = "\n        ".join(lines)
+    return f"    asm volatile({body}\n        : {', '.join(outs)}\n        : {', '.join(ins)});\n"
 
 
 # ---- the append of a step as code selection: n_h = 3 t is static ----------------------------------------------------------------
@@ -412,7 +429,7 @@ def emit(f):
     for r in range(NTR):
         u = u_of(r)
         full = [g for g in m.groups[r] if g < (u >> 2)]
-        f.write(f"__device__ __forceinline__ void one_hset_row_{r}(unsigned long long mBase, unsigned long long mLast, const double* V) {{\n    unsigned long long sv_;\n    (void)mLast;\n")
+        f.write(f"__device__ __forceinline__ void one_hset_row_{r}(unsigned long long mBase, unsigned long long mLast, const double* V) {{\n    (void)mLast;\n")
         for s_ in range(0, len(full), 12):
             f.write(hidden_set_stmt([(m.reg("p", r, g), f"V[{g}]") for g in full[s_:s_ + 12]], "mBase"))
         if u & 3:
@@ -433,16 +450,16 @@ def emit(f):
         f.write(f"__device__ __forceinline__ void one_hset_gd_{g}(double v) {{\n"
                 f"    asm volatile(\"v_accvgpr_write_b32 a{a}, %0\\n\\tv_accvgpr_write_b32 a{a + 1}, %1\" : : \"v\"(__double2loint(v)), \"v\"(__double2hiint(v)));\n}}\n")
         f.write(f"__device__ __forceinline__ void one_touch_gd_{g}(OnePanels& P) {{ asm volatile(\"\" : \"+{{a[{a}:{a + 1}]}}\"(P.gd[{g}])); }}\n")
-        f.write(f"__device__ __forceinline__ void one_set_gd_{g}(OnePanels& P, unsigned long long mask, double v) {{\n    unsigned long long sv_;\n")
-        f.write(set_stmt([(a, f"P.gd[{g}]", "v")]))
+        f.write(f"__device__ __forceinline__ void one_put_gd_{g}(OnePanels& P, double v) {{\n")
+        f.write(put_stmt([(a, f"P.gd[{g}]", "v")]))
         f.write("}\n")
     # everything to zero, the diagonal tiles to the identity
-    f.write("__device__ __forceinline__ void one_init(OnePanels& P, double inat) {\n    unsigned long long sv_;\n    unsigned long long mask = ~0ull;\n    double z = 0.0;\n")
+    f.write("__device__ __forceinline__ void one_init(OnePanels& P, double inat) {\n    double z = 0.0;\n")
     allp = [(m.reg("p", r, g), member(r, g), "z") for r in range(NTR) for g in m.groups[r]]
     for s in range(0, len(allp), 6):
-        f.write(set_stmt(allp[s:s + 6]))
+        f.write(put_stmt(allp[s:s + 6]))
     for g in m.gd:
-        f.write(set_stmt([(m.reg("gd", g, 0), f"P.gd[{g}]", "inat")]))
+        f.write(put_stmt([(m.reg("gd", g, 0), f"P.gd[{g}]", "inat")]))
     f.write("}\n")
 
     def disp(name, ret, params, args, rng):
@@ -457,7 +474,7 @@ def emit(f):
     disp("one_solve", "void", "OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1", "P, Vu, RN, MK, nh, S0, S1", m.gd)
     disp("one_hset_row", "void", "unsigned long long mBase, unsigned long long mLast, const double* V", "mBase, mLast, V", range(NTR))
     disp("one_gdm", "double", "OnePanels& P, double acc", "P, acc", m.gd)
-    disp("one_set_gd", "void", "OnePanels& P, unsigned long long mask, double v", "P, mask, v", m.gd)
+    disp("one_put_gd", "void", "OnePanels& P, double v", "P, v", m.gd)
     disp("one_hset_gd", "void", "double v", "v", m.gd)
     disp("one_touch_gd", "void", "OnePanels& P", "P", m.gd)
     emit_append(f)
