@@ -176,6 +176,11 @@ def dptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return t.data_ptr()
 
 
+def workspace(nbytes: int, dev) -> torch.Tensor:
+    """An uninitialised device buffer of at least ``nbytes`` bytes (never empty: an empty tensor has no address)."""
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev)
+
+
 def current_stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 

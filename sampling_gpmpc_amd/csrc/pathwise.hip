@@ -260,27 +260,18 @@ int gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* en
                            int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample, const double* U, int32_t u_per_sample,
                            const double* Z, int64_t ldz, const double* V, double* X_traj, double* Y, int32_t* info, void* stream) {
     const std::string me = "gpmpc_pathwise_rollout: ";
-    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
-    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
-    if (H < 0) return fail(GPMPC_E_ARG, me + "H must be >= 0");
+    if (int rc = pw_rollout_check(me, gp, env, M, Ns, ldz, H)) return rc;
     if (Ns > 0 && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && !U)))
         return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj and info are required)");
-    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
-    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (int rc = pw_rollout_check_env(me, gp, env, M, Ns)) return rc;
     if (Ns == 0) return GPMPC_OK;
     PwRollArgs a;
-    a.gp = make_gp_params(gp);
-    a.env = make_env_params(env);
-    a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.X_traj = X_traj, a.Y = Y, a.info = (int*)info;
-    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per_sample != 0, a.u_per = u_per_sample != 0;
+    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_sample, U, u_per_sample, Z, ldz, V, info);
+    a.X_traj = X_traj, a.Y = Y;
     const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
-    if (env->env_id == GPMPC_ENV_PENDULUM1D)
-        hipLaunchKernelGGL(pathwise_rollout_kernel<GPMPC_ENV_PENDULUM1D>, grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(pathwise_rollout_kernel<GPMPC_ENV_CAR_RESIDUAL>, grid, block, 0, (hipStream_t)stream, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
+    return pw_launch_env(env->env_id, [&](auto e) {
+        hipLaunchKernelGGL(pathwise_rollout_kernel<decltype(e)::value>, grid, block, 0, (hipStream_t)stream, a);
+    });
 }
 
 }  // extern "C"

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void pathwise_rollout_vjp_kernel(const PwGradA
             for (int k = 0; k < 1 + D; ++k) y[o][k] = yq[o][k];
         if (t > 0) load_step(t - 1);
         bool fin = true;
-        // the step input, the statements of pw_rollout_step: Y is the sample at exactly this point
+        // the step input, the statements of pw_rollout_step (restated, not shared: DESIGN 4.13d): Y is the sample at exactly this point
 #pragma unroll
         for (int i = 0; i < NU; ++i) {
             const double ufi = ut[i];
@@ -172,29 +172,19 @@ int gpmpc_pathwise_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t
                                const double* Z, int64_t ldz, const double* V, const double* X_traj, const double* Y, const double* gX,
                                double* gx0, double* gU, int32_t* info, void* stream) {
     const std::string me = "gpmpc_pathwise_rollout_vjp: ";
-    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
-    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
-    if (H < 0) return fail(GPMPC_E_ARG, me + "H must be >= 0");
+    if (int rc = pw_rollout_check(me, gp, env, M, Ns, ldz, H)) return rc;
     // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
     if (Ns > 0 && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && (!U || !gU))))
         return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj, gU and info are required)");
-    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
-    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (int rc = pw_rollout_check_env(me, gp, env, M, Ns)) return rc;
     if (Ns == 0) return GPMPC_OK;
     PwGradArgs a;
-    a.gp = make_gp_params(gp);
-    a.env = make_env_params(env);
-    a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.X_traj = X_traj, a.Y = Y, a.gX = gX;
-    a.gx0 = gx0, a.gU = gU, a.info = (int*)info;
-    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per_sample != 0, a.u_per = u_per_sample != 0;
+    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_sample, U, u_per_sample, Z, ldz, V, info);
+    a.X_traj = X_traj, a.Y = Y, a.gX = gX, a.gx0 = gx0, a.gU = gU;
     const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
-    if (env->env_id == GPMPC_ENV_PENDULUM1D)
-        hipLaunchKernelGGL(pathwise_rollout_vjp_kernel<GPMPC_ENV_PENDULUM1D>, grid, block, 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(pathwise_rollout_vjp_kernel<GPMPC_ENV_CAR_RESIDUAL>, grid, block, 0, (hipStream_t)stream, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
+    return pw_launch_env(env->env_id, [&](auto e) {
+        hipLaunchKernelGGL(pathwise_rollout_vjp_kernel<decltype(e)::value>, grid, block, 0, (hipStream_t)stream, a);
+    });
 }
 
 }  // extern "C"

@@ -266,20 +266,13 @@ int gpmpc_pathwise_tube_stats(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t*
                               void* stream) {
     const std::string me = "gpmpc_pathwise_tube_stats: ";
     if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
-    if (int rc = pw_check(me, gp, M, Ns, (int64_t)gp->g_ny * ((int64_t)M + gp->N_r))) return rc;
-    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
-    if (H < 0) return fail(GPMPC_E_ARG, me + "H must be >= 0");
+    if (int rc = pw_rollout_check(me, gp, env, M, Ns, (int64_t)gp->g_ny * ((int64_t)M + gp->N_r), H)) return rc;
     if (offset < 0) return fail(GPMPC_E_ARG, me + "offset must be >= 0");
     if (n_eps < 0 || n_eps > PWS_MAX_EPS) return fail(GPMPC_E_ARG, me + "n_eps must be 0..16");
     if (n_eps > 0 && !eps) return fail(GPMPC_E_ARG, me + "eps is NULL with n_eps > 0");
     for (int k = 0; k < n_eps; ++k)
         if (!(eps[k] >= 0.0 && eps[k] < __builtin_inf())) return fail(GPMPC_E_ARG, me + "eps must be finite and >= 0");
-    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
-    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    if (scale)
-        for (int d = 0; d < env->nx; ++d)
-            if (!(scale[d] > 0.0 && scale[d] < __builtin_inf())) return fail(GPMPC_E_ARG, me + "scale must be finite and > 0");
-    if (int rc = pw_supported(me, gp, M, Ns)) return rc;
+    if (int rc = pw_rollout_check_env(me, gp, env, M, Ns, scale)) return rc;
     const PwStatsLayout l = pws_layout(gp, M, H, env->nx, max_groups);
     if (workspace_bytes < l.bytes)
         return fail(GPMPC_E_ARG, me + "workspace smaller than gpmpc_pathwise_tube_stats_workspace_bytes() for the same max_groups");
@@ -302,11 +295,10 @@ int gpmpc_pathwise_tube_stats(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t*
     a.sup = sup;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)groups), block(256);
-    if (env->env_id == GPMPC_ENV_PENDULUM1D)
-        hipLaunchKernelGGL(pathwise_tube_stats_kernel<GPMPC_ENV_PENDULUM1D>, grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL(pathwise_tube_stats_kernel<GPMPC_ENV_CAR_RESIDUAL>, grid, block, 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
+    if (int rc = pw_launch_env(env->env_id, [&](auto e) {
+            hipLaunchKernelGGL(pathwise_tube_stats_kernel<decltype(e)::value>, grid, block, 0, st, a);
+        }))
+        return rc;
     const long n_act = Ns < a.n_waves ? (long)Ns : a.n_waves;
     hipLaunchKernelGGL(pathwise_tube_stats_finish, dim3((unsigned)((l.entries + PWS_SLOTS + 3) / 4)), block, 0, st, a, l.entries, n_act,
                        (int)n_eps, dev_max, (long long*)dev_arg, box_lo, box_hi, (long long*)n_within, (long long*)n_nonfinite);

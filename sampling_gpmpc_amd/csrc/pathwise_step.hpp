@@ -241,4 +241,40 @@ inline int pw_supported(const std::string& me, const gpmpc_gp_desc_t* gp, int32_
     return GPMPC_OK;
 }
 
+// gpmpc_pathwise_rollout, _rollout_vjp and _tube_stats: the checks in front of an entry point's own NULL-pointer test ...
+inline int pw_rollout_check(const std::string& me, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int32_t M, int64_t Ns,
+                            int64_t ldz, int32_t H) {
+    if (int rc = pw_check(me, gp, M, Ns, ldz)) return rc;
+    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
+    return H < 0 ? fail(GPMPC_E_ARG, me + "H must be >= 0") : GPMPC_OK;
+}
+// ... and those behind it; scale: the statistics' divisors, one per state dimension (NULL: none), read once env->nx is known good
+inline int pw_rollout_check_env(const std::string& me, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, int32_t M, int64_t Ns,
+                                const double* scale = nullptr) {
+    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
+    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
+    for (int d = 0; scale && d < env->nx; ++d)
+        if (!(scale[d] > 0.0 && scale[d] < __builtin_inf())) return fail(GPMPC_E_ARG, me + "scale must be finite and > 0");
+    return pw_supported(me, gp, M, Ns);
+}
+
+// the fields PwRollArgs and PwGradArgs share (each keeps its own layout)
+template <class Args>
+void pw_fill_args(Args& a, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M, const double* omega,
+                  int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample, const double* U, int32_t u_per_sample, const double* Z,
+                  int64_t ldz, const double* V, int32_t* info) {
+    a.gp = make_gp_params(gp), a.env = make_env_params(env);
+    a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.info = (int*)info;
+    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per_sample != 0, a.u_per = u_per_sample != 0;
+}
+
+// launch(env) with the environment as an integral constant (as mom_dispatch), then the launch's status
+template <class Launch>
+int pw_launch_env(int env_id, Launch&& launch) {
+    if (env_id == GPMPC_ENV_PENDULUM1D) launch(std::integral_constant<int, GPMPC_ENV_PENDULUM1D>{});
+    else launch(std::integral_constant<int, GPMPC_ENV_CAR_RESIDUAL>{});
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
 }  // namespace gpmpc

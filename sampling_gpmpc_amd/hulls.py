@@ -122,7 +122,7 @@ def convex_hulls(X: torch.Tensor, dims: Sequence[int] = (0, 1), max_vertices: in
     mv = int(max_vertices)
     ws_bytes = int(lib.gpmpc_hull_workspace_bytes(int(n_points), int(n_sets), mv))
     with torch.cuda.device(dev):
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         out = HullSet(verts=torch.empty(n_sets, max(mv, 0), 2, dtype=torch.float64, device=dev),
                       n_verts=torch.empty(n_sets, dtype=torch.int32, device=dev),
                       area=torch.empty(n_sets, dtype=torch.float64, device=dev),
@@ -176,7 +176,7 @@ def hull_query(h: HullSet, X: torch.Tensor, dims: Sequence[int] = (0, 1), layout
     with torch.cuda.device(dev):
         def new(shape, dtype, want):
             return torch.empty(shape, dtype=dtype, device=dev) if want else None
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         q = HullQuery(tol=tol, n_points=n_points, margin=new((n_points, n_sets), torch.float64, margins),
                       n_inside=new(n_sets, torch.int32, per_set), n_finite=new(n_sets, torch.int32, per_set),
                       min_margin=new(n_sets, torch.float64, per_set), argmin=new(n_sets, torch.int32, per_set),

@@ -24,6 +24,7 @@ import torch.nn.functional as Fn
 
 from . import _lib
 from ._lib import GpmpcError
+from ._planning import adam_update
 from .gp_model import F64, GPHyperParams
 
 MAX_ROWS = 140            # gpmpc_marginal_likelihood: label rows n (include/gpmpc_hip.h)
@@ -252,7 +253,6 @@ def fit_hyperparameters(X: torch.Tensor, Y: torch.Tensor, theta0: torch.Tensor, 
     if free is not None:
         mask = mask & torch.as_tensor(free, dtype=torch.bool, device=dev)
     div = float(pr.n) if normalise else 1.0
-    b1, b2, eps = 0.9, 0.999, 1e-8
     m, v = torch.zeros_like(raw), torch.zeros_like(raw)
     frozen = torch.zeros(B, pr.g_ny, dtype=torch.bool, device=dev)
     info_or = torch.zeros(B, pr.g_ny, dtype=torch.int32, device=dev)
@@ -266,10 +266,7 @@ def fit_hyperparameters(X: torch.Tensor, Y: torch.Tensor, theta0: torch.Tensor, 
         g = raw_gradient(raw, r.grad / div, pr.D)
         upd = mask & ~frozen.unsqueeze(-1)
         g = torch.where(upd, g, torch.zeros_like(g))
-        m_new = torch.lerp(m, g, 1.0 - b1)                           # the operations of torch.optim.Adam's single-tensor step
-        v_new = torch.addcmul(v * b2, g, g, value=1.0 - b2)
-        denom = v_new.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
-        raw_new = torch.addcdiv(raw, m_new, denom, value=-(lr / (1.0 - b1 ** it)))
+        raw_new, m_new, v_new = adam_update(raw, m, v, g, it, lr)
         raw = torch.where(upd, raw_new, raw)
         m, v = torch.where(upd, m_new, m), torch.where(upd, v_new, v)
     theta, noise = theta_from_raw(raw, pr.D)

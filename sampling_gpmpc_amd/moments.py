@@ -17,6 +17,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._planning import adam_update, check_planner_args, like_input, rollout_inputs, squared_violation
 from .hulls import HullSet, convex_hulls
 
 F64 = torch.float64
@@ -107,13 +108,8 @@ class MomentTube:
 def _prepare(plan, env_desc, x0, U, P0):
     """The argument handling of ``moment_rollout_plan``: -> (device, x0, U, P0, B, H) with float64 contiguous device tensors."""
     dev = _lib.require_hip_device(plan.X_r.device)
-    nx, nu = int(env_desc.nx), int(env_desc.nu)
-    x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
-    U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
-    if x0.dim() not in (1, 2) or x0.shape[-1] != nx:
-        raise _lib.GpmpcError(f"x0 must be ({nx},) or (B, {nx})")
-    if U.dim() not in (2, 3) or U.shape[-1] != nu:
-        raise _lib.GpmpcError(f"U must be (H, {nu}) or (B, H, {nu})")
+    nx = int(env_desc.nx)
+    x0, U = rollout_inputs(x0, U, nx, int(env_desc.nu), dev)
     H = int(U.shape[-2])
     sizes = {int(t.shape[0]) for t, per in ((x0, x0.dim() == 2), (U, U.dim() == 3)) if per}
     if P0 is not None:
@@ -187,13 +183,8 @@ class _MomentRollout(torch.autograd.Function):
             return (None,) * 9
         g_x0, g_U, g_P0, _ = _backward(ctx.plan, ctx.env_desc, x0.device, x0, U, P0, B, H, mean, cov, g_mean, g_cov)
         need = ctx.needs_input_grad
-        return (_like_input(g_x0, x0.dim() == 2) if need[0] else None, _like_input(g_U, U.dim() == 3) if need[1] else None,
+        return (like_input(g_x0, x0.dim() == 2) if need[0] else None, like_input(g_U, U.dim() == 3) if need[1] else None,
                 g_P0 if (need[2] and ctx.has_p0) else None, None, None, None, None, None, None)
-
-
-def _like_input(g, per_candidate):
-    """A shared input's gradient is the sum of the candidates' (the kernel writes per candidate: no atomics)."""
-    return g if per_candidate else g.sum(0)
 
 
 def moment_rollout_plan(plan, env_desc, x0: torch.Tensor, U: torch.Tensor, P0: Optional[torch.Tensor] = None,
@@ -232,7 +223,7 @@ def moment_rollout_vjp_plan(plan, env_desc, tube: MomentTube, x0, U, P0=None, g_
     cotangent that is None is zero.  One launch, no host synchronisation."""
     dev, x0, U, P0, B, H = _prepare(plan, env_desc, x0, U, P0)
     g_x0, g_U, g_P0, info = _backward(plan, env_desc, dev, x0, U, P0, B, H, tube.mean, tube.cov, g_mean, g_cov)
-    return _like_input(g_x0, x0.dim() == 2), _like_input(g_U, U.dim() == 3), g_P0, info
+    return like_input(g_x0, x0.dim() == 2), like_input(g_U, U.dim() == 3), g_P0, info
 
 
 def moment_rollout_vjp(agent, tube: MomentTube, x0, U, P0=None, g_mean=None, g_cov=None, use_feedback: Optional[bool] = None):
@@ -260,31 +251,15 @@ def chance_constraint_penalty(tube: MomentTube, rows, beta: float, eps: float = 
     if r.off is not None:
         val = val + r.off[None]
     sd = float(beta) * torch.sqrt(torch.einsum("rd,btde,re->btr", r.E, tube.cov, r.E) + float(eps))
-    lo, hi = r.lo[None, :, :n_lin], r.hi[None, :, :n_lin]
-    zero = torch.zeros_like(val)
-    up = torch.where(torch.isfinite(hi), val + sd - torch.where(torch.isfinite(hi), hi, zero), zero)
-    dn = torch.where(torch.isfinite(lo), torch.where(torch.isfinite(lo), lo, zero) - (val - sd), zero)
-    return (torch.relu(up) ** 2 + torch.relu(dn) ** 2).sum(dim=(1, 2))
-
-
-def _check_plan_inputs(U0, cost, steps, lr):
-    if not callable(cost):
-        raise _lib.GpmpcError("plan_inputs: cost must be a function (tube, U) -> (B,)")
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
-        raise _lib.GpmpcError("plan_inputs: steps must be an integer >= 0")
-    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0.0:
-        raise _lib.GpmpcError("plan_inputs: lr must be a positive number")
-    if not torch.is_tensor(U0) or U0.dim() != 3:
-        raise _lib.GpmpcError("plan_inputs: U0 must be a tensor (B, H, nu): the population of input sequences")
+    return squared_violation(val + sd, val - sd, r.lo[None, :, :n_lin], r.hi[None, :, :n_lin])
 
 
 def plan_inputs_plan(plan, env_desc, x0, U0, cost, steps: int, lr: float, P0=None):
     """``plan_inputs`` for a ``RealDataPlan`` and an environment descriptor."""
-    _check_plan_inputs(U0, cost, steps, lr)
+    check_planner_args("plan_inputs", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
     dev = _lib.require_hip_device(plan.X_r.device)
     U = U0.detach().to(device=dev, dtype=F64).clone()
     B, steps = int(U.shape[0]), int(steps)
-    b1, b2, eps = 0.9, 0.999, 1e-8
     m, v = torch.zeros_like(U), torch.zeros_like(U)
     hist = torch.empty(steps + 1, B, dtype=F64, device=dev)
 
@@ -299,10 +274,7 @@ def plan_inputs_plan(plan, env_desc, x0, U0, cost, steps: int, lr: float, P0=Non
         c = costs(moment_rollout_plan(plan, env_desc, x0, Uc, P0, differentiable=True), Uc)
         hist[it - 1] = c.detach()
         g, = torch.autograd.grad(c.sum(), Uc)                        # the candidates are independent: one backward launch for all
-        m = torch.lerp(m, g, 1.0 - b1)                               # the operations of torch.optim.Adam's single-tensor step
-        v = torch.addcmul(v * b2, g, g, value=1.0 - b2)
-        denom = v.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
-        U = torch.addcdiv(U, m, denom, value=-(lr / (1.0 - b1 ** it)))
+        U, m, v = adam_update(U, m, v, g, it, lr)
     with torch.no_grad():
         hist[steps] = costs(moment_rollout_plan(plan, env_desc, x0, U, P0), U)
     final = hist[steps]
@@ -317,6 +289,6 @@ def plan_inputs(agent, x0, U0, cost, steps: int, lr: float, P0=None, use_feedbac
     (``chance_constraint_penalty`` is one ingredient).  Returns the final ``U (B, H, nu)``, the cost history ``(steps + 1, B)`` - row
     ``k`` is the cost before update ``k + 1``, the last row that of the result - and the index of the best candidate (0-dim, on the
     device).  One forward and one backward launch per iteration, no host round trip inside the loop."""
-    _check_plan_inputs(U0, cost, steps, lr)
+    check_planner_args("plan_inputs", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
     _lib.require_hip_device(agent.torch_device)
     return plan_inputs_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U0, cost, steps, lr, P0)

@@ -26,6 +26,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from ._planning import adam_update, check_planner_args, like_input, rollout_inputs, squared_violation
 
 F64 = torch.float64
 M_STEP, MAX_M, MAX_ROWS = 128, 1024, 64          # include/gpmpc_hip.h, gpmpc_pathwise_*: the limits
@@ -69,6 +70,22 @@ def _plan_of(agent_or_plan):
     return agent_or_plan, None
 
 
+def _omega_for(plan, omega, n_features: int, seed, dev) -> torch.Tensor:
+    """The frequencies of a draw on the device: those given, else ``draw_omega(ell, n_features, seed)``."""
+    d = plan.desc
+    omega = draw_omega(plan.hyper.ell, n_features, seed) if omega is None else omega
+    omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
+    if tuple(omega.shape) != (d.g_ny, n_features // 2, d.D):
+        raise _lib.GpmpcError(f"omega must be ({d.g_ny}, {n_features // 2}, {d.D})")
+    return omega
+
+
+def _mean_sample(plan, agent, omega: torch.Tensor, n_features: int) -> "PathwiseSamples":
+    """The ``Z = 0`` sample of the frequencies ``omega``: its update vector is the plan's ``alpha_r`` and the function the posterior mean."""
+    Z = torch.zeros(1, plan.desc.g_ny * (n_features + plan.desc.N_r), dtype=F64, device=omega.device)
+    return PathwiseSamples._fit(plan, agent, omega, Z, n_features, None, 0)
+
+
 class PathwiseSamples:
     """``Ns`` pathwise posterior samples of a ``RealDataPlan``'s GP as device tensors: ``omega (g_ny, F, D)``, ``Z (Ns, V)`` (the
     normals, ``V = g_ny (M + N_r)``) and ``V (Ns, g_ny, N_r)`` (the update vectors); ``info (Ns)`` int32 of the fit."""
@@ -109,11 +126,7 @@ class PathwiseSamples:
         lib = _lib.load()
         dev = plan.X_r.device
         d = plan.desc
-        if omega is None:
-            omega = draw_omega(plan.hyper.ell, n_features, seed)
-        omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
-        if tuple(omega.shape) != (d.g_ny, n_features // 2, d.D):
-            raise _lib.GpmpcError(f"omega must be ({d.g_ny}, {n_features // 2}, {d.D})")
+        omega = _omega_for(plan, omega, n_features, seed, dev)
         Vn = d.g_ny * (int(n_features) + d.N_r)
         Z = torch.empty(int(Ns), Vn, dtype=F64, device=dev)
         if Ns > 0:
@@ -140,8 +153,7 @@ class PathwiseSamples:
     def mean_only(self) -> "PathwiseSamples":
         """The ``Z = 0`` sample of the same frequencies: its update vector is the plan's ``alpha_r`` and the function the posterior mean."""
         if self._mean is None:
-            Z = torch.zeros(1, self.Z.shape[1], dtype=F64, device=self.Z.device)
-            self._mean = PathwiseSamples._fit(self.plan, self.agent, self.omega, Z, self.n_features, None, 0)
+            self._mean = _mean_sample(self.plan, self.agent, self.omega, self.n_features)
         return self._mean
 
     def _ldz(self) -> int:
@@ -189,28 +201,19 @@ class PathwiseSamples:
         ``differentiable=True``: ``X_traj`` carries a ``grad_fn`` whose backward is one launch of ``gpmpc_pathwise_rollout_vjp``; ``x0`` and
         ``U`` receive gradients if they require them (``Y`` and ``info`` are not differentiable; ``Y`` is kept for the backward when
         ``want_samples``, else evaluated again there); the values are those of the default call, bit for bit."""
-        if differentiable:
-            dev = _lib.require_hip_device(self.Z.device)
-            env_desc = self._env_desc(use_feedback, env_desc)
-            x0, U = _rollout_inputs(self, env_desc, dev, x0, U)
-            X, Y, info = _PathwiseRollout.apply(x0, U, self, env_desc, bool(want_samples))
-            self.last_info = info
-            return (X, Y) if want_samples else X
-        lib = _lib.load()
         dev = _lib.require_hip_device(self.Z.device)
-        if env_desc is None:
-            if self.agent is None:
-                raise _lib.GpmpcError("rollout needs an environment: draw the samples for an Agent or pass env_desc")
-            env_desc = self.agent.env_desc(use_feedback)
-        d = self.plan.desc
-        nx, nu = int(env_desc.nx), int(env_desc.nu)
-        x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
-        U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
-        if x0.dim() not in (1, 2) or x0.shape[-1] != nx or (x0.dim() == 2 and x0.shape[0] != self.Ns):
-            raise _lib.GpmpcError(f"x0 must be ({nx},) or ({self.Ns}, {nx})")
-        if U.dim() not in (2, 3) or U.shape[-1] != nu or (U.dim() == 3 and U.shape[0] != self.Ns):
-            raise _lib.GpmpcError(f"U must be (H, {nu}) or ({self.Ns}, H, {nu})")
-        H = int(U.shape[-2])
+        env_desc = self._env_desc(use_feedback, env_desc)
+        x0, U = rollout_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev, n=self.Ns)
+        X, Y, info = (_PathwiseRollout.apply(x0, U, self, env_desc, bool(want_samples)) if differentiable
+                      else self._launch_rollout(x0, U, env_desc, want_samples))
+        self.last_info = info
+        return (X, Y) if want_samples else X
+
+    def _launch_rollout(self, x0, U, env_desc, want_samples):
+        """One launch of ``gpmpc_pathwise_rollout`` for inputs ``rollout_inputs`` has prepared: ``(X_traj, Y or None, info)``."""
+        lib = _lib.load()
+        dev, d = self.Z.device, self.plan.desc
+        nx, H = int(env_desc.nx), int(U.shape[-2])
         X = torch.empty(self.Ns, nx, H + 1, dtype=F64, device=dev)
         Y = torch.empty(self.Ns, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
         info = torch.zeros(self.Ns, dtype=torch.int32, device=dev)
@@ -218,8 +221,7 @@ class PathwiseSamples:
                                               _lib.dptr(x0), int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), self.Z.data_ptr(),
                                               self._ldz(), _lib.dptr(self.V), _lib.dptr(X), _lib.dptr(Y), _lib.dptr(info),
                                               _lib.current_stream_ptr()), "gpmpc_pathwise_rollout")
-        self.last_info = info
-        return (X, Y) if want_samples else X
+        return X, Y, info
 
 
 def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
@@ -288,18 +290,6 @@ def torch_rollout(samples: PathwiseSamples, x0: torch.Tensor, U: torch.Tensor, e
 # ---------------------------------------------------------------------------------------------------------------------
 # the reverse-mode gradient of the rollout and what it is for
 # ---------------------------------------------------------------------------------------------------------------------
-def _rollout_inputs(samples: PathwiseSamples, env_desc, dev, x0, U):
-    """The argument handling of ``rollout``: float64 contiguous device tensors (the conversions keep an autograd graph)."""
-    nx, nu = int(env_desc.nx), int(env_desc.nu)
-    x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
-    U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
-    if x0.dim() not in (1, 2) or x0.shape[-1] != nx or (x0.dim() == 2 and x0.shape[0] != samples.Ns):
-        raise _lib.GpmpcError(f"x0 must be ({nx},) or ({samples.Ns}, {nx})")
-    if U.dim() not in (2, 3) or U.shape[-1] != nu or (U.dim() == 3 and U.shape[0] != samples.Ns):
-        raise _lib.GpmpcError(f"U must be (H, {nu}) or ({samples.Ns}, H, {nu})")
-    return x0, U
-
-
 def _rollout_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
     """One launch of ``gpmpc_pathwise_rollout_vjp``: per-sample gradients ``(g_x0 (Ns, nx), g_U (Ns, H, nu), info (Ns))``."""
     lib = _lib.load()
@@ -323,19 +313,12 @@ def _rollout_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X)
     return g_x0, g_U, info
 
 
-def _like_input(g, per_sample):
-    """A shared input's gradient is the sum of the samples' (the kernel writes per sample: no atomics)."""
-    return g if per_sample else g.sum(0)
-
-
 class _PathwiseRollout(torch.autograd.Function):
     """``gpmpc_pathwise_rollout`` with ``gpmpc_pathwise_rollout_vjp`` as its backward; ``Y`` and ``info`` carry no gradient."""
 
     @staticmethod
     def forward(ctx, x0, U, samples, env_desc, want_samples):
-        out = samples.rollout(x0, U, want_samples=want_samples, env_desc=env_desc)
-        X, Y = out if want_samples else (out, None)
-        info = samples.last_info
+        X, Y, info = samples._launch_rollout(x0, U, env_desc, want_samples)
         ctx.samples, ctx.env_desc, ctx.has_y = samples, env_desc, Y is not None
         ctx.save_for_backward(x0, U, X, *(() if Y is None else (Y,)))
         ctx.set_materialize_grads(False)
@@ -350,7 +333,7 @@ class _PathwiseRollout(torch.autograd.Function):
         Y = ctx.saved_tensors[3] if ctx.has_y else None
         g_x0, g_U, _ = _rollout_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X)
         need = ctx.needs_input_grad
-        return (_like_input(g_x0, x0.dim() == 2) if need[0] else None, _like_input(g_U, U.dim() == 3) if need[1] else None,
+        return (like_input(g_x0, x0.dim() == 2) if need[0] else None, like_input(g_U, U.dim() == 3) if need[1] else None,
                 None, None, None)
 
 
@@ -362,11 +345,11 @@ def pathwise_rollout_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, u
     synchronisation."""
     dev = _lib.require_hip_device(samples.Z.device)
     env_desc = samples._env_desc(use_feedback, env_desc)
-    x0, U = _rollout_inputs(samples, env_desc, dev, x0, U)
+    x0, U = rollout_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev, n=samples.Ns)
     if not torch.is_tensor(X_traj):
         raise _lib.GpmpcError("X_traj must be the tensor samples.rollout returned")
     g_x0, g_U, info = _rollout_backward(samples, env_desc, x0, U, X_traj, Y, g_X)
-    return _like_input(g_x0, x0.dim() == 2), _like_input(g_U, U.dim() == 3), info
+    return like_input(g_x0, x0.dim() == 2), like_input(g_U, U.dim() == 3), info
 
 
 def sampled_tube_penalty(X_traj: torch.Tensor, rows) -> torch.Tensor:
@@ -391,11 +374,7 @@ def sampled_tube_penalty(X_traj: torch.Tensor, rows) -> torch.Tensor:
         dq = X_traj.permute(0, 2, 1)[:, :, None, :] - r.c[None, None]                 # (Ns, T, n_quad, nx)
         vals.append(torch.einsum("stqi,qij,stqj->stq", dq, r.M, dq))
     val = torch.cat(vals, dim=2)                                                     # (Ns, T, n_rows)
-    lo, hi = r.lo[None], r.hi[None]
-    zero = torch.zeros_like(val)
-    up = torch.where(torch.isfinite(hi), val - torch.where(torch.isfinite(hi), hi, zero), zero)
-    dn = torch.where(torch.isfinite(lo), torch.where(torch.isfinite(lo), lo, zero) - val, zero)
-    return (torch.relu(up) ** 2 + torch.relu(dn) ** 2).sum(dim=(1, 2))
+    return squared_violation(val, val, r.lo[None], r.hi[None])
 
 
 def plan_inputs_sampled(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: float, use_feedback: Optional[bool] = None, env_desc=None):
@@ -406,19 +385,11 @@ def plan_inputs_sampled(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: 
     ``U (H, nu)`` and the cost history ``(steps + 1,)`` - entry ``k`` is the cost before update ``k + 1``, the last that of the result
     (there is one sequence, so no index of a best one).  One forward and one backward launch per iteration, no host round trip inside
     the loop."""
-    if not callable(cost):
-        raise _lib.GpmpcError("plan_inputs_sampled: cost must be a function (X_traj, U) -> (Ns,)")
-    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 0:
-        raise _lib.GpmpcError("plan_inputs_sampled: steps must be an integer >= 0")
-    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or lr <= 0.0:
-        raise _lib.GpmpcError("plan_inputs_sampled: lr must be a positive number")
-    if not torch.is_tensor(U0) or U0.dim() != 2:
-        raise _lib.GpmpcError("plan_inputs_sampled: U0 must be a tensor (H, nu): one input sequence shared by the samples")
+    check_planner_args("plan_inputs_sampled", U0, 2, cost, steps, lr, "(H, nu): one input sequence shared by the samples")
     dev = _lib.require_hip_device(samples.Z.device)
     env_desc = samples._env_desc(use_feedback, env_desc)
     U = U0.detach().to(device=dev, dtype=F64).clone()
     Ns = samples.Ns
-    b1, b2, eps = 0.9, 0.999, 1e-8
     m, v = torch.zeros_like(U), torch.zeros_like(U)
     hist = torch.empty(steps + 1, dtype=F64, device=dev)
 
@@ -434,10 +405,7 @@ def plan_inputs_sampled(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: 
         c = mean_cost(samples.rollout(x0, Uc, want_samples=True, env_desc=env_desc, differentiable=True)[0], Uc)
         hist[it - 1] = c.detach()
         g, = torch.autograd.grad(c, Uc)                                # one backward launch; the sum over the samples is torch's
-        m = torch.lerp(m, g, 1.0 - b1)                                 # the operations of torch.optim.Adam's single-tensor step
-        v = torch.addcmul(v * b2, g, g, value=1.0 - b2)
-        denom = v.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
-        U = torch.addcdiv(U, m, denom, value=-(lr / (1.0 - b1 ** it)))
+        U, m, v = adam_update(U, m, v, g, it, lr)
     with torch.no_grad():
         hist[steps] = mean_cost(samples.rollout(x0, U, env_desc=env_desc), U)
     return U, hist
@@ -498,20 +466,14 @@ def pathwise_tube_stats(agent_or_plan, x0, U, Ns: int, n_features: int, seed: in
     Ns, M, offset = int(Ns), int(n_features), int(offset)
     if Ns < 1:
         raise _lib.GpmpcError("pathwise_tube_stats needs Ns >= 1")
-    if omega is None:
-        omega = draw_omega(plan.hyper.ell, M, seed)
-    omega = torch.as_tensor(omega, dtype=F64).to(dev).contiguous()
-    if tuple(omega.shape) != (d.g_ny, M // 2, d.D):
-        raise _lib.GpmpcError(f"omega must be ({d.g_ny}, {M // 2}, {d.D})")
+    omega = _omega_for(plan, omega, M, seed, dev)
     nx, nu = int(env_desc.nx), int(env_desc.nu)
-    x0 = torch.as_tensor(x0, dtype=F64).to(dev).contiguous()
-    U = torch.as_tensor(U, dtype=F64).to(dev).contiguous()
-    if tuple(x0.shape) != (nx,) or U.dim() != 2 or U.shape[1] != nu:
-        raise _lib.GpmpcError(f"x0 must be ({nx},) and U (H, {nu}): shared by the samples")
+    x0, U = rollout_inputs(x0, U, nx, nu, dev, n=Ns)
+    if x0.dim() != 1 or U.dim() != 2:
+        raise _lib.GpmpcError(f"pathwise_tube_stats takes x0 ({nx},) and U (H, {nu}) shared by the samples")
     H = int(U.shape[0])
     if centre is None:
-        Z0 = torch.zeros(1, d.g_ny * (M + d.N_r), dtype=F64, device=dev)
-        centre = PathwiseSamples._fit(plan, agent, omega, Z0, M, None, 0).rollout(x0, U, env_desc=env_desc)[0]
+        centre = _mean_sample(plan, agent, omega, M).rollout(x0, U, env_desc=env_desc)[0]
     centre = torch.as_tensor(centre, dtype=F64).to(dev).contiguous()
     if tuple(centre.shape) != (nx, H + 1):
         raise _lib.GpmpcError(f"centre must be ({nx}, {H + 1}): the layout of one sample of the tube")
@@ -534,7 +496,7 @@ def pathwise_tube_stats(agent_or_plan, x0, U, Ns: int, n_features: int, seed: in
     n_within = torch.zeros(len(eps), dtype=torch.int64, device=dev) if eps else None
     n_nonfinite = torch.zeros(1, dtype=torch.int64, device=dev)
     ws_bytes = int(lib.gpmpc_pathwise_tube_stats_workspace_bytes(d, M, H, nx, len(eps), groups))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(ws_bytes, dev)
     with torch.cuda.device(dev):
         _lib.check(lib.gpmpc_pathwise_tube_stats(d, env_desc, _lib.dptr(plan.buf), _lib.dptr(plan.X_r), _lib.dptr(plan.Y_r), M,
                                                  _lib.dptr(omega), int(seed) & ((1 << 64) - 1), offset, Ns, H, _lib.dptr(x0), _lib.dptr(U),

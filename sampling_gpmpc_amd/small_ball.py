@@ -122,7 +122,7 @@ def sup_deviation(root: torch.Tensor, Ns: int, eps: Union[float, Sequence[float]
     with torch.cuda.device(dev):
         def new(shape, dtype, want):
             return torch.empty(shape, dtype=dtype, device=dev) if want else None
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         r = SmallBall(Ns=Ns, eps=tuple(eps_l), offset=offset,
                       n_within=new(n_eps, torch.int64, n_eps > 0),
                       n_within_out=new((g_ny, n_eps), torch.int64, n_eps > 0 and want_per_output),

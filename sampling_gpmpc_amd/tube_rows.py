@@ -126,7 +126,7 @@ def tube_rows(X: torch.Tensor, rows: TubeRows, tol: float = 0.0, values: bool = 
         def new(shape, dtype, want):
             return torch.empty(shape, dtype=dtype, device=dev) if want else None
         ws_bytes = int(lib.gpmpc_tube_rows_workspace_bytes(Ns, T, r.n_lin, r.n_quad)) if per_row else 0
-        ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         out = TubeRowsResult(tol=float(tol), Ns=Ns, val=new((Ns, T, n_rows), F64, values),
                              grad=new((Ns, T, r.n_quad, nx), F64, gradients), n_viol=new((T, n_rows), torch.int32, per_row),
                              min_margin=new((T, n_rows), F64, per_row), argmin=new((T, n_rows), torch.int32, per_row),

@@ -85,7 +85,11 @@ def test_header_and_sources_carry_the_declaration_and_the_contract():
     csrc = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
     src = open(os.path.join(csrc, "pathwise_grad.hip")).read()
     assert "pw_eval_point<D, true>" in src and "env_jacobian_ct<ENV>" in src and "env_input_jacobian_ct<ENV>" in src
-    assert "pw_check(" in src and "pw_supported(" in src
+    assert "pw_rollout_check(" in src and "pw_rollout_check_env(" in src
+    step = open(os.path.join(csrc, "pathwise_step.hpp")).read()
+    first = step[step.index("inline int pw_rollout_check("):step.index("inline int pw_rollout_check_env(")]
+    second = step[step.index("inline int pw_rollout_check_env("):step.index("void pw_fill_args(")]
+    assert "pw_check(" in first and "pw_supported(" in second
     assert "atomicAdd" not in src and "__hip_atomic" not in src and "__atomic" not in src and "__shared__" not in src
     assert '"pathwise_grad.hip"' in open(os.path.join(csrc, "build.py")).read()
     assert "env_input_jacobian_ct" in open(os.path.join(csrc, "moments_step.hpp")).read()
