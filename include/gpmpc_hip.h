@@ -950,6 +950,91 @@ int     gpmpc_pathwise_tube_stats(const gpmpc_gp_desc_t* gp, const gpmpc_env_des
                                   int64_t* n_nonfinite /* (1) */, int32_t max_groups, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
+/*
+ * gpmpc_robust_tube_rollout - the robust ellipsoidal over-approximation of the reachable set of B candidates over H steps in one
+ * launch: Koller, Berkenkamp, Turchetta, Krause, "Learning-based MPC for safe exploration" (2018), section IV.  The set at step t
+ * is {x : (x - p_t)^T Q_t^-1 (x - p_t) <= 1}.  One candidate per lane, mapping and staging of gpmpc_moment_rollout.  An additive
+ * entry point: the ABI version stays 12.
+ * Replaces: the loop of reference benchmarking/robust_tube_based_GPMPC_koller.py:277-307 around onestep_reachability of the
+ * external repository safe-exploration-koller - one nominal trajectory at a time on the host.  That repository was not available:
+ * the recursion below is written from the paper's formulae and pinned by two independent CPU references
+ * (tests/robust_tube_reference.py), not by a run of that library.
+ *
+ * For candidate b and t = 0..H-1, from p_0 = x0[b] and Q_0 = Q0[b] (zero when Q0 is NULL: the state is a point), nx the state
+ * dimension, K the feedback gain (0 when env.use_feedback is off):
+ *   1. u_t, xi_t, the GP mean m, its gradient and the clamped variance s, p_{t+1} = env_step(p_t, u_t, m) and the closed-loop
+ *      Jacobian A_t exactly as steps 1 - 5 of gpmpc_moment_rollout: the kernels call the same device functions, and M comes out
+ *      bit-equal to the M of that entry point for the same inputs;
+ *   2. Qbar = A_t Q_t A_t^T;
+ *   3. r2 = max(lambda_max(W Q_t W^T), 0), W the upper Cholesky factor of I + K^T K (formed on the host side of this call): the
+ *      largest |(x - p, K (x - p))|^2 over the set; lambda_max by 8 cyclic Jacobi sweeps in registers;
+ *   4. the remainder boxes  ub_d = 0.5 l_mu[d] r2  (linearisation of the mean) and
+ *      sb_d = beta (sqrt(gdiag_d) + l_sigma[d] sqrt(r2)),  gdiag the diagonal of B_d diag(s) B_d^T;
+ *   5. their outer ellipsoids  Q_mu = nx diag(ub^2),  Q_sig = nx diag(sb^2)  (a box with half-widths w lies in nx diag(w^2));
+ *   6. Q_{t+1} = (Q_sig (+) Q_mu) (+) Qbar, where X (+) Y = (1 + 1/c) X + (1 + c) Y, c = sqrt(tr X / tr Y), is the trace-minimal
+ *      outer ellipsoid of the Minkowski sum; X (+) Y = X when tr Y == 0 and Y when tr X == 0, so Q_0 = 0 gives
+ *      Q_1 = nx diag(beta^2 gdiag).  One triangle is computed and mirrored: Q is exactly symmetric (of Q0 the lower triangle is read).
+ *   x0, x0_per_candidate, U, u_per_candidate   as gpmpc_moment_rollout
+ *   Q0      [dev] (B, nx, nx) or NULL
+ *   l_mu    [dev] (B, nx) if l_per_candidate else (nx): the Lipschitz constants of the gradient of the one-step mean, per state
+ *   l_sigma [dev] the same shapes: the Lipschitz constants of the standard deviation
+ *   beta    the confidence scaling of the GP (a scalar)
+ *   M    [dev] (B, nx, H+1)          out: the centres p_t, tube layout
+ *   Q    [dev] (B, H+1, nx, nx)      out
+ *   R2   [dev] (B, H)                out or NULL: r2 of every step
+ *   Sd   [dev] (B, H, nx)            out or NULL: gdiag of every step
+ *   Jz   [dev] (B, H, nx, nx+nu)     out or NULL: [d f / d x | d f / d u] of the OPEN-loop one-step mean map at (p_t, u_t) (the
+ *                                    Jacobian of step 5 of gpmpc_moment_rollout with the feedback flag cleared, and B_t): what a
+ *                                    Lipschitz estimate of the mean's gradient needs
+ *   info [dev] (B) int32             out: OR of GPMPC_INFO_VAR_CLAMPED and GPMPC_INFO_NONFINITE over the steps
+ * Non-finite values, as gpmpc_moment_rollout: a candidate whose x0, Q0, l_mu, l_sigma (or beta) is not finite has NaN in every
+ * output; when anything computed in step t is not finite - with large constants Q overflows within a few steps, which is a result
+ * and not an error - R2, Sd and Jz of the steps >= t and M and Q of the steps > t are NaN.  Either way the candidate carries
+ * GPMPC_INFO_NONFINITE; no other candidate is touched.
+ * Reproducibility: a candidate's results are the same bits whatever B is and wherever it stands in the batch.
+ * Limits and errors are those of gpmpc_moment_rollout: D = 2, both environments, any X_r, at most 64 label rows, B < 2^31;
+ * GPMPC_E_ARG / GPMPC_E_UNSUPPORTED before any device work (required with B > 0: plan, X_r, x0, l_mu, l_sigma, M, Q, info, and U
+ * when H > 0; a feedback gain that is not finite).  B == 0: nothing is launched and the array pointers are not looked at.  No
+ * workspace, no host round trip, everything goes to `stream`.
+ */
+int     gpmpc_robust_tube_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                  int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                                  int32_t u_per_candidate, const double* Q0 /* NULL or (B, nx, nx) */, const double* l_mu,
+                                  const double* l_sigma /* (nx) or (B, nx) */, int32_t l_per_candidate, double beta,
+                                  double* M /* (B, nx, H+1) */, double* Q /* (B, H+1, nx, nx) */, double* R2 /* (B, H) or NULL */,
+                                  double* Sd /* (B, H, nx) or NULL */, double* Jz /* (B, H, nx, nx+nu) or NULL */,
+                                  int32_t* info /* (B) */, void* stream);
+
+/*
+ * gpmpc_pairwise_lipschitz - the sampled Lipschitz constant of G vector functions over N points: for every group g
+ *   out_max[g] = max over i < j of |F[i,g,:] - F[j,g,:]|_2 / (|X[i,:] - X[j,:]|_2 + eps),
+ * as a tiled sweep over the N (N - 1) / 2 pairs that never forms an N x N array.  Additive entry points: the ABI version stays 12.
+ * Replaces: reference benchmarking/robust_tube_based_GPMPC_koller.py:34-44 (estimate_Lipschitz_constant: N x N x d tensors on the
+ * host, eps = 1e-6 - fine for the 50 points of one logged trajectory, impossible on a grid of 10^4 .. 10^5 points).
+ *   X    [dev] (N, dx);  F [dev] (N, G, df);  eps >= 0, finite
+ *   out_max  [dev] (G)               out
+ *   out_pair [dev] (G, 2) int64      out: the pair (i, j), i < j, that attains the maximum; on a tie the lexicographically lowest
+ *   out_skipped [dev] (1) int64      out or NULL: the number of rows that hold a non-finite entry (in X or in any group of F); such a
+ *                                    row takes part in no pair of any group
+ *   max_blocks   persistent workgroups walk the tile pairs on a grid of at most max_blocks workgroups (<= 0: the library chooses,
+ *                1024; at most 65536)
+ *   workspace [dev], workspace_bytes >= gpmpc_pairwise_lipschitz_workspace_bytes of the same N, dx, G, df, max_blocks: one record
+ *                per workgroup and group
+ * N < 2, or no pair of finite rows: out_max = 0 and out_pair = (-1, -1).
+ * Reproducibility: a pair's ratio depends on the pair alone (fixed summation order), and the maximum is taken under a total order
+ * (larger ratio, then lower i, then lower j) per thread, per wave by shuffles, per workgroup through LDS and over the workgroups'
+ * records by a finishing kernel - no atomics - so all outputs are bit-identical for every max_blocks.
+ * Limits: dx <= 8, df <= 8, G <= 8, N <= 2^20; GPMPC_E_UNSUPPORTED beyond.  GPMPC_E_ARG (before any device work): N < 0; dx, G or
+ * df < 1; eps negative or not finite; max_blocks > 65536; NULL out_max, out_pair or workspace; with N > 0 NULL X or F;
+ * workspace_bytes below the size function's value.  The size function returns 0 for sizes it rejects.  No hidden allocation, no
+ * host round trip, everything goes to `stream`.
+ */
+size_t  gpmpc_pairwise_lipschitz_workspace_bytes(int64_t N, int32_t dx, int32_t G, int32_t df, int32_t max_blocks);
+int     gpmpc_pairwise_lipschitz(int64_t N, int32_t dx, int32_t G, int32_t df, const double* X /* (N, dx) */,
+                                 const double* F /* (N, G, df) */, double eps, double* out_max /* (G) */,
+                                 int64_t* out_pair /* (G, 2) */, int64_t* out_skipped /* (1) or NULL */, int32_t max_blocks,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

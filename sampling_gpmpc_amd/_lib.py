@@ -29,7 +29,7 @@ INFO_ROOT_EIGH = 0x0080
 INFO_EIGH_NOCONV = 0x0100
 INFO_STATE_FULL = 0x0200
 INFO_BAD_HYPER = 0x0400                                 # gpmpc_marginal_likelihood
-INFO_NONFINITE = 0x0800                                 # gpmpc_moment_rollout, gpmpc_pathwise_*
+INFO_NONFINITE = 0x0800                                 # gpmpc_moment_rollout, gpmpc_robust_tube_rollout, gpmpc_pathwise_*
 # gpmpc_convex_hulls: per-set info word
 HULL_OVERFLOW, HULL_NONFINITE, HULL_EMPTY, HULL_DEGENERATE = 0x1, 0x2, 0x4, 0x8
 # gpmpc_hull_query: per-set info word
@@ -123,6 +123,10 @@ SYMBOLS = {
     "gpmpc_pathwise_tube_stats": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _P, _I32, _P, C.c_uint64, _I64, _I64, _I32,
                                             _P, _P, _P, C.POINTER(C.c_double), _I32, C.POINTER(C.c_double), _P, _P, _P, _P, _P, _P, _P,
                                             _I32, _P, _SZ, _P]),
+    "gpmpc_robust_tube_rollout": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _P, _P,
+                                            _I32, _D, _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_pairwise_lipschitz_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
+    "gpmpc_pairwise_lipschitz": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _D, _P, _P, _P, _I32, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,372 @@
+// robust_tube_kernel: the robust ellipsoidal over-approximation of B candidates (Koller, Berkenkamp, Turchetta, Krause, "Learning-
+// based MPC for safe exploration", 2018, section IV), whole horizon in one launch (semantics: include/gpmpc_hip.h,
+// gpmpc_robust_tube_rollout).  gfx950, wave64.
+//
+// Mapping and staging are those of moment_rollout_kernel (moments.hip): ONE CANDIDATE PER LANE, the packed L_rr^-1 triangles, alpha and
+// X_r staged in LDS by mom_stage, the GP of a step by mom_gp_pass1 / mom_variance, the environment by the env_*_ct functions of
+// moments_step.hpp - so the centres p_t are the means of the moment rollout bit for bit.  What is new is the shape matrix: instead of
+// P+ = A P A^T + G diag(s) G^T the step sums three ellipsoids by their trace-minimal outer ellipsoid,
+//   Q+ = (nx diag(sb^2) (+) nx diag(ub^2)) (+) A Q A^T,
+// the boxes sb (confidence interval of the GP plus the Lipschitz remainder of its standard deviation) and ub (the remainder of the
+// linearisation of the mean) growing with r2 = lambda_max(W Q W^T), the largest squared distance |(x - p, K (x - p))|^2 over the set.
+// lambda_max of the symmetric nx x nx matrix (nx <= 4) is taken in registers by cyclic Jacobi sweeps with compile-time indices.
+// The centre (NX) and the lower triangle of Q (NX (NX + 1) / 2 <= 10 entries) stay in registers across the step loop.
+// Work per candidate-step: the GP pass of the moment rollout, then ~4 NX^3 for A Q A^T and W Q W^T and JAC_SWEEPS NX (NX - 1) / 2 rotations.
+#include "moments_step.hpp"
+
+#include <cmath>
+
+namespace gpmpc {
+
+constexpr int ROB_MAX_NX = 4;             // the largest state dimension of the two environments
+
+struct RobustArgs : MomentStepArgs {
+    const double *Q0, *l_mu, *l_sigma;
+    int l_per;
+    double beta;
+    double W[ROB_MAX_NX][ROB_MAX_NX];                                  // upper Cholesky factor of I + K^T K (nx <= 4), identity without feedback
+    double *M, *Q, *R2, *Sd, *Jz;
+    int* info;
+};
+
+constexpr int JAC_SWEEPS = 8;              // cyclic Jacobi converges quadratically: a 4 x 4 matrix is diagonal to rounding after 5 - 6 sweeps
+
+// The largest eigenvalue of the symmetric matrix whose lower triangle is T (destroyed), by cyclic Jacobi; *abs_sum receives the sum of
+// the |diagonal| after the sweeps (NaN / inf if anything in T was).  Not clamped.
+template <int NX>
+__host__ __device__ __forceinline__ double sym_lambda_max(double (&T)[NX][NX], double& abs_sum) {
+#pragma unroll 1
+    for (int sweep = 0; sweep < JAC_SWEEPS; ++sweep) {
+#pragma unroll
+        for (int p = 0; p < NX - 1; ++p)
+#pragma unroll
+            for (int q = p + 1; q < NX; ++q) {
+                const double apq = T[q][p];
+                // tan of the rotation angle: the smaller root of t^2 + 2 theta t - 1 = 0, theta = (a_qq - a_pp) / (2 a_pq)
+                double t = 0.0;
+                if (apq != 0.0) {
+                    const double theta = (T[q][q] - T[p][p]) / (2.0 * apq);
+                    const double den = fabs(theta) + sqrt(fma(theta, theta, 1.0));
+                    t = (theta < 0.0 ? -1.0 : 1.0) / den;            // theta^2 overflows: den = inf, t = 0
+                }
+                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+                T[p][p] = fma(-t, apq, T[p][p]);
+                T[q][q] = fma(t, apq, T[q][q]);
+                T[q][p] = (apq != 0.0) ? 0.0 : apq;                 // NaN stays
+#pragma unroll
+                for (int r = 0; r < NX; ++r) {
+                    if (r == p || r == q) continue;
+                    double& arp = (r > p) ? T[r][p] : T[p][r];
+                    double& arq = (r > q) ? T[r][q] : T[q][r];
+                    const double vp = arp, vq = arq;
+                    arp = fma(c, vp, -(s * vq));
+                    arq = fma(s, vp, c * vq);
+                }
+            }
+    }
+    double lam = T[0][0];
+    abs_sum = fabs(T[0][0]);
+#pragma unroll
+    for (int i = 1; i < NX; ++i) {
+        abs_sum += fabs(T[i][i]);
+        lam = (T[i][i] > lam) ? T[i][i] : lam;
+    }
+    return lam;
+}
+
+// c of X (+) Y = (1 + 1/c) X + (1 + c) Y, c = sqrt(tr X / tr Y); X (+) Y = X when tr Y == 0 and Y when tr X == 0: -> the two weights
+__host__ __device__ __forceinline__ void ellipsoid_sum_weights(double trx, double try_, double& wx, double& wy) {
+    if (try_ == 0.0) {
+        wx = 1.0, wy = 0.0;
+    } else if (trx == 0.0) {
+        wx = 0.0, wy = 1.0;
+    } else {
+        const double c = sqrt(trx / try_);
+        wx = 1.0 + 1.0 / c;
+        wy = 1.0 + c;
+    }
+}
+
+template <int ENV, int NRP, bool HG>
+__global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
+    constexpr int TRI = mom_col_ofs<NRP>(NRP);
+    __shared__ __attribute__((aligned(16))) double Ltri[G_NY * TRI];
+    __shared__ double alpha_s[G_NY * NRP];
+    __shared__ double xr_s[2 * NRP];
+    const GpParams& gp = a.gp;
+    const int n = gp.n_r;                                              // <= NRP (host)
+    mom_stage<NRP, G_NY>(a, Ltri, alpha_s, xr_s, threadIdx.x, blockDim.x);
+    __syncthreads();
+
+    const long braw = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool active = braw < a.B;
+    const long b = active ? braw : a.B - 1;
+    const int H = a.H;
+    const double nan = __builtin_nan("");
+    const double beta = a.beta;
+
+    double x[NX], Q[NX][NX], lmu[NX], lsig[NX];                        // Q: the lower triangle [i][j], j <= i, is live
+    double chk = fabs(beta);
+#pragma unroll
+    for (int d = 0; d < NX; ++d) {
+        x[d] = a.x0[(a.x0_per ? b * NX : 0) + d];
+        lmu[d] = a.l_mu[(a.l_per ? b * NX : 0) + d];
+        lsig[d] = a.l_sigma[(a.l_per ? b * NX : 0) + d];
+        chk += fabs(x[d]) + fabs(lmu[d]) + fabs(lsig[d]);
+    }
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) {
+            // Q0 is read as given and symmetrised by taking its lower triangle
+            Q[i][j] = (a.Q0 && j <= i) ? a.Q0[(b * NX + i) * NX + j] : 0.0;
+            chk += fabs(Q[i][j]);
+        }
+    bool dead = !mom_finite(chk);
+    int info_acc = dead ? GPMPC_INFO_NONFINITE : 0;
+    if (dead) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            x[i] = nan;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) Q[i][j] = nan;
+        }
+    }
+    auto store_state = [&](int t) {
+        if (!active) return;
+#pragma unroll
+        for (int d = 0; d < NX; ++d) a.M[(b * NX + d) * (H + 1) + t] = x[d];
+        double* Qt = a.Q + (b * (H + 1) + t) * (NX * NX);
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) Qt[i * NX + j] = (j <= i) ? Q[i][j] : Q[j][i];
+    };
+
+#pragma unroll 1
+    for (int t = 0; t < H; ++t) {
+        store_state(t);
+        double u[NU], xi[2];
+        chk = 0.0;
+        env_input_ct<ENV>(a.env, x, a.U + ((a.u_per ? b * H : 0) + t) * NU, u, xi);
+#pragma unroll
+        for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
+
+        double gm[G_NY], gs[G_NY], gd[G_NY][2];                        // posterior mean, variance, d mean / d xi per output
+#pragma unroll 1
+        for (int o = 0; o < G_NY; ++o) {
+            const double il[2] = {gp.inv_l2[o][0], gp.inv_l2[o][1]};
+            double acc[MOM_ACC<NRP>];
+#pragma unroll
+            for (int i = 0; i < NRP; ++i) acc[i] = 0.0;
+            MomGpSums g;
+            const double ss = mom_gp_pass1<NRP, HG, false>(Ltri + o * TRI, alpha_s + o * NRP, xr_s, n, il, gp.os[o], xi, acc, g);
+            double s;
+            mom_variance(gp, gp.os[o], ss, s, info_acc);
+            chk += fabs(g.m) + fabs(s) + fabs(g.d0) + fabs(g.d1);
+#pragma unroll
+            for (int oo = 0; oo < G_NY; ++oo)
+                if (oo == o) gm[oo] = g.m, gs[oo] = s, gd[oo][0] = g.d0, gd[oo][1] = g.d1;
+        }
+
+        double dxi[2][NX], A[NX][NX], xn[NX], gdiag[NX];               // gdiag: the diagonal of G diag(s) G^T
+        env_jacobian_ct<ENV>(a.env, x, gm, gd, dxi, A);
+        env_step_ct<ENV>(a.env, x, u, gm, xn);
+        env_noise_diag_ct<ENV>(x, gs, gdiag);
+
+        // ---- Qbar = A Q A^T, lower triangle --------------------------------------------------------------------------------
+        double AQ[NX][NX], Qn[NX][NX];
+        double tr_bar = 0.0;
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int c = 0; c < NX; ++c) {
+                double s_ = 0.0;
+#pragma unroll
+                for (int kk = 0; kk < NX; ++kk) s_ = fma(A[i][kk], (c <= kk) ? Q[kk][c] : Q[c][kk], s_);
+                AQ[i][c] = s_;
+            }
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                double s_ = 0.0;
+#pragma unroll
+                for (int kk = 0; kk < NX; ++kk) s_ = fma(AQ[i][kk], A[j][kk], s_);
+                Qn[i][j] = s_;
+                if (i == j) tr_bar += s_;
+            }
+
+        // ---- r2 = lambda_max(W Q W^T), W upper triangular ------------------------------------------------------------------
+        double WQ[NX][NX], T[NX][NX];
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int c = 0; c < NX; ++c) {
+                double s_ = 0.0;
+#pragma unroll
+                for (int kk = i; kk < NX; ++kk) s_ = fma(a.W[i][kk], (c <= kk) ? Q[kk][c] : Q[c][kk], s_);
+                WQ[i][c] = s_;
+            }
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j < NX; ++j) {
+                double s_ = 0.0;
+                if (j <= i) {
+#pragma unroll
+                    for (int kk = j; kk < NX; ++kk) s_ = fma(WQ[i][kk], a.W[j][kk], s_);
+                }
+                T[i][j] = s_;
+            }
+        double lam_abs;
+        double r2 = sym_lambda_max<NX>(T, lam_abs);
+        chk += lam_abs;
+        r2 = (r2 < 0.0) ? 0.0 : r2;                                    // NaN stays (and is in chk)
+        const double r1 = sqrt(r2);
+
+        // ---- the remainder boxes, their outer ellipsoids nx diag(b^2), and the two sums --------------------------------------
+        double qs[NX], qm[NX];
+        double tr_s = 0.0, tr_m = 0.0;
+#pragma unroll
+        for (int d = 0; d < NX; ++d) {
+            const double ub = 0.5 * lmu[d] * r2;
+            const double sb = beta * (sqrt(gdiag[d]) + lsig[d] * r1);
+            qs[d] = (double)NX * (sb * sb);
+            qm[d] = (double)NX * (ub * ub);
+            tr_s += qs[d];
+            tr_m += qm[d];
+        }
+        double ws, wm, wd, wb;
+        ellipsoid_sum_weights(tr_s, tr_m, ws, wm);
+        double tr_d = 0.0;
+#pragma unroll
+        for (int d = 0; d < NX; ++d) {
+            qs[d] = ws * qs[d] + wm * qm[d];                           // Q_sig (+) Q_mu, diagonal
+            tr_d += qs[d];
+        }
+        ellipsoid_sum_weights(tr_d, tr_bar, wd, wb);
+#pragma unroll
+        for (int i = 0; i < NX; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) {
+                double v = wb * Qn[i][j];
+                if (i == j) v += wd * qs[i];
+                Qn[i][j] = v;
+                chk += fabs(v);
+            }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            chk += fabs(xn[i]);
+#pragma unroll
+            for (int c = 0; c < NX; ++c) chk += fabs(A[i][c]);
+        }
+        if (!dead && !mom_finite(chk)) {
+            dead = true;
+            info_acc |= GPMPC_INFO_NONFINITE;
+        }
+        if (active) {
+            if (a.R2) a.R2[b * H + t] = dead ? nan : r2;
+            if (a.Sd) {
+#pragma unroll
+                for (int d = 0; d < NX; ++d) a.Sd[(b * H + t) * NX + d] = dead ? nan : gdiag[d];
+            }
+            if (a.Jz) {
+                // [d f / d x | d f / d u] of the open-loop one-step mean map at (p_t, u_t): the feedback flag cleared
+                EnvParams e0 = a.env;
+                e0.use_feedback = 0;
+                double dxi0[2][NX], A0[NX][NX], B0[NX][NU];
+                env_jacobian_ct<ENV>(e0, x, gm, gd, dxi0, A0);
+                env_input_jacobian_ct<ENV>(a.env, x, gd, B0);
+                double* Jt = a.Jz + (b * H + t) * (NX * (NX + NU));
+#pragma unroll
+                for (int i = 0; i < NX; ++i) {
+#pragma unroll
+                    for (int c = 0; c < NX; ++c) Jt[i * (NX + NU) + c] = dead ? nan : A0[i][c];
+#pragma unroll
+                    for (int c = 0; c < NU; ++c) Jt[i * (NX + NU) + NX + c] = dead ? nan : B0[i][c];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            x[i] = dead ? nan : xn[i];
+#pragma unroll
+            for (int j = 0; j <= i; ++j) Q[i][j] = dead ? nan : Qn[i][j];
+        }
+    }
+    store_state(H);
+    if (active) a.info[b] = info_acc;
+}
+
+template <int ENV, int NRP, bool HG>
+static int robust_launch(const RobustArgs& a, hipStream_t st) {
+    const unsigned grid = (unsigned)((a.B + 63) / 64);
+    hipLaunchKernelGGL((robust_tube_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// W upper triangular with W^T W = I + K^T K (K: the first nu rows of env.K when the feedback is on, else 0): positive definite, the
+// Cholesky recursion cannot break down for finite K
+static bool robust_fill_w(RobustArgs& a, const gpmpc_env_desc_t* env) {
+    constexpr int MW = ROB_MAX_NX;
+    const int nx = env->nx;
+    double S[MW][MW];
+    for (int i = 0; i < MW; ++i)
+        for (int j = 0; j < MW; ++j) {
+            double s = (i == j) ? 1.0 : 0.0;
+            if (env->use_feedback && i < nx && j < nx)
+                for (int r = 0; r < env->nu; ++r) s += env->K[r][i] * env->K[r][j];
+            S[i][j] = s;
+            a.W[i][j] = 0.0;
+        }
+    for (int i = 0; i < MW; ++i)
+        for (int j = i; j < MW; ++j) {                                   // row i of the upper factor
+            double s = S[i][j];
+            for (int k = 0; k < i; ++k) s -= a.W[k][i] * a.W[k][j];
+            if (i == j) {
+                if (!(s > 0.0) || !std::isfinite(s)) return false;
+                a.W[i][i] = std::sqrt(s);
+            } else {
+                a.W[i][j] = s / a.W[i][i];
+            }
+        }
+    return true;
+}
+
+}  // namespace gpmpc
+
+using namespace gpmpc;
+
+extern "C" {
+
+int gpmpc_robust_tube_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r, int64_t B,
+                              int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
+                              const double* Q0, const double* l_mu, const double* l_sigma, int32_t l_per_candidate, double beta,
+                              double* M, double* Q, double* R2, double* Sd, double* Jz, int32_t* info, void* stream) {
+    const std::string me = "gpmpc_robust_tube_rollout: ";
+    if (int rc = mom_check_args(me, gp, env, plan, X_r, B, H, x0, U, M, Q, info, false, nullptr)) return rc;
+    if (B > 0 && (!l_mu || !l_sigma)) return fail(GPMPC_E_ARG, me + "NULL pointer (l_mu and l_sigma are required)");
+    if (B == 0) return GPMPC_OK;
+    RobustArgs a;
+    mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
+    a.Q0 = Q0;
+    a.l_mu = l_mu;
+    a.l_sigma = l_sigma;
+    a.l_per = l_per_candidate != 0;
+    a.beta = beta;
+    if (!robust_fill_w(a, env)) return fail(GPMPC_E_ARG, me + "the feedback gain K is not finite");
+    a.M = M;
+    a.Q = Q;
+    a.R2 = R2;
+    a.Sd = Sd;
+    a.Jz = Jz;
+    a.info = (int*)info;
+    return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
+        return robust_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"
