@@ -5,9 +5,11 @@
 
 #include <cmath>
 
+#include "min_index.hpp"   // finite1
+
 namespace gpmpc {
 
-__device__ __forceinline__ bool finite2(double x, double y) { return fabs(x) < INFINITY && fabs(y) < INFINITY; }
+__device__ __forceinline__ bool finite2(double x, double y) { return finite1(x) && finite1(y); }
 
 // the cross product of the two difference vectors (a - c) x (b - c), ordinary FP64 with one fma
 __device__ __forceinline__ double orient_d(double dax, double day, double dbx, double dby) { return fma(dax, dby, -(day * dbx)); }

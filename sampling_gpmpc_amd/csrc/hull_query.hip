@@ -13,12 +13,13 @@
 //                        point per lane: the edge loop is wave-uniform, the edge reads are LDS broadcasts, and the per-set
 //                        reductions of the tile are ballots and one wave tournament.  The margins go through an LDS tile so that
 //                        the stores run along the set axis of margin (n_points, n_sets).
-//   hullq_finish_kernel  one workgroup per set folds the tiles' partial records.
-// Every reduction is a count, an OR, or a minimum with an index tie rule: none depends on the order it is taken in, so the
-// results are the same bits for every geometry and on every run; no atomics are used at all, and every workspace record that is
-// read was written by the same call.
+//   min_index_finish_kernel<2>  (min_index.hpp) one workgroup per set folds the tiles' partial records.
+// Every reduction is a count, an OR, or a minimum with the index tie rule of min_index.hpp: none depends on the order it is taken
+// in, so the results are the same bits for every geometry and on every run; no atomics are used at all, and every workspace
+// record that is read was written by the same call.
 #include "gpmpc_host.hpp"
 #include "hull_geom.hpp"
+#include "min_index.hpp"
 
 #include <climits>
 #include <cmath>
@@ -32,14 +33,8 @@ constexpr int HQ_PT = 64;     // points per tile = lanes per wave
 constexpr int HQ_SG = 16;     // sets per group
 constexpr int HQ_EV = 32;     // edges per set kept in LDS
 constexpr int HQ_XP = HQ_PT + 1, HQ_MP = HQ_SG + 1;   // LDS pitches
-constexpr int HQ_FIN_WG = 256;
 
-struct HullqPartial {     // one tile's share of one set
-    double m;             // minimum margin of the tile's finite points
-    int idx;              // the lowest point index attaining it, -1: no finite point
-    int n_in, n_fin;
-    unsigned info;
-};
+using HullqPartial = MinIdxPartial<2>;   // cnt: n_in, n_fin
 
 struct HullqArgs {
     const double* verts;
@@ -80,30 +75,6 @@ __device__ __forceinline__ void edge_step(const Edge& e, double px, double py, d
     const double t = fmin(fmax(fma(dx, e.ex, dy * e.ey) * e.inv, 0.0), 1.0);
     const double cx = fma(-t, e.ex, dx), cy = fma(-t, e.ey, dy);
     d2min = fmin(d2min, fma(cx, cx, cy * cy));
-}
-
-struct MinIdx {
-    double m;
-    int idx;   // < 0: none
-};
-
-// the smaller value; of two equal values (+0 and -0 are equal) the lower index: symmetric, so no order matters
-__device__ __forceinline__ MinIdx pick_min(const MinIdx& a, const MinIdx& b) {
-    if (b.idx < 0) return a;
-    if (a.idx < 0) return b;
-    if (b.m < a.m) return b;
-    if (a.m < b.m) return a;
-    return a.idx < b.idx ? a : b;
-}
-
-__device__ __forceinline__ MinIdx wave_min(MinIdx v) {
-    for (int k = 1; k < 64; k <<= 1) {
-        MinIdx o;
-        o.m = __shfl_xor(v.m, k);
-        o.idx = __shfl_xor(v.idx, k);
-        v = pick_min(v, o);
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(HQ_WG) void hullq_kernel(HullqArgs a) {
@@ -196,8 +167,8 @@ __global__ __launch_bounds__(HQ_WG) void hullq_kernel(HullqArgs a) {
                     HullqPartial p;
                     p.m = r.idx >= 0 ? r.m : nan;
                     p.idx = r.idx;
-                    p.n_in = n_in;
-                    p.n_fin = n_fin;
+                    p.cnt[0] = n_in;
+                    p.cnt[1] = n_fin;
                     p.info = (bad_hull ? GPMPC_HULLQ_BAD_HULL : 0u) | (n == 0 ? GPMPC_HULLQ_EMPTY_HULL : 0u) |
                              (dirty ? GPMPC_HULLQ_NONFINITE : 0u);
                     a.part[(long long)set * a.n_tiles + blockIdx.x] = p;
@@ -227,54 +198,6 @@ __global__ __launch_bounds__(HQ_WG) void hullq_kernel(HullqArgs a) {
             if (a.worst) a.worst[gi] = worst.idx >= 0 ? worst.m : nan;
             if (a.first_out) a.first_out[gi] = first_out == INT_MAX ? -1 : first_out;
         }
-    }
-}
-
-__global__ __launch_bounds__(HQ_FIN_WG) void hullq_finish_kernel(const HullqPartial* __restrict__ part, int n_tiles,
-                                                                 int* __restrict__ n_inside, int* __restrict__ n_finite,
-                                                                 double* __restrict__ min_margin, int* __restrict__ argmin,
-                                                                 unsigned* __restrict__ info) {
-    __shared__ double sm[HQ_FIN_WG / 64];
-    __shared__ int si[HQ_FIN_WG / 64], sin_[HQ_FIN_WG / 64], sfin[HQ_FIN_WG / 64];
-    __shared__ unsigned sinfo[HQ_FIN_WG / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, set = blockIdx.x;
-    const HullqPartial* p = part + (long long)set * n_tiles;
-    MinIdx best{0.0, -1};
-    int n_in = 0, n_fin = 0;
-    unsigned flags = 0;
-    for (int t = tid; t < n_tiles; t += HQ_FIN_WG) {
-        const HullqPartial r = p[t];
-        best = pick_min(best, MinIdx{r.m, r.idx});
-        n_in += r.n_in;
-        n_fin += r.n_fin;
-        flags |= r.info;
-    }
-    best = wave_min(best);
-    for (int k = 1; k < 64; k <<= 1) {
-        n_in += __shfl_xor(n_in, k);
-        n_fin += __shfl_xor(n_fin, k);
-        flags |= (unsigned)__shfl_xor((int)flags, k);
-    }
-    if (lane == 0) {
-        sm[wave] = best.m;
-        si[wave] = best.idx;
-        sin_[wave] = n_in;
-        sfin[wave] = n_fin;
-        sinfo[wave] = flags;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < HQ_FIN_WG / 64; ++w) {
-            best = pick_min(best, MinIdx{sm[w], si[w]});
-            n_in += sin_[w];
-            n_fin += sfin[w];
-            flags |= sinfo[w];
-        }
-        if (n_inside) n_inside[set] = n_in;
-        if (n_finite) n_finite[set] = n_fin;
-        if (min_margin) min_margin[set] = best.idx >= 0 ? best.m : __builtin_nan("");
-        if (argmin) argmin[set] = best.idx;
-        if (info) info[set] = flags;
     }
 }
 
@@ -327,8 +250,8 @@ int gpmpc_hull_query(const double* verts, const int* n_verts, int n_sets, int ma
     hipLaunchKernelGGL(hullq_kernel, dim3((unsigned)a.n_tiles), dim3(HQ_WG), 0, st, a);
     GPMPC_HIP_CHECK(hipGetLastError());
     if (per_set) {
-        hipLaunchKernelGGL(hullq_finish_kernel, dim3((unsigned)n_sets), dim3(HQ_FIN_WG), 0, st, (const HullqPartial*)ws, a.n_tiles,
-                           n_inside, n_finite, min_margin, argmin, info);
+        hipLaunchKernelGGL(min_index_finish_kernel<2>, dim3((unsigned)n_sets), dim3(MIN_IDX_FIN_WG), 0, st, (const HullqPartial*)ws,
+                           a.n_tiles, MinIdxCounts<2>{{n_inside, n_finite}}, min_margin, argmin, info);
         GPMPC_HIP_CHECK(hipGetLastError());
     }
     return GPMPC_OK;

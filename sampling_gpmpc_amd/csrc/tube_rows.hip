@@ -14,12 +14,13 @@
 //                        wave-uniform, the row data are LDS broadcasts (E, M, c) and scalar loads (lo, hi, off), and the
 //                        per-(stage, row) reductions of the tile are ballots and one wave tournament.  The per-sample results
 //                        are carried in registers over the stages and folded over the four waves at the end.
-//   trows_finish_kernel  one workgroup per (stage, row) folds the tiles' partial records.
-// Every reduction is a count, an OR, or a minimum with an index tie rule: none depends on the order it is taken in, so the
-// results are the same bits for every geometry and on every run; no atomics are used at all, and every workspace record that is
-// read was written by the same call.  A value is one fixed chain of fma in the state index: its bits depend on the state and the
-// row data alone.
+//   min_index_finish_kernel<1>  (min_index.hpp) one workgroup per (stage, row) folds the tiles' partial records.
+// Every reduction is a count, an OR, or a minimum with the index tie rule of min_index.hpp: none depends on the order it is taken
+// in, so the results are the same bits for every geometry and on every run; no atomics are used at all, and every workspace
+// record that is read was written by the same call.  A value is one fixed chain of fma in the state index: its bits depend on the
+// state and the row data alone.
 #include "gpmpc_host.hpp"
+#include "min_index.hpp"
 
 #include <climits>
 #include <cmath>
@@ -33,14 +34,8 @@ constexpr int TR_PT = 64;         // samples per tile = lanes per wave
 constexpr int TR_TG = 16;         // stages per group
 constexpr int TR_XP = TR_PT + 1;  // LDS pitch
 constexpr int TR_MAX_NX = 4, TR_MAX_LIN = 16, TR_MAX_QUAD = 8;
-constexpr int TR_FIN_WG = 256;
 
-struct TrowsPartial {     // one tile's share of one (stage, row)
-    double m;             // minimum margin of the tile's samples (NaN: the row is inactive at the stage)
-    int idx;              // the lowest sample index attaining it, -1: inactive
-    int n_viol;
-    unsigned info;        // of the stage
-};
+using TrowsPartial = MinIdxPartial<1>;   // cnt: n_viol; (NaN, -1): the row is inactive at the stage; info is the stage's
 
 struct TrowsArgs {
     const double* X;
@@ -55,32 +50,6 @@ struct TrowsArgs {
     double* worst;
     int* first_out;
 };
-
-struct MinIdx {
-    double m;
-    int idx;   // < 0: none
-};
-
-// the smaller value; of two equal values (+0 and -0 are equal) the lower index: symmetric, so no order matters
-__device__ __forceinline__ MinIdx pick_min(const MinIdx& a, const MinIdx& b) {
-    if (b.idx < 0) return a;
-    if (a.idx < 0) return b;
-    if (b.m < a.m) return b;
-    if (a.m < b.m) return a;
-    return a.idx < b.idx ? a : b;
-}
-
-__device__ __forceinline__ MinIdx wave_min(MinIdx v) {
-    for (int k = 1; k < 64; k <<= 1) {
-        MinIdx o;
-        o.m = __shfl_xor(v.m, k);
-        o.idx = __shfl_xor(v.idx, k);
-        v = pick_min(v, o);
-    }
-    return v;
-}
-
-__device__ __forceinline__ bool finite1(double x) { return fabs(x) < INFINITY; }
 
 template <int NX>
 __global__ __launch_bounds__(TR_WG) void trows_kernel(TrowsArgs a) {
@@ -174,7 +143,7 @@ __global__ __launch_bounds__(TR_WG) void trows_kernel(TrowsArgs a) {
                         TrowsPartial p;
                         p.m = nan;
                         p.idx = -1;
-                        p.n_viol = 0;
+                        p.cnt[0] = 0;
                         p.info = dirty;
                         a.part[((long long)t * n_rows + r) * a.n_tiles + blockIdx.x] = p;
                     }
@@ -196,7 +165,7 @@ __global__ __launch_bounds__(TR_WG) void trows_kernel(TrowsArgs a) {
                         TrowsPartial p;
                         p.m = w.m;
                         p.idx = w.idx;
-                        p.n_viol = n_viol;
+                        p.cnt[0] = n_viol;
                         p.info = dirty;
                         a.part[((long long)t * n_rows + r) * a.n_tiles + blockIdx.x] = p;
                     }
@@ -220,48 +189,6 @@ __global__ __launch_bounds__(TR_WG) void trows_kernel(TrowsArgs a) {
             if (a.worst) a.worst[gi] = any_active ? worst : nan;
             if (a.first_out) a.first_out[gi] = first_out == INT_MAX ? -1 : first_out;
         }
-    }
-}
-
-__global__ __launch_bounds__(TR_FIN_WG) void trows_finish_kernel(const TrowsPartial* __restrict__ part, int n_tiles, int n_rows,
-                                                                 int* __restrict__ n_viol, double* __restrict__ min_margin,
-                                                                 int* __restrict__ argmin, unsigned* __restrict__ info) {
-    __shared__ double sm[TR_FIN_WG / 64];
-    __shared__ int si[TR_FIN_WG / 64], sv[TR_FIN_WG / 64];
-    __shared__ unsigned sinfo[TR_FIN_WG / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cell = blockIdx.x;   // cell = stage * n_rows + row
-    const TrowsPartial* p = part + (long long)cell * n_tiles;
-    MinIdx best{0.0, -1};
-    int nv = 0;
-    unsigned flags = 0;
-    for (int t = tid; t < n_tiles; t += TR_FIN_WG) {
-        const TrowsPartial r = p[t];
-        best = pick_min(best, MinIdx{r.m, r.idx});
-        nv += r.n_viol;
-        flags |= r.info;
-    }
-    best = wave_min(best);
-    for (int k = 1; k < 64; k <<= 1) {
-        nv += __shfl_xor(nv, k);
-        flags |= (unsigned)__shfl_xor((int)flags, k);
-    }
-    if (lane == 0) {
-        sm[wave] = best.m;
-        si[wave] = best.idx;
-        sv[wave] = nv;
-        sinfo[wave] = flags;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < TR_FIN_WG / 64; ++w) {
-            best = pick_min(best, MinIdx{sm[w], si[w]});
-            nv += sv[w];
-            flags |= sinfo[w];
-        }
-        if (n_viol) n_viol[cell] = nv;
-        if (min_margin) min_margin[cell] = best.idx >= 0 ? best.m : __builtin_nan("");
-        if (argmin) argmin[cell] = best.idx;
-        if (info && cell % n_rows == 0) info[cell / n_rows] = flags;
     }
 }
 
@@ -344,8 +271,8 @@ int gpmpc_tube_rows(const double* X, long long stride_sample, long long stride_d
     GPMPC_HIP_CHECK(hipGetLastError());
     if (per_row) {
         const int n_rows = n_lin + n_quad;
-        hipLaunchKernelGGL(trows_finish_kernel, dim3((unsigned)(T * n_rows)), dim3(TR_FIN_WG), 0, st, (const TrowsPartial*)ws,
-                           a.n_tiles, n_rows, n_viol, min_margin, argmin, info);
+        hipLaunchKernelGGL(min_index_finish_kernel<1>, dim3((unsigned)T, (unsigned)n_rows), dim3(MIN_IDX_FIN_WG), 0, st,
+                           (const TrowsPartial*)ws, a.n_tiles, MinIdxCounts<1>{{n_viol}}, min_margin, argmin, info);
         GPMPC_HIP_CHECK(hipGetLastError());
     }
     return GPMPC_OK;

@@ -356,75 +356,69 @@ def all_gather_hulls(local, group=None):
     return merge_hulls(parts, max_vertices=mv)
 
 
-def all_reduce_hull_query(q, group=None):
-    """The per-set results of a ``hulls.hull_query`` of a sample-sharded query tube against replicated hulls (those of
-    ``all_gather_hulls``), over the whole tube: ``n_inside`` and ``n_finite`` are summed, ``min_margin`` is the minimum, ``info``
-    is ORed, and ``argmin`` becomes the GLOBAL sample index - the shard's first index is the number of points on the ranks
-    below it, which is ``shard_range``'s for its contiguous shards - with the lowest index among equal minima, as on one
-    device.  The per-point outputs (``margin``, ``worst``, ``first_out``) stay local.  Returns a new ``HullQuery``; works on
-    the tensors' own device (CPU tensors under gloo).  Three small collectives, no host wait."""
-    import dataclasses
-    if q.n_inside is None:
-        raise ValueError("all_reduce_hull_query needs the per-set outputs (hull_query(..., per_set=True))")
+def _all_reduce_sum_with_sizes(parts, n_local: int, group=None):
+    """ONE SUM (int64 on the wire) of the integer tensors ``parts`` and of every shard's size ``n_local``: returns the summed parts
+    (flat, int64), the ``(world,)`` sizes and this shard's first global index - the number of members on the ranks below it, which is
+    ``shard_range``'s for its contiguous shards.  A 0/1 part comes back > 0 where any rank had it set: the OR (RCCL has no bitwise
+    reduction).  No host wait."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
-    n_sets, dev = q.n_inside.shape[0], q.n_inside.device
-    # one SUM carries the counts, the info bits (a sum > 0 is the OR: RCCL has no bitwise reduction) and every shard's size
-    bits = torch.stack([(q.info.to(torch.int64) >> b) & 1 for b in range(8)]).reshape(-1)          # HULLQ_* uses 3
-    sizes = torch.zeros(world, dtype=torch.int64, device=dev)
-    sizes[rank] = int(q.n_points)
-    packed = torch.cat([q.n_inside.to(torch.int64), q.n_finite.to(torch.int64), bits, sizes])
+    sizes = torch.zeros(world, dtype=torch.int64, device=parts[0].device)
+    sizes[rank] = int(n_local)
+    packed = torch.cat([p.reshape(-1).to(torch.int64) for p in parts] + [sizes])
     dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
-    n_inside, n_finite = packed[:n_sets].to(q.n_inside.dtype), packed[n_sets:2 * n_sets].to(q.n_finite.dtype)
-    got = (packed[2 * n_sets:10 * n_sets].reshape(8, n_sets) > 0).to(torch.int64)
-    info = sum(got[b] << b for b in range(8)).to(q.info.dtype)
-    lo = packed[10 * n_sets:][:rank].sum()
-    # a shard without a finite point (NaN) takes no part in the minimum
-    m = torch.where(torch.isnan(q.min_margin), torch.full_like(q.min_margin, float("inf")), q.min_margin)
+    *summed, sizes = packed.split([p.numel() for p in parts] + [world])
+    return summed, sizes, sizes[:rank].sum()
+
+
+def _all_reduce_min_index(value, index, offset, group=None):
+    """The minimum of ``value`` over the ranks and the lowest GLOBAL index (``index + offset``) among the ranks that attain it - the tie
+    rule of one device (csrc/min_index.hpp: equal values, +0 and -0 included, go to the lower index).  A NaN ``value`` or an ``index`` < 0
+    means "nothing here" and takes no part.  Returns the value (NaN where no rank had one) and the int64 index (-1 there).  Two
+    collectives, no host wait."""
+    m = torch.where(torch.isnan(value), torch.full_like(value, float("inf")), value)
     dist.all_reduce(m, op=dist.ReduceOp.MIN, group=group)
     # every rank whose own minimum equals the global one proposes its global index, the lowest wins
     big = torch.iinfo(torch.int64).max
-    local = q.argmin.to(torch.int64)
-    idx = torch.where((local >= 0) & (q.min_margin == m), local + lo, torch.full_like(local, big))
+    local = index.to(torch.int64)
+    idx = torch.where((local >= 0) & (value == m), local + offset, torch.full_like(local, big))
     dist.all_reduce(idx, op=dist.ReduceOp.MIN, group=group)
     none = idx == big
-    return dataclasses.replace(q, n_points=int(q.n_points), n_inside=n_inside, n_finite=n_finite,
-                               min_margin=torch.where(none, torch.full_like(m, float("nan")), m),
-                               argmin=torch.where(none, torch.full_like(idx, -1), idx).to(q.argmin.dtype), info=info)
+    return torch.where(none, torch.full_like(m, float("nan")), m), torch.where(none, torch.full_like(idx, -1), idx)
+
+
+def all_reduce_hull_query(q, group=None):
+    """The per-set results of a ``hulls.hull_query`` of a sample-sharded query tube against replicated hulls (those of
+    ``all_gather_hulls``), over the whole tube: ``n_inside`` and ``n_finite`` are summed, ``min_margin`` is the minimum, ``info``
+    is ORed, and ``argmin`` becomes the GLOBAL sample index with the lowest index among equal minima, as on one device
+    (``_all_reduce_min_index``).  The per-point outputs (``margin``, ``worst``, ``first_out``) stay local.  Returns a new ``HullQuery``;
+    works on the tensors' own device (CPU tensors under gloo).  Three small collectives, no host wait."""
+    import dataclasses
+    if q.n_inside is None:
+        raise ValueError("all_reduce_hull_query needs the per-set outputs (hull_query(..., per_set=True))")
+    n_sets = q.n_inside.shape[0]
+    bits = torch.stack([(q.info.to(torch.int64) >> b) & 1 for b in range(8)])                      # HULLQ_* uses 3
+    (n_inside, n_finite, bits), _, lo = _all_reduce_sum_with_sizes([q.n_inside, q.n_finite, bits], q.n_points, group)
+    got = (bits.reshape(8, n_sets) > 0).to(torch.int64)
+    info = sum(got[b] << b for b in range(8)).to(q.info.dtype)
+    min_margin, argmin = _all_reduce_min_index(q.min_margin, q.argmin, lo, group)
+    return dataclasses.replace(q, n_points=int(q.n_points), n_inside=n_inside.to(q.n_inside.dtype), n_finite=n_finite.to(q.n_finite.dtype),
+                               min_margin=min_margin, argmin=argmin.to(q.argmin.dtype), info=info)
 
 
 def all_reduce_tube_check(chk, group=None):
     """The per-(stage, row) results of a ``tube_rows.check_tube`` of a sample-sharded tube against replicated rows, over the whole tube:
-    ``n_viol`` and ``n_safe`` are summed, ``info`` is ORed, ``min_margin`` is the minimum and ``argmin`` becomes the GLOBAL sample index - the
-    shard's first index is the number of samples on the ranks below it, as in ``all_reduce_hull_query`` - with the lowest index among
-    equal minima, as on one device; ``Ns`` becomes the total.  The per-sample outputs (``worst``, ``first_out``) stay local.  Returns a new
-    ``TubeCheck``; works on the tensors' own device (CPU tensors under gloo).  Three small collectives and one host read (``Ns``)."""
+    ``n_viol`` and ``n_safe`` are summed, ``info`` is ORed, ``min_margin`` is the minimum and ``argmin`` becomes the GLOBAL sample index with
+    the lowest index among equal minima, as in ``all_reduce_hull_query``; ``Ns`` becomes the total.  The per-sample outputs (``worst``,
+    ``first_out``) stay local.  Returns a new ``TubeCheck``; works on the tensors' own device (CPU tensors under gloo).  Three small
+    collectives and one host read (``Ns``)."""
     import dataclasses
-    rank, world = dist.get_rank(group), dist.get_world_size(group)
-    dev, shape = chk.n_viol.device, chk.n_viol.shape
-    sizes = torch.zeros(world, dtype=torch.int64, device=dev)
-    sizes[rank] = int(chk.Ns)
-    # one SUM carries the counts, the info bit (a sum > 0 is the OR: RCCL has no bitwise reduction) and every shard's size
-    packed = torch.cat([chk.n_viol.reshape(-1).to(torch.int64), (chk.info.to(torch.int64) & 1), chk.n_safe.reshape(1).to(torch.int64),
-                        sizes])
-    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
-    n_cells, T = chk.n_viol.numel(), chk.info.shape[0]
-    n_viol = packed[:n_cells].reshape(shape).to(chk.n_viol.dtype)
-    info = (packed[n_cells:n_cells + T] > 0).to(chk.info.dtype)
-    n_safe = packed[n_cells + T]
-    all_sizes = packed[n_cells + T + 1:]
-    lo = all_sizes[:rank].sum()
-    # an inactive row (NaN on every rank) takes no part in the minimum
-    m = torch.where(torch.isnan(chk.min_margin), torch.full_like(chk.min_margin, float("inf")), chk.min_margin)
-    dist.all_reduce(m, op=dist.ReduceOp.MIN, group=group)
-    big = torch.iinfo(torch.int64).max
-    local = chk.argmin.to(torch.int64)
-    idx = torch.where((local >= 0) & (chk.min_margin == m), local + lo, torch.full_like(local, big))
-    dist.all_reduce(idx, op=dist.ReduceOp.MIN, group=group)
-    none = idx == big
-    _lib.host_wait(all_sizes)
-    return dataclasses.replace(chk, Ns=int(all_sizes.sum().item()), n_viol=n_viol, info=info, n_safe=n_safe,
-                               min_margin=torch.where(none, torch.full_like(m, float("nan")), m),
-                               argmin=torch.where(none, torch.full_like(idx, -1), idx).to(chk.argmin.dtype))
+    (n_viol, info, n_safe), sizes, lo = _all_reduce_sum_with_sizes([chk.n_viol, chk.info.to(torch.int64) & 1, chk.n_safe.reshape(1)],
+                                                                   chk.Ns, group)
+    min_margin, argmin = _all_reduce_min_index(chk.min_margin, chk.argmin, lo, group)   # an inactive row is NaN on every rank
+    _lib.host_wait(sizes)
+    return dataclasses.replace(chk, Ns=int(sizes.sum().item()), n_viol=n_viol.reshape(chk.n_viol.shape).to(chk.n_viol.dtype),
+                               info=(info > 0).to(chk.info.dtype), n_safe=n_safe[0], min_margin=min_margin,
+                               argmin=argmin.to(chk.argmin.dtype))
 
 
 def all_reduce_small_ball(result, group=None):

@@ -65,6 +65,7 @@ def test_workspace_bytes_monotone_and_zero_for_empty_shapes(lib):
     assert lib.gpmpc_hull_query_workspace_bytes(1000, 82, 256) >= lib.gpmpc_hull_query_workspace_bytes(1000, 41, 256)
     assert lib.gpmpc_hull_query_workspace_bytes(1000, 41, 4096) >= lib.gpmpc_hull_query_workspace_bytes(1000, 41, 8)
     assert lib.gpmpc_hull_query_workspace_bytes(0, 41, 256) == 0 and lib.gpmpc_hull_query_workspace_bytes(10, 0, 256) == 0
+    assert lib.gpmpc_hull_query_workspace_bytes(65, 17, 8) == 1024          # 2 tiles x 17 sets x 24 B, rounded up to 256
 
 
 def test_wrappers_need_a_hip_device_and_are_exported():

@@ -182,6 +182,7 @@ def test_argument_checks_come_before_any_device_work(lib, kw):
 def test_the_workspace(lib):
     need = lib.gpmpc_tube_rows_workspace_bytes(257, 9, 16, 8)
     assert need == ((5 * 9 * 24 * 24 + 255) // 256) * 256                                      # one 24-byte record per (tile, stage, row)
+    assert lib.gpmpc_tube_rows_workspace_bytes(65, 17, 2, 1) == 2560                           # 2 x 17 x 3 x 24 B, rounded up to 256
     assert _rows(lib, ws_bytes=lib.gpmpc_tube_rows_workspace_bytes(8, 11, 3, 1) - 1) == -2 and _rows(lib, ws=None) == -2
     assert "workspace" in lib.gpmpc_last_error_string().decode()
     for bad in ((0, 9, 1, 1), (8, 0, 1, 1), (8, 9, 0, 0), (8, 9, 17, 0), (8, 9, 0, 9), (2 ** 31, 9, 1, 1), (8, 9, -1, 2)):
