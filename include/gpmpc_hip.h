@@ -1006,6 +1006,69 @@ int     gpmpc_robust_tube_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_des
                                   int32_t* info /* (B) */, void* stream);
 
 /*
+ * gpmpc_robust_tube_rollout_vjp - the reverse-mode derivative (vector-Jacobian product) of the map
+ * (x0, U, Q0, l_mu, l_sigma) -> (M, Q) that gpmpc_robust_tube_rollout computes, exactly as that kernel defines it.  One candidate
+ * per lane, one backward sweep t = H-1..0 that reads p_t and Q_t from the forward's M and Q (the forward is not run again).  An
+ * additive entry point: the ABI version stays 12.
+ * Replaces: nothing the reference can do - benchmarking/robust_tube_based_GPMPC_koller.py:277-307 only evaluates the recursion
+ * along a given input trajectory, the optimiser of Koller's MPC living in the external repository safe-exploration-koller, which
+ * was not available.  With this gradient the inputs can be moved so that the ellipsoids shrink or satisfy constraints.
+ * The adjoint of one step, in the names of steps 1 - 6 above, Lambda the symmetrised cotangent of Q_{t+1}, lambda that of p_{t+1}:
+ *   6. wb_bar = <Lambda, Qbar>, wd_bar = sum_d Lambda_dd qd_d, Qbar_bar = wb Lambda, qd_bar_d = wd Lambda_dd; the weights
+ *      wx = 1 + 1/c, wy = 1 + c pass c_bar = wy_bar - wx_bar / c^2 to the traces, trx_bar = c_bar c / (2 tr X),
+ *      try_bar = -c_bar c / (2 tr Y), which feed back as Qbar_bar += trb_bar I and qd_bar_d += trd_bar; the same for Q_sig (+) Q_mu;
+ *   5. sb_bar_d = 2 nx sb_d qs_bar_d,  ub_bar_d = 2 nx ub_d qm_bar_d;
+ *   4. r2_bar = sum_d 0.5 l_mu[d] ub_bar_d + (sum_d beta l_sigma[d] sb_bar_d) / (2 sqrt(r2)),
+ *      gdiag_bar_d = beta sb_bar_d / (2 sqrt(gdiag_d)),  g_l_mu[d] += 0.5 r2 ub_bar_d,  g_l_sigma[d] += beta sqrt(r2) sb_bar_d;
+ *   3. Q_t_bar += r2_bar (W^T v)(W^T v)^T, v the unit eigenvector of W Q_t W^T for lambda_max (the Jacobi sweeps of the forward
+ *      with their rotations accumulated);
+ *   2. Q_t_bar += A^T Qbar_bar A,  A_bar = 2 Qbar_bar A Q_t;
+ *   1. from A_bar, gdiag_bar and lambda through the Hessian of the posterior mean, the gradient of the variance, env_step and the
+ *      feedback gain exactly as gpmpc_moment_rollout_vjp proceeds (the two kernels call the same device functions):
+ *      g_U[b, t], lambda_t = x_bar + gM[:, t], Lambda_t = Q_t_bar + sym(gQ[:, t]).
+ * Conventions (the recursion is not differentiable everywhere; both CPU references of tests/robust_tube_grad_reference.py follow
+ * them):
+ *   1. where r2 == 0 (a clamped negative lambda_max and Q_t = 0 included) nothing passes to Q_t through r2 or sqrt(r2);
+ *   2. where gdiag_d == 0 (the pendulum's angle row, the car's speed row) nothing passes through sqrt(gdiag_d);
+ *   3. a variance raised to the floor passes nothing, as in gpmpc_moment_rollout_vjp (the floor value itself still meets d G / d x);
+ *   4. on an exact tie of the largest eigenvalue the eigenvector is that of the lowest diagonal index after the sweeps.  Apart from
+ *      an exact tie the gradient is only defined with a gap between the two largest eigenvalues of W Q_t W^T: close to a tie it
+ *      is ill-conditioned, as the derivative of lambda_max is;
+ *   5. g_Q0 comes back on the lower triangle, the part of Q0 that is read (the rule of gP0); in the two degenerate branches of
+ *      X (+) Y (tr X == 0 or tr Y == 0) the weights are constants and pass nothing.
+ *   x0, x0_per_candidate, U, u_per_candidate, Q0, l_mu, l_sigma, l_per_candidate, beta   the forward's inputs
+ *   M    [dev] (B, nx, H+1), Q [dev] (B, H+1, nx, nx)   the forward's outputs, read
+ *   gM   [dev] (B, nx, H+1) or NULL     cotangent of M; NULL is zero
+ *   gQ   [dev] (B, H+1, nx, nx) or NULL cotangent of Q; NULL is zero.  It need not be symmetric: the kernel works with (gQ + gQ^T) / 2
+ *   g_x0 [dev] (B, nx) or NULL          out: d / d x0
+ *   g_U  [dev] (B, H, nu)               out: d / d U (the feed-forward input)      (may be NULL when H == 0)
+ *   g_Q0 [dev] (B, nx, nx) or NULL      out: d / d Q0 with the whole gradient on the lower triangle (diagonal included: the entry
+ *                                       (i, j), j < i, carries both mirrored copies) and exact zeros above it
+ *   g_l_mu, g_l_sigma [dev] (B, nx) or NULL   out: d / d l_mu, d / d l_sigma
+ *   info [dev] (B) int32                out: GPMPC_INFO_VAR_CLAMPED, GPMPC_INFO_NONFINITE
+ * Gradients are always per candidate, also when x0 / U / l_mu / l_sigma are shared (*_per_candidate == 0): the host sums over B for
+ * a shared input, the kernel needs no cross-lane reduction and no atomics.
+ * Non-finite values: a candidate whose x0, U, Q0, l_mu, l_sigma (or beta), M, Q, gM or gQ hold a non-finite value - a forward that
+ * overflowed is one - or for which one is computed, has NaN in all its gradients and GPMPC_INFO_NONFINITE; no other candidate is
+ * touched.
+ * Reproducibility: a candidate's gradient bits do not depend on B or on its place in the batch.
+ * Limits and errors are those of gpmpc_moment_rollout_vjp and gpmpc_robust_tube_rollout: D = 2, both environments, any X_r, at most
+ * 64 label rows, B < 2^31; GPMPC_E_ARG / GPMPC_E_UNSUPPORTED before any device work (required with B > 0: plan, X_r, x0, l_mu,
+ * l_sigma, M, Q, info, and U and g_U when H > 0; a feedback gain that is not finite).  B == 0: nothing is launched and the array
+ * pointers are not looked at.  H == 0: g_x0 = gM[:, :, 0] and g_Q0 from gQ[:, 0].  No workspace, no host round trip, everything
+ * goes to `stream`.
+ */
+int     gpmpc_robust_tube_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                      int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                                      int32_t u_per_candidate, const double* Q0 /* NULL or (B, nx, nx) */, const double* l_mu,
+                                      const double* l_sigma /* (nx) or (B, nx) */, int32_t l_per_candidate, double beta,
+                                      const double* M /* (B, nx, H+1) */, const double* Q /* (B, H+1, nx, nx) */,
+                                      const double* gM /* (B, nx, H+1) or NULL */, const double* gQ /* (B, H+1, nx, nx) or NULL */,
+                                      double* g_x0 /* (B, nx) or NULL */, double* g_U /* (B, H, nu) */,
+                                      double* g_Q0 /* (B, nx, nx) or NULL */, double* g_l_mu, double* g_l_sigma /* (B, nx) or NULL */,
+                                      int32_t* info /* (B) */, void* stream);
+
+/*
  * gpmpc_pairwise_lipschitz - the sampled Lipschitz constant of G vector functions over N points: for every group g
  *   out_max[g] = max over i < j of |F[i,g,:] - F[j,g,:]|_2 / (|X[i,:] - X[j,:]|_2 + eps),
  * as a tiled sweep over the N (N - 1) / 2 pairs that never forms an N x N array.  Additive entry points: the ABI version stays 12.

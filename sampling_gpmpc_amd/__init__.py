@@ -20,7 +20,8 @@ from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
 from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats, pathwise_tube_stats, merge_tube_stats,  # noqa: F401
                        tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled)
-from .robust_tube import RobustTube, robust_tube_rollout, robust_tube_rollout_plan, pairwise_lipschitz, estimate_lipschitz  # noqa: F401
+from .robust_tube import (RobustTube, robust_tube_rollout, robust_tube_rollout_plan, pairwise_lipschitz, estimate_lipschitz,  # noqa: F401
+                          robust_tube_rollout_vjp, robust_tube_rollout_vjp_plan, plan_inputs_robust, plan_inputs_robust_plan)
 
 __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable_set_ball",
            "random_vector_within_bounds", "HullSet", "HullAccumulator", "convex_hulls", "merge_hulls", "hull_area_ratio",
@@ -32,5 +33,6 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
            "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error",
            "TubeStats", "pathwise_tube_stats", "merge_tube_stats", "tube_stats_of", "pathwise_rollout_vjp", "sampled_tube_penalty",
-           "plan_inputs_sampled", "RobustTube", "robust_tube_rollout", "robust_tube_rollout_plan", "pairwise_lipschitz",
+           "plan_inputs_sampled", "RobustTube", "robust_tube_rollout", "robust_tube_rollout_plan", "robust_tube_rollout_vjp",
+           "robust_tube_rollout_vjp_plan", "plan_inputs_robust", "plan_inputs_robust_plan", "pairwise_lipschitz",
            "estimate_lipschitz"]

@@ -1,5 +1,6 @@
-"""What the rollout wrappers and their planners share (``moments.py``, ``pathwise.py``, ``mle.py``): the handling of ``x0`` / ``U``, the
-planners' argument checks, the Adam update, the squared violation of tube rows.  Plain torch: all of it runs on CPU tensors too."""
+"""What the rollout wrappers and their planners share (``moments.py``, ``robust_tube.py``, ``pathwise.py``, ``mle.py``): the handling of
+``x0`` / ``U``, the planners' argument checks, the Adam update, the population loop of ``plan_inputs`` / ``plan_inputs_robust``, the
+squared violation of tube rows.  Plain torch: all of it runs on CPU tensors too."""
 import math
 
 import torch
@@ -44,6 +45,34 @@ def adam_update(p, m, v, g, it: int, lr: float):
     v = torch.addcmul(v * b2, g, g, value=1.0 - b2)
     denom = v.sqrt() / math.sqrt(1.0 - b2 ** it) + eps
     return torch.addcdiv(p, m, denom, value=-(lr / (1.0 - b1 ** it))), m, v
+
+
+def plan_population(who: str, rollout, U0, cost, steps: int, lr: float, dev):
+    """The loop of ``plan_inputs`` and ``plan_inputs_robust``: Adam on a population ``U0 (B, H, nu)``.  ``rollout(U, differentiable)`` gives
+    the tube of the candidates ``U`` - with a ``grad_fn`` when ``differentiable`` -, ``cost(tube, U) -> (B,)``.  One forward and one
+    backward per iteration.  Returns ``(U, hist (steps + 1, B), best)``."""
+    U = U0.detach().to(device=dev, dtype=torch.float64).clone()
+    B, steps = int(U.shape[0]), int(steps)
+    m, v = torch.zeros_like(U), torch.zeros_like(U)
+    hist = torch.empty(steps + 1, B, dtype=torch.float64, device=dev)
+
+    def costs(tube, Uc):
+        c = cost(tube, Uc)
+        if not torch.is_tensor(c) or tuple(c.shape) != (B,):
+            raise GpmpcError(f"{who}: cost must return a tensor ({B},), one value per candidate")
+        return c
+
+    for it in range(1, steps + 1):
+        Uc = U.detach().requires_grad_(True)
+        c = costs(rollout(Uc, True), Uc)
+        hist[it - 1] = c.detach()
+        g, = torch.autograd.grad(c.sum(), Uc)                        # the candidates are independent: one backward launch for all
+        U, m, v = adam_update(U, m, v, g, it, lr)
+    with torch.no_grad():
+        hist[steps] = costs(rollout(U, False), U)
+    final = hist[steps]
+    best = torch.where(torch.isfinite(final), final, torch.full_like(final, float("inf"))).argmin()
+    return U, hist, best
 
 
 def squared_violation(upper: torch.Tensor, lower: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:

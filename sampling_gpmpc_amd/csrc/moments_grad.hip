@@ -34,14 +34,12 @@ struct MomentGradArgs : MomentStepArgs {
 template <int ENV, int NRP, bool HG>
 __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, const double* Ltri, const double* alpha_s,
                                                         const double* xr_s, const long b, const bool active) {
-    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY, SEL = EnvDims<ENV>::SEL;
-    constexpr int TR = HG ? 3 : 1;
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
     constexpr int TRI = mom_col_ofs<NRP>(NRP);
     const GpParams& gp = a.gp;
     const int n = gp.n_r;
     const int H = a.H;
     const double nan = __builtin_nan("");
-    const bool use_fb = a.env.use_feedback != 0;
 
     double lam[NX], Lam[NX][NX];                                       // Lam: the lower triangle [i][j], j <= i, is live
     double chk = 0.0;
@@ -83,39 +81,10 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
         for (int o = 0; o < G_NY; ++o) {
             const double il[2] = {gp.inv_l2[o][0], gp.inv_l2[o][1]};
             const double os = gp.os[o];
-            const double* LT = Ltri + o * TRI;
-            const double* al = alpha_s + o * NRP;
-            double acc[MOM_ACC<NRP>];
-#pragma unroll
-            for (int i = 0; i < NRP; ++i) acc[i] = 0.0;
-            MomGpSums g;                                               // pass 1: the forward's column loop, with the Hessian sums
-            const double ss = mom_gp_pass1<NRP, HG, true>(LT, al, xr_s, n, il, os, xi, acc, g);
-            double s, k = 0.0, q[2] = {0.0, 0.0};
-            const bool clamped = mom_variance(gp, os, ss, s, info_acc);
-            // pass 2: w = L^-T acc column by column, d s / d xi_d = -2 sum_j w_j d k_j / d xi_d
-            double e0 = 0.0, e1 = 0.0;
-#pragma unroll
-            for (int j = 0; j < NRP; ++j) {
-                if (j < n) {
-                    const int tb = j % TR;
-                    if (tb == 0) mom_kernel_point(xi, xr_s, j / TR, il, os, q, k);
-                    const double* col = LT + mom_col_ofs<NRP>(j);
-                    double wa = 0.0, wb = 0.0;                         // two chains: the even and the odd entries of the column
-#pragma unroll
-                    for (int i = j; i + 1 < NRP; i += 2) {
-                        const double2_m l = *reinterpret_cast<const double2_m*>(col + (i - j));
-                        wa = fma(l.x, acc[i], wa);
-                        wb = fma(l.y, acc[i + 1], wb);
-                    }
-                    if ((NRP - j) & 1) wa = fma(col[NRP - 1 - j], acc[NRP - 1], wa);
-                    const double w = wa + wb;
-                    e0 = fma(w, kern_entry<2>(q, k, il, 1, tb), e0);
-                    e1 = fma(w, kern_entry<2>(q, k, il, 2, tb), e1);
-                    asm volatile("" ::: "memory");
-                }
-            }
-            e0 = clamped ? 0.0 : -2.0 * e0;
-            e1 = clamped ? 0.0 : -2.0 * e1;
+            MomGpGrad r;                                               // pass 1 with the Hessian sums, the variance, pass 2
+            mom_gp_grad<NRP, HG>(gp, Ltri + o * TRI, alpha_s + o * NRP, xr_s, n, il, os, xi, info_acc, r);
+            const MomGpSums& g = r.g;
+            const double s = r.s, e0 = r.e0, e1 = r.e1;
             chk += fabs(g.m) + fabs(s) + fabs(g.d0) + fabs(g.d1) + fabs(g.h00) + fabs(g.h01) + fabs(g.h11) + fabs(e0) + fabs(e1);
 #pragma unroll
             for (int oo = 0; oo < G_NY; ++oo)
@@ -175,52 +144,10 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
         }
 
         // ---- cotangents of x, u_ff, m, grad m and s from env_step, A and G ------------------------------------------------------------
-        double xbar[NX], ubar[NU], mbar[G_NY], gbar[G_NY][2], sbar[G_NY];
-        if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
-            xbar[0] = lam[0];
-            xbar[1] = fma(a.env.dt, lam[0], lam[1]);
-            mbar[0] = lam[1];
+        double xbar[NX], ubar[NU], dbar[NX];
 #pragma unroll
-            for (int d = 0; d < 2; ++d) gbar[0][d] = Abar[1][0] * dxi[d][0] + Abar[1][1] * dxi[d][1];
-            sbar[0] = Lam[1][1];
-        } else {
-            const double v = x[3];
-            double vbar = lam[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                xbar[i] = lam[i];
-                vbar = fma(lam[i], gm[i], vbar);
-                mbar[i] = fma(v, lam[i], Abar[i][3]);
-                double td[2];
-#pragma unroll
-                for (int d = 0; d < 2; ++d) {
-                    double s_ = 0.0;
-#pragma unroll
-                    for (int c = 0; c < NX; ++c) s_ = fma(Abar[i][c], dxi[d][c], s_);
-                    td[d] = s_;
-                    gbar[i][d] = v * s_;
-                }
-                vbar += td[0] * gd[i][0] + td[1] * gd[i][1];
-                sbar[i] = v * v * Lam[i][i];
-                vbar = fma(2.0 * v * gs[i], Lam[i][i], vbar);
-            }
-            xbar[3] = vbar;
-            ubar[1] = a.env.dt * lam[3];
-        }
-        double xib[2] = {0.0, 0.0};
-#pragma unroll
-        for (int o = 0; o < G_NY; ++o) {
-            xib[0] += mbar[o] * gd[o][0] + gh[o][0] * gbar[o][0] + gh[o][1] * gbar[o][1] + sbar[o] * ge[o][0];
-            xib[1] += mbar[o] * gd[o][1] + gh[o][1] * gbar[o][0] + gh[o][2] * gbar[o][1] + sbar[o] * ge[o][1];
-        }
-        xbar[SEL] += xib[0];
-        ubar[0] = xib[1];
-        if (use_fb) {
-#pragma unroll
-            for (int c = 0; c < NX; ++c)
-#pragma unroll
-                for (int i = 0; i < NU; ++i) xbar[c] = fma(a.env.K[i][c], ubar[i], xbar[c]);
-        }
+        for (int i = 0; i < NX; ++i) dbar[i] = Lam[i][i];
+        mom_step_tail<ENV>(a.env, x, gm, gs, gd, gh, ge, dxi, Abar, dbar, lam, xbar, ubar);
         if (active) {
 #pragma unroll
             for (int i = 0; i < NU; ++i) a.gU[(b * H + t) * NU + i] = ubar[i];

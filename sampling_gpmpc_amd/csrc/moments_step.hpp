@@ -249,6 +249,112 @@ __host__ __device__ __forceinline__ bool mom_variance(const GpParams& gp, double
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// the backward step, shared by moment_rollout_vjp_kernel (moments_grad.hip) and robust_tube_vjp_kernel (robust_tube_grad.hip)
+// ---------------------------------------------------------------------------------------------------------------
+struct MomGpGrad {                         // one output at xi: the label sums with the Hessian, the clamped variance, d s / d xi
+    MomGpSums g;
+    double s, e0, e1;                      // e: 0 where the variance was raised to the floor
+};
+
+// The GP passes of a backward step for one output: pass 1 with the Hessian sums, the variance, and pass 2, w = L^-T acc column by
+// column and d s / d xi_d = -2 sum_j w_j d k_j / d xi_d (the kernel rows are formed again, one exponential per real point).
+template <int NRP, bool HG>
+__host__ __device__ __forceinline__ void mom_gp_grad(const GpParams& gp, const double* LT, const double* al, const double* xr_s, int n,
+                                                     const double (&il)[2], double os, const double (&xi)[2], int& info_acc, MomGpGrad& r) {
+    constexpr int TR = HG ? 3 : 1;
+    double acc[MOM_ACC<NRP>];
+#pragma unroll
+    for (int i = 0; i < NRP; ++i) acc[i] = 0.0;
+    const double ss = mom_gp_pass1<NRP, HG, true>(LT, al, xr_s, n, il, os, xi, acc, r.g);
+    double k = 0.0, q[2] = {0.0, 0.0};
+    const bool clamped = mom_variance(gp, os, ss, r.s, info_acc);
+    double e0 = 0.0, e1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < NRP; ++j) {
+        if (j < n) {
+            const int tb = j % TR;
+            if (tb == 0) mom_kernel_point(xi, xr_s, j / TR, il, os, q, k);
+            const double* col = LT + mom_col_ofs<NRP>(j);
+            double wa = 0.0, wb = 0.0;                                 // two chains: the even and the odd entries of the column
+#pragma unroll
+            for (int i = j; i + 1 < NRP; i += 2) {
+                const double2_m l = *reinterpret_cast<const double2_m*>(col + (i - j));
+                wa = fma(l.x, acc[i], wa);
+                wb = fma(l.y, acc[i + 1], wb);
+            }
+            if ((NRP - j) & 1) wa = fma(col[NRP - 1 - j], acc[NRP - 1], wa);
+            const double w = wa + wb;
+            e0 = fma(w, kern_entry<2>(q, k, il, 1, tb), e0);
+            e1 = fma(w, kern_entry<2>(q, k, il, 2, tb), e1);
+            asm volatile("" ::: "memory");
+        }
+    }
+    r.e0 = clamped ? 0.0 : -2.0 * e0;
+    r.e1 = clamped ? 0.0 : -2.0 * e1;
+}
+
+// The tail of a backward step: from Abar (cotangent of A_t), dbar (cotangent of the diagonal of B_d diag(s) B_d^T, env_noise_diag_ct)
+// and lam (cotangent of x_{t+1}) to xbar (cotangent of x_t, before the step's own output cotangent is added) and ubar (that of the
+// feed-forward input) through env_step, the entries of A, the Hessian of the mean (gh: H00, H01, H11), the gradient of the
+// variance (ge) and the feedback gain.
+template <int ENV>
+__host__ __device__ __forceinline__ void mom_step_tail(const EnvParams& e, const double (&x)[EnvDims<ENV>::NX],
+                                                       const double (&gm)[EnvDims<ENV>::G_NY], const double (&gs)[EnvDims<ENV>::G_NY],
+                                                       const double (&gd)[EnvDims<ENV>::G_NY][2], const double (&gh)[EnvDims<ENV>::G_NY][3],
+                                                       const double (&ge)[EnvDims<ENV>::G_NY][2], const double (&dxi)[2][EnvDims<ENV>::NX],
+                                                       const double (&Abar)[EnvDims<ENV>::NX][EnvDims<ENV>::NX],
+                                                       const double (&dbar)[EnvDims<ENV>::NX], const double (&lam)[EnvDims<ENV>::NX],
+                                                       double (&xbar)[EnvDims<ENV>::NX], double (&ubar)[EnvDims<ENV>::NU]) {
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY, SEL = EnvDims<ENV>::SEL;
+    double mbar[G_NY], gbar[G_NY][2], sbar[G_NY];
+    if constexpr (ENV == GPMPC_ENV_PENDULUM1D) {
+        xbar[0] = lam[0];
+        xbar[1] = fma(e.dt, lam[0], lam[1]);
+        mbar[0] = lam[1];
+#pragma unroll
+        for (int d = 0; d < 2; ++d) gbar[0][d] = Abar[1][0] * dxi[d][0] + Abar[1][1] * dxi[d][1];
+        sbar[0] = dbar[1];
+    } else {
+        const double v = x[3];
+        double vbar = lam[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            xbar[i] = lam[i];
+            vbar = fma(lam[i], gm[i], vbar);
+            mbar[i] = fma(v, lam[i], Abar[i][3]);
+            double td[2];
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                double s_ = 0.0;
+#pragma unroll
+                for (int c = 0; c < NX; ++c) s_ = fma(Abar[i][c], dxi[d][c], s_);
+                td[d] = s_;
+                gbar[i][d] = v * s_;
+            }
+            vbar += td[0] * gd[i][0] + td[1] * gd[i][1];
+            sbar[i] = v * v * dbar[i];
+            vbar = fma(2.0 * v * gs[i], dbar[i], vbar);
+        }
+        xbar[3] = vbar;
+        ubar[1] = e.dt * lam[3];
+    }
+    double xib[2] = {0.0, 0.0};
+#pragma unroll
+    for (int o = 0; o < G_NY; ++o) {
+        xib[0] += mbar[o] * gd[o][0] + gh[o][0] * gbar[o][0] + gh[o][1] * gbar[o][1] + sbar[o] * ge[o][0];
+        xib[1] += mbar[o] * gd[o][1] + gh[o][1] * gbar[o][0] + gh[o][2] * gbar[o][1] + sbar[o] * ge[o][1];
+    }
+    xbar[SEL] += xib[0];
+    ubar[0] = xib[1];
+    if (e.use_feedback != 0) {
+#pragma unroll
+        for (int c = 0; c < NX; ++c)
+#pragma unroll
+            for (int i = 0; i < NU; ++i) xbar[c] = fma(e.K[i][c], ubar[i], xbar[c]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // host: the instantiation set, the argument block and the argument checks of the two entry points
 // ---------------------------------------------------------------------------------------------------------------
 // launch(env, nrp, hg) with integral constants: n_r rounded up to a multiple of 8 (16 with derivative labels)

@@ -12,80 +12,14 @@
 // lambda_max of the symmetric nx x nx matrix (nx <= 4) is taken in registers by cyclic Jacobi sweeps with compile-time indices.
 // The centre (NX) and the lower triangle of Q (NX (NX + 1) / 2 <= 10 entries) stay in registers across the step loop.
 // Work per candidate-step: the GP pass of the moment rollout, then ~4 NX^3 for A Q A^T and W Q W^T and JAC_SWEEPS NX (NX - 1) / 2 rotations.
-#include "moments_step.hpp"
-
-#include <cmath>
+#include "robust_step.hpp"
 
 namespace gpmpc {
 
-constexpr int ROB_MAX_NX = 4;             // the largest state dimension of the two environments
-
-struct RobustArgs : MomentStepArgs {
-    const double *Q0, *l_mu, *l_sigma;
-    int l_per;
-    double beta;
-    double W[ROB_MAX_NX][ROB_MAX_NX];                                  // upper Cholesky factor of I + K^T K (nx <= 4), identity without feedback
+struct RobustArgs : RobustStepArgs {
     double *M, *Q, *R2, *Sd, *Jz;
     int* info;
 };
-
-constexpr int JAC_SWEEPS = 8;              // cyclic Jacobi converges quadratically: a 4 x 4 matrix is diagonal to rounding after 5 - 6 sweeps
-
-// The largest eigenvalue of the symmetric matrix whose lower triangle is T (destroyed), by cyclic Jacobi; *abs_sum receives the sum of
-// the |diagonal| after the sweeps (NaN / inf if anything in T was).  Not clamped.
-template <int NX>
-__host__ __device__ __forceinline__ double sym_lambda_max(double (&T)[NX][NX], double& abs_sum) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < JAC_SWEEPS; ++sweep) {
-#pragma unroll
-        for (int p = 0; p < NX - 1; ++p)
-#pragma unroll
-            for (int q = p + 1; q < NX; ++q) {
-                const double apq = T[q][p];
-                // tan of the rotation angle: the smaller root of t^2 + 2 theta t - 1 = 0, theta = (a_qq - a_pp) / (2 a_pq)
-                double t = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (T[q][q] - T[p][p]) / (2.0 * apq);
-                    const double den = fabs(theta) + sqrt(fma(theta, theta, 1.0));
-                    t = (theta < 0.0 ? -1.0 : 1.0) / den;            // theta^2 overflows: den = inf, t = 0
-                }
-                const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
-                T[p][p] = fma(-t, apq, T[p][p]);
-                T[q][q] = fma(t, apq, T[q][q]);
-                T[q][p] = (apq != 0.0) ? 0.0 : apq;                 // NaN stays
-#pragma unroll
-                for (int r = 0; r < NX; ++r) {
-                    if (r == p || r == q) continue;
-                    double& arp = (r > p) ? T[r][p] : T[p][r];
-                    double& arq = (r > q) ? T[r][q] : T[q][r];
-                    const double vp = arp, vq = arq;
-                    arp = fma(c, vp, -(s * vq));
-                    arq = fma(s, vp, c * vq);
-                }
-            }
-    }
-    double lam = T[0][0];
-    abs_sum = fabs(T[0][0]);
-#pragma unroll
-    for (int i = 1; i < NX; ++i) {
-        abs_sum += fabs(T[i][i]);
-        lam = (T[i][i] > lam) ? T[i][i] : lam;
-    }
-    return lam;
-}
-
-// c of X (+) Y = (1 + 1/c) X + (1 + c) Y, c = sqrt(tr X / tr Y); X (+) Y = X when tr Y == 0 and Y when tr X == 0: -> the two weights
-__host__ __device__ __forceinline__ void ellipsoid_sum_weights(double trx, double try_, double& wx, double& wy) {
-    if (try_ == 0.0) {
-        wx = 1.0, wy = 0.0;
-    } else if (trx == 0.0) {
-        wx = 0.0, wy = 1.0;
-    } else {
-        const double c = sqrt(trx / try_);
-        wx = 1.0 + 1.0 / c;
-        wy = 1.0 + c;
-    }
-}
 
 template <int ENV, int NRP, bool HG>
 __global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
@@ -306,34 +240,6 @@ static int robust_launch(const RobustArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((robust_tube_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
     GPMPC_HIP_CHECK(hipGetLastError());
     return GPMPC_OK;
-}
-
-// W upper triangular with W^T W = I + K^T K (K: the first nu rows of env.K when the feedback is on, else 0): positive definite, the
-// Cholesky recursion cannot break down for finite K
-static bool robust_fill_w(RobustArgs& a, const gpmpc_env_desc_t* env) {
-    constexpr int MW = ROB_MAX_NX;
-    const int nx = env->nx;
-    double S[MW][MW];
-    for (int i = 0; i < MW; ++i)
-        for (int j = 0; j < MW; ++j) {
-            double s = (i == j) ? 1.0 : 0.0;
-            if (env->use_feedback && i < nx && j < nx)
-                for (int r = 0; r < env->nu; ++r) s += env->K[r][i] * env->K[r][j];
-            S[i][j] = s;
-            a.W[i][j] = 0.0;
-        }
-    for (int i = 0; i < MW; ++i)
-        for (int j = i; j < MW; ++j) {                                   // row i of the upper factor
-            double s = S[i][j];
-            for (int k = 0; k < i; ++k) s -= a.W[k][i] * a.W[k][j];
-            if (i == j) {
-                if (!(s > 0.0) || !std::isfinite(s)) return false;
-                a.W[i][i] = std::sqrt(s);
-            } else {
-                a.W[i][j] = s / a.W[i][i];
-            }
-        }
-    return true;
 }
 
 }  // namespace gpmpc

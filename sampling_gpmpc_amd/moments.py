@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._planning import adam_update, check_planner_args, like_input, rollout_inputs, squared_violation
+from ._planning import check_planner_args, like_input, plan_population, rollout_inputs, squared_violation
 from .hulls import HullSet, convex_hulls
 
 F64 = torch.float64
@@ -255,31 +255,12 @@ def chance_constraint_penalty(tube: MomentTube, rows, beta: float, eps: float = 
 
 
 def plan_inputs_plan(plan, env_desc, x0, U0, cost, steps: int, lr: float, P0=None):
-    """``plan_inputs`` for a ``RealDataPlan`` and an environment descriptor."""
+    """``plan_inputs`` for a ``RealDataPlan`` and an environment descriptor: the population loop of ``_planning.plan_population`` - one
+    ``adam_update(U, m, v, g, it, lr)`` per iteration, shared with ``plan_inputs_robust`` - with ``moment_rollout_plan`` as its rollout."""
     check_planner_args("plan_inputs", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
     dev = _lib.require_hip_device(plan.X_r.device)
-    U = U0.detach().to(device=dev, dtype=F64).clone()
-    B, steps = int(U.shape[0]), int(steps)
-    m, v = torch.zeros_like(U), torch.zeros_like(U)
-    hist = torch.empty(steps + 1, B, dtype=F64, device=dev)
-
-    def costs(tube, Uc):
-        c = cost(tube, Uc)
-        if not torch.is_tensor(c) or tuple(c.shape) != (B,):
-            raise _lib.GpmpcError(f"plan_inputs: cost must return a tensor ({B},), one value per candidate")
-        return c
-
-    for it in range(1, steps + 1):
-        Uc = U.detach().requires_grad_(True)
-        c = costs(moment_rollout_plan(plan, env_desc, x0, Uc, P0, differentiable=True), Uc)
-        hist[it - 1] = c.detach()
-        g, = torch.autograd.grad(c.sum(), Uc)                        # the candidates are independent: one backward launch for all
-        U, m, v = adam_update(U, m, v, g, it, lr)
-    with torch.no_grad():
-        hist[steps] = costs(moment_rollout_plan(plan, env_desc, x0, U, P0), U)
-    final = hist[steps]
-    best = torch.where(torch.isfinite(final), final, torch.full_like(final, float("inf"))).argmin()
-    return U, hist, best
+    return plan_population("plan_inputs", lambda U, differentiable: moment_rollout_plan(plan, env_desc, x0, U, P0, differentiable=differentiable),
+                           U0, cost, steps, lr, dev)
 
 
 def plan_inputs(agent, x0, U0, cost, steps: int, lr: float, P0=None, use_feedback: Optional[bool] = None):

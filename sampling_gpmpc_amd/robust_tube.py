@@ -18,7 +18,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from ._planning import rollout_inputs
+from ._planning import check_planner_args, like_input, plan_population, rollout_inputs
 from .moments import MomentTube
 
 F64 = torch.float64
@@ -49,12 +49,8 @@ def _lip_arg(name, l, nx, dev):
     return l
 
 
-def robust_tube_rollout_plan(plan, env_desc, x0, U, l_mu, l_sigma, beta: float, Q0: Optional[torch.Tensor] = None,
-                             want_parts: bool = False) -> RobustTube:
-    """``gpmpc_robust_tube_rollout`` for a ``RealDataPlan`` and an environment descriptor.  ``x0 (nx,)`` or ``(B, nx)``, ``U (H, nu)``
-    or ``(B, H, nu)``, ``l_mu`` and ``l_sigma`` both ``(nx,)`` or both ``(B, nx)``, ``beta`` a number, ``Q0 (B, nx, nx)`` or None
-    (zero: the state is a point); ``B`` is taken from whichever argument carries it (1 if none does).  ``want_parts``: also ``r2``,
-    ``sd`` and ``jz``.  One launch, no host synchronisation."""
+def _prepare(plan, env_desc, x0, U, l_mu, l_sigma, Q0):
+    """The argument handling of ``robust_tube_rollout_plan``: -> (device, x0, U, l_mu, l_sigma, Q0, B, H), float64 contiguous on the device."""
     dev = _lib.require_hip_device(plan.X_r.device)
     nx, nu = int(env_desc.nx), int(env_desc.nu)
     x0, U = rollout_inputs(x0, U, nx, nu, dev)
@@ -71,6 +67,11 @@ def robust_tube_rollout_plan(plan, env_desc, x0, U, l_mu, l_sigma, beta: float, 
     if len(sizes) > 1:
         raise _lib.GpmpcError(f"x0, U, l_mu / l_sigma and Q0 disagree on the number of candidates: {sorted(sizes)}")
     B = sizes.pop() if sizes else 1
+    return dev, x0, U, l_mu, l_sigma, Q0, B, H
+
+
+def _forward(plan, env_desc, dev, x0, U, l_mu, l_sigma, beta, Q0, B, H, want_parts) -> RobustTube:
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
     lib = _lib.load()
     parts = bool(want_parts)
     out = RobustTube(mean=torch.empty(B, nx, H + 1, dtype=F64, device=dev), cov=torch.empty(B, H + 1, nx, nx, dtype=F64, device=dev),
@@ -86,15 +87,138 @@ def robust_tube_rollout_plan(plan, env_desc, x0, U, l_mu, l_sigma, beta: float, 
     return out
 
 
+def _backward(plan, env_desc, x0, U, l_mu, l_sigma, beta, Q0, B, H, mean, cov, g_mean, g_cov):
+    """One launch of ``gpmpc_robust_tube_rollout_vjp``: per-candidate gradients ``(g_x0 (B, nx), g_U (B, H, nu), g_Q0 (B, nx, nx) or
+    None, g_l_mu (B, nx), g_l_sigma (B, nx), info (B))``."""
+    lib = _lib.load()
+    dev = x0.device                                                   # with its index, as the tube's tensors carry it
+    nx, nu = int(env_desc.nx), int(env_desc.nu)
+    for name, t, shape in (("tube.mean", mean, (B, nx, H + 1)), ("tube.cov", cov, (B, H + 1, nx, nx)),
+                           ("g_mean", g_mean, (B, nx, H + 1)), ("g_cov", g_cov, (B, H + 1, nx, nx))):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
+            raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
+    mean, cov = mean.detach().contiguous(), cov.detach().contiguous()
+    g_mean = None if g_mean is None else g_mean.detach().contiguous()
+    g_cov = None if g_cov is None else g_cov.detach().contiguous()
+    g_x0 = torch.empty(B, nx, dtype=F64, device=dev)
+    g_U = torch.empty(B, H, nu, dtype=F64, device=dev)
+    g_Q0 = None if Q0 is None else torch.empty(B, nx, nx, dtype=F64, device=dev)
+    g_l_mu, g_l_sigma = torch.empty(B, nx, dtype=F64, device=dev), torch.empty(B, nx, dtype=F64, device=dev)
+    info = torch.zeros(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.gpmpc_robust_tube_rollout_vjp(plan.desc, env_desc, _lib.dptr(plan.buf), _lib.dptr(plan.X_r), B, H, _lib.dptr(x0),
+                                                 int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), _lib.dptr(Q0), _lib.dptr(l_mu),
+                                                 _lib.dptr(l_sigma), int(l_mu.dim() == 2), float(beta), _lib.dptr(mean), _lib.dptr(cov),
+                                                 _lib.dptr(g_mean), _lib.dptr(g_cov), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(g_Q0),
+                                                 _lib.dptr(g_l_mu), _lib.dptr(g_l_sigma), _lib.dptr(info), _lib.current_stream_ptr()),
+               "gpmpc_robust_tube_rollout_vjp")
+    return g_x0, g_U, g_Q0, g_l_mu, g_l_sigma, info
+
+
+class _RobustRollout(torch.autograd.Function):
+    """``gpmpc_robust_tube_rollout`` with ``gpmpc_robust_tube_rollout_vjp`` as its backward; ``r2``, ``sd``, ``jz`` and ``info`` carry no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, U, Q0, l_mu, l_sigma, plan, env_desc, beta, B, H, want_parts):
+        out = _forward(plan, env_desc, x0.device, x0, U, l_mu, l_sigma, beta, Q0, B, H, want_parts)
+        ctx.plan, ctx.env_desc, ctx.beta, ctx.sizes, ctx.has_q0 = plan, env_desc, beta, (B, H), Q0 is not None
+        ctx.save_for_backward(x0, U, l_mu, l_sigma, out.mean, out.cov, *(() if Q0 is None else (Q0,)))
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (out.info, out.r2, out.sd, out.jz) if t is not None))
+        return out.mean, out.cov, out.info, out.r2, out.sd, out.jz
+
+    @staticmethod
+    def backward(ctx, g_mean, g_cov, *_):
+        x0, U, l_mu, l_sigma, mean, cov = ctx.saved_tensors[:6]
+        Q0 = ctx.saved_tensors[6] if ctx.has_q0 else None
+        B, H = ctx.sizes
+        if g_mean is None and g_cov is None:
+            return (None,) * 11
+        g_x0, g_U, g_Q0, g_lm, g_ls, _ = _backward(ctx.plan, ctx.env_desc, x0, U, l_mu, l_sigma, ctx.beta, Q0, B, H, mean, cov, g_mean, g_cov)
+        need = ctx.needs_input_grad
+        per_l = l_mu.dim() == 2
+        return (like_input(g_x0, x0.dim() == 2) if need[0] else None, like_input(g_U, U.dim() == 3) if need[1] else None,
+                g_Q0 if (need[2] and ctx.has_q0) else None, like_input(g_lm, per_l) if need[3] else None,
+                like_input(g_ls, per_l) if need[4] else None, None, None, None, None, None, None)
+
+
+def robust_tube_rollout_plan(plan, env_desc, x0, U, l_mu, l_sigma, beta: float, Q0: Optional[torch.Tensor] = None,
+                             want_parts: bool = False, differentiable: bool = False) -> RobustTube:
+    """``gpmpc_robust_tube_rollout`` for a ``RealDataPlan`` and an environment descriptor.  ``x0 (nx,)`` or ``(B, nx)``, ``U (H, nu)``
+    or ``(B, H, nu)``, ``l_mu`` and ``l_sigma`` both ``(nx,)`` or both ``(B, nx)``, ``beta`` a number, ``Q0 (B, nx, nx)`` or None
+    (zero: the state is a point); ``B`` is taken from whichever argument carries it (1 if none does).  ``want_parts``: also ``r2``,
+    ``sd`` and ``jz``.  One launch, no host synchronisation.  ``differentiable=True``: ``mean`` and ``cov`` carry a ``grad_fn`` whose
+    backward is one launch of ``gpmpc_robust_tube_rollout_vjp``; ``x0``, ``U``, ``Q0``, ``l_mu`` and ``l_sigma`` receive gradients if
+    they require them (``r2``, ``sd``, ``jz`` and ``info`` are not differentiable); the values are those of the default call, bit for
+    bit.  ``chance_constraint_penalty(tube, rows, 1.0)`` of such a tube is the squared violation of the rows by the support function
+    ``E p +- sqrt(E Q E^T)`` of the ellipsoids: the constraint ingredient of a cost on the robust tube."""
+    dev, x0, U, l_mu, l_sigma, Q0, B, H = _prepare(plan, env_desc, x0, U, l_mu, l_sigma, Q0)
+    if not differentiable:
+        return _forward(plan, env_desc, dev, x0, U, l_mu, l_sigma, beta, Q0, B, H, want_parts)
+    mean, cov, info, r2, sd, jz = _RobustRollout.apply(x0, U, Q0, l_mu, l_sigma, plan, env_desc, float(beta), B, H, bool(want_parts))
+    return RobustTube(mean=mean, cov=cov, info=info, r2=r2, sd=sd, jz=jz)
+
+
+def _agent_beta(agent, beta):
+    return float(agent.params["agent"]["Dyn_gp_beta"]) if beta is None else beta
+
+
 def robust_tube_rollout(agent, x0, U, l_mu, l_sigma, beta: Optional[float] = None, Q0=None, use_feedback: Optional[bool] = None,
-                        want_parts: bool = False) -> RobustTube:
+                        want_parts: bool = False, differentiable: bool = False) -> RobustTube:
     """The robust ellipsoidal tube of ``B`` candidates under the model and environment of ``moment_rollout(agent, ...)``:
     ``agent._plan(use_grad=True)`` and ``agent.env_desc(use_feedback)`` (None: ``agent.feedback.use``).  ``beta`` None: the agent's
     ``params["agent"]["Dyn_gp_beta"]``, the reference's ``cem_beta_safety``.  See ``robust_tube_rollout_plan``."""
     _lib.require_hip_device(agent.torch_device)
-    if beta is None:
-        beta = float(agent.params["agent"]["Dyn_gp_beta"])
-    return robust_tube_rollout_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U, l_mu, l_sigma, beta, Q0, want_parts)
+    return robust_tube_rollout_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U, l_mu, l_sigma, _agent_beta(agent, beta),
+                                    Q0, want_parts, differentiable)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reverse-mode gradient and the planner on it
+# ---------------------------------------------------------------------------------------------------------------------
+def robust_tube_rollout_vjp_plan(plan, env_desc, tube: RobustTube, x0, U, l_mu, l_sigma, beta: float, Q0=None, g_mean=None, g_cov=None):
+    """``gpmpc_robust_tube_rollout_vjp`` (include/gpmpc_hip.h) for a ``RealDataPlan`` and an environment descriptor: the gradients of
+    ``sum(g_mean * tube.mean) + sum(g_cov * tube.cov)`` with respect to the inputs ``tube`` was computed from.  Returns
+    ``(g_x0, g_U, g_Q0, g_l_mu, g_l_sigma, info)`` with the shapes of the inputs - summed over the candidates where the input was
+    shared, ``g_Q0`` None when ``Q0`` was (it comes back on the lower triangle, the part of ``Q0`` that is read) - and ``info (B)``
+    int32.  A cotangent that is None is zero.  One launch, no host synchronisation."""
+    _, x0, U, l_mu, l_sigma, Q0, B, H = _prepare(plan, env_desc, x0, U, l_mu, l_sigma, Q0)
+    g_x0, g_U, g_Q0, g_lm, g_ls, info = _backward(plan, env_desc, x0, U, l_mu, l_sigma, beta, Q0, B, H, tube.mean, tube.cov, g_mean, g_cov)
+    per_l = l_mu.dim() == 2
+    return like_input(g_x0, x0.dim() == 2), like_input(g_U, U.dim() == 3), g_Q0, like_input(g_lm, per_l), like_input(g_ls, per_l), info
+
+
+def robust_tube_rollout_vjp(agent, tube: RobustTube, x0, U, l_mu, l_sigma, beta: Optional[float] = None, Q0=None, g_mean=None,
+                            g_cov=None, use_feedback: Optional[bool] = None):
+    """``robust_tube_rollout_vjp_plan`` with the model, environment and ``beta`` ``robust_tube_rollout(agent, ...)`` uses (the reference
+    has no counterpart: the optimiser of Koller's MPC lives in the external library)."""
+    _lib.require_hip_device(agent.torch_device)
+    return robust_tube_rollout_vjp_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), tube, x0, U, l_mu, l_sigma,
+                                        _agent_beta(agent, beta), Q0, g_mean, g_cov)
+
+
+def plan_inputs_robust_plan(plan, env_desc, x0, U0, l_mu, l_sigma, beta: float, cost, steps: int, lr: float, Q0=None):
+    """``plan_inputs_robust`` for a ``RealDataPlan`` and an environment descriptor (``beta`` a number)."""
+    check_planner_args("plan_inputs_robust", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
+    dev = _lib.require_hip_device(plan.X_r.device)
+    return plan_population("plan_inputs_robust", lambda U, differentiable: robust_tube_rollout_plan(
+        plan, env_desc, x0, U, l_mu, l_sigma, beta, Q0, differentiable=differentiable), U0, cost, steps, lr, dev)
+
+
+def plan_inputs_robust(agent, x0, U0, l_mu, l_sigma, cost, steps: int, lr: float, beta: Optional[float] = None, Q0=None,
+                       use_feedback: Optional[bool] = None):
+    """``plan_inputs`` on the robust tube - the optimisation Koller's method is, which the reference leaves to an external library:
+    Adam (``torch.optim.Adam``'s update and defaults) on a population ``U0 (B, H, nu)`` of ``cost(tube, U) -> (B,)``, any torch function
+    of the differentiable ``robust_tube_rollout(agent, x0, U, l_mu, l_sigma, beta, Q0, differentiable=True)`` and of ``U``, with the
+    Lipschitz constants held fixed (``estimate_lipschitz`` is not run again inside the loop).
+    ``chance_constraint_penalty(tube, rows, 1.0)`` is the constraint ingredient: with ``beta = 1`` its tightening is the support
+    function ``E p +- sqrt(E Q E^T)`` of the ellipsoid.  Returns what ``plan_inputs`` returns: the final ``U (B, H, nu)``, the cost
+    history ``(steps + 1, B)`` - row ``k`` is the cost before update ``k + 1``, the last row that of the result - and the index of
+    the best candidate (0-dim, on the device).  One forward and one backward launch per iteration, no host round trip in the loop."""
+    check_planner_args("plan_inputs_robust", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
+    _lib.require_hip_device(agent.torch_device)
+    return plan_inputs_robust_plan(agent._plan(use_grad=True), agent.env_desc(use_feedback), x0, U0, l_mu, l_sigma, _agent_beta(agent, beta),
+                                   cost, steps, lr, Q0)
 
 
 def pairwise_lipschitz(X: torch.Tensor, F: torch.Tensor, eps: float = 1e-6,
