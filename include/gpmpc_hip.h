@@ -59,6 +59,8 @@ extern "C" {
                                              * or a noise variance < 0: every output of that problem is NaN               */
 #define GPMPC_INFO_NONFINITE         0x0800 /* gpmpc_moment_rollout: an input of the candidate or a value computed for it was
                                              * not finite: its outputs are NaN from that step on (gpmpc_pathwise_*: likewise) */
+#define GPMPC_INFO_BAD_CANDIDATE     0x1000 /* gpmpc_contraction_rates: the candidate's P has a non-positive Cholesky pivot, or its
+                                             * P, K or rho holds a non-finite entry                                        */
 
 /* root_mode of gpmpc_joint_sample */
 #define GPMPC_ROOT_AUTO      0   /* gpytorch: Cholesky with the jitter chain; if ANY chain of the batch fails all  */
@@ -1097,6 +1099,47 @@ int     gpmpc_pairwise_lipschitz(int64_t N, int32_t dx, int32_t G, int32_t df, c
                                  const double* F /* (N, G, df) */, double eps, double* out_max /* (G) */,
                                  int64_t* out_pair /* (G, 2) */, int64_t* out_skipped /* (1) or NULL */, int32_t max_blocks,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * gpmpc_contraction_rates - how fast the closed loops of N sampled Jacobian pairs contract in the norms of C candidate terminal sets:
+ *   r[c, i] = | P_c^(1/2) (A_i + B_i K_c) P_c^(-1/2) |_2 = sqrt(lambda_max(L_c^-1 (A_i + B_i K_c)^T P_c (A_i + B_i K_c) L_c^-T)),
+ * P_c = L_c L_c^T, and per candidate the largest rate, the pair that attains it and the number of pairs above rho_c.  Additive entry
+ * points: the ABI version stays 12.
+ * Replaces: the verification loops of the reference's offline scripts (extra/pendulum_mpi.py:410-468, extra/car_mpi.py:180-238: the
+ * worst | P^(1/2) (A + B K) P^(-1/2) |_2 over a set of Jacobians, one numpy norm per pair on the host - the number typed into the
+ * YAMLs as tight.Lipschitz), and it is the check over all pairs of a constraint-generation solve of their synthesis problem
+ * (pendulum_mpi.py:27-58, 98-218, car_mpi.py:15-153, invariant_Set.py:97-198: one 2n x 2n LMI block per pair in cvxpy).
+ *   A [dev] (Ns, nx, H, nx), B [dev] (Ns, nx, H, nu)   read in place in the layout of y_grad / u_grad of gpmpc_assemble_jacobians;
+ *                       N = Ns H, the pair index is i = s H + t.  A packed (N, nx, nx) / (N, nx, nu) buffer is H = 1.
+ *   P [dev] (C, nx, nx) (the lower triangle is read), K [dev] (C, nu, nx), rho [dev] (C)
+ *   max_rate [dev] (C)           out: the largest rate
+ *   argmax   [dev] (C) int64     out: the lowest pair index that attains it
+ *   n_above  [dev] (C) int64     out: the number of pairs with r > rho_c
+ *   rates    [dev] (C, N)        out or NULL: every rate; NULL: nothing of size N is written
+ *   info     [dev] (C) uint32    out: 0, GPMPC_INFO_NONFINITE, GPMPC_INFO_BAD_CANDIDATE
+ *   max_blocks   persistent workgroups walk the tiles of 256 pairs on a grid of at most max_blocks workgroups (<= 0: the library
+ *                chooses, 2048; at most 65536)
+ *   workspace [dev], workspace_bytes >= gpmpc_contraction_rates_workspace_bytes of the same Ns, H, nx, nu, C, max_blocks: the prepared
+ *                candidates and one record per workgroup and candidate
+ * Non-finite values: a pair with a non-finite entry - or one whose rate overflows on the way - has the rate +inf for every candidate:
+ * it counts as above rho_c and wins the maximum (an unsafe answer must not look safe, as in gpmpc_tube_rows), and the candidate
+ * carries GPMPC_INFO_NONFINITE.  A candidate whose P has a non-positive Cholesky pivot, or whose P, K or rho holds a non-finite entry,
+ * gets max_rate = NaN, argmax = -1, n_above = N, NaN in its row of rates and GPMPC_INFO_BAD_CANDIDATE; no other candidate is touched.
+ * N = 0 launches nothing and writes nothing.
+ * Reproducibility: a rate is one fixed chain of operations in the entries of the pair and of the candidate - its bits depend on
+ * neither N, the pair's position nor C -, and the maximum (larger rate, then lower index), the count and the flags are folded per wave,
+ * per workgroup and by a finishing kernel without atomics: all outputs are bit-identical for every max_blocks.
+ * Limits: 1 <= nx <= 4, 1 <= nu <= 2 (those of gpmpc_tube_gram), 1 <= C <= 16, N < 2^40; GPMPC_E_UNSUPPORTED beyond.  GPMPC_E_ARG
+ * (before any device work): Ns < 0; H, nx, nu or C < 1; max_blocks > 65536; NULL P, K, rho, max_rate, argmax, n_above or info; with
+ * N > 0 NULL A or B.  GPMPC_E_WORKSPACE: with N > 0 a NULL workspace or workspace_bytes below the size function's value.  The size
+ * function returns 0 for sizes it rejects.  No hidden allocation, no host round trip, everything goes to `stream`.
+ */
+size_t  gpmpc_contraction_rates_workspace_bytes(int64_t Ns, int32_t H, int32_t nx, int32_t nu, int32_t C, int32_t max_blocks);
+int     gpmpc_contraction_rates(int64_t Ns, int32_t H, int32_t nx, int32_t nu, int32_t C, const double* A /* (Ns, nx, H, nx) */,
+                                const double* B /* (Ns, nx, H, nu) */, const double* P /* (C, nx, nx) */,
+                                const double* K /* (C, nu, nx) */, const double* rho /* (C) */, double* max_rate /* (C) */,
+                                int64_t* argmax /* (C) */, int64_t* n_above /* (C) */, double* rates /* (C, N) or NULL */,
+                                uint32_t* info /* (C) */, int32_t max_blocks, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@ INFO_EIGH_NOCONV = 0x0100
 INFO_STATE_FULL = 0x0200
 INFO_BAD_HYPER = 0x0400                                 # gpmpc_marginal_likelihood
 INFO_NONFINITE = 0x0800                                 # gpmpc_moment_rollout, gpmpc_robust_tube_rollout, gpmpc_pathwise_*
+INFO_BAD_CANDIDATE = 0x1000                             # gpmpc_contraction_rates
 # gpmpc_convex_hulls: per-set info word
 HULL_OVERFLOW, HULL_NONFINITE, HULL_EMPTY, HULL_DEGENERATE = 0x1, 0x2, 0x4, 0x8
 # gpmpc_hull_query: per-set info word
@@ -129,6 +130,8 @@ SYMBOLS = {
                                                 _I32, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_pairwise_lipschitz_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
     "gpmpc_pairwise_lipschitz": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _D, _P, _P, _P, _I32, _P, _SZ, _P]),
+    "gpmpc_contraction_rates_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32]),
+    "gpmpc_contraction_rates": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

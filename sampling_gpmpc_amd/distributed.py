@@ -471,3 +471,24 @@ def all_reduce_tube_stats(stats, group=None):
         box_hi=packed[E:2 * E].reshape(stats.box_hi.shape), box_lo=-packed[2 * E:].reshape(stats.box_lo.shape),
         n_nonfinite=counts[1:2].reshape(stats.n_nonfinite.shape),
         n_within=None if stats.n_within is None else counts[2:].reshape(stats.n_within.shape))
+
+
+def all_reduce_contraction(check, offset, group=None):
+    """The per-candidate results of a ``terminal_set.contraction_rates`` over Jacobian pairs that are spread over the ranks, this rank's
+    first pair having the GLOBAL index ``offset``: ``max_rate`` is the maximum and ``argmax`` the lowest global pair index among the ranks
+    that attain it (``_all_reduce_min_index`` on the negated rates: the tie rule of one device), ``n_above`` and ``N`` are summed,
+    ``info`` is ORed.  A bad candidate is bad on every rank and stays ``NaN`` / ``-1``; a rank without pairs takes no part in the
+    maximum.  ``rates`` stays local.  Returns a new ``ContractionCheck``; works on the tensors' own device (CPU tensors under gloo).
+    Three small collectives and one host read (``N``)."""
+    import dataclasses
+    bits = torch.stack([(check.info.to(torch.int64) >> b) & 1 for b in range(16)])
+    n_local = torch.tensor([int(check.N)], dtype=torch.int64, device=check.max_rate.device)
+    packed = torch.cat([check.n_above.reshape(-1).to(torch.int64), bits.reshape(-1), n_local])
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+    C = check.max_rate.numel()
+    got = (packed[C:C + 16 * C].reshape(16, C) > 0).to(torch.int64)
+    info = sum(got[b] << b for b in range(16)).to(check.info.dtype)
+    neg, argmax = _all_reduce_min_index(-check.max_rate, check.argmax, int(offset), group)
+    _lib.host_wait(packed)
+    return dataclasses.replace(check, N=int(packed[-1].item()), max_rate=-neg, argmax=argmax, n_above=packed[:C].to(check.n_above.dtype),
+                               info=info)
