@@ -1071,6 +1071,94 @@ int     gpmpc_robust_tube_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env
                                       int32_t* info /* (B) */, void* stream);
 
 /*
+ * gpmpc_optimistic_rollout - the optimistic-dynamics (hallucinated control, H-UCRL) rollout of B candidates over H steps in one
+ * launch: the input is extended by one variable eta per model output and stage, and the dynamics are the posterior mean of the
+ * real-data GP plus beta eta times its posterior standard deviation, so that an optimiser over (U, eta) picks the most favourable
+ * dynamics inside the confidence set.  One candidate per lane, mapping and staging of gpmpc_moment_rollout.  An additive entry
+ * point: the ABI version stays 12.
+ * Replaces: reference extra/approx_sampling_mpc - agent.get_optimistic_dynamics_grad (src/agent.py:886-935: mean + eta * Dyn_gp_beta *
+ * sigma per stage, with autograd on the host), the model of utils/optimistic_ocp.py (nu += nx, eta bounded by
+ * optimistic_optimizer.u_min / u_max) as DEMPC.optimistic_planner / solver.solve_optimistic_problem roll it out - one trajectory at a
+ * time; here every candidate of a population is one call.  With S it also answers get_posterior_uncertainity (src/agent.py:231-268):
+ * the posterior variance of the real-data GP along a trajectory.
+ *
+ * For candidate b and t = 0..H-1, from x_0 = x0[b]; notation and conventions are those of gpmpc_moment_rollout (real-data GP of the
+ * plan, value-only or with derivative labels):
+ *   1. u_t, xi_t  as steps 1 - 2 of gpmpc_moment_rollout (the feedback law included);
+ *   2. m_o, s_o   the posterior mean and the latent variance of output o at xi_t, s_o raised to gp.var_floor
+ *                 (GPMPC_INFO_VAR_CLAMPED), exactly as step 3 of gpmpc_moment_rollout forms them: the kernels call the same device
+ *                 functions;
+ *   3. f_o = m_o + (beta * eta[b,t,o]) * sqrt(s_o);
+ *   4. x_{t+1} = env_step(x_t, u_t, f)  (the map of gpmpc_rollout).
+ * eta is read as given: the kernel does not clamp it (the planner projects onto [-1, 1]).  eta == NULL is zero; with eta = 0 the
+ * trajectory is gpmpc_moment_rollout's M and S its S, bit for bit.
+ *   x0, x0_per_candidate, U, u_per_candidate   as gpmpc_moment_rollout
+ *   eta  [dev] (B, H, g_ny) if eta_per_candidate else (H, g_ny), or NULL
+ *   beta                         finite, >= 0
+ *   X    [dev] (B, nx, H+1)      out: x_t in the tube layout of gpmpc_rollout's X_traj
+ *   F    [dev] (B, H, g_ny)      out or NULL: f of every step
+ *   S    [dev] (B, H, g_ny)      out or NULL: s of every step (after the floor)
+ *   info [dev] (B) int32         out: OR of GPMPC_INFO_VAR_CLAMPED and GPMPC_INFO_NONFINITE over the steps
+ * Non-finite values, as gpmpc_moment_rollout: a candidate whose x0 has a non-finite entry has NaN in every output; when U[b,t],
+ * eta[b,t] or anything computed in step t (u_t, m, s, f, x_{t+1}) is not finite, F and S of the steps >= t and X of the steps > t are
+ * NaN (the steps before keep their values).  Either way the candidate carries GPMPC_INFO_NONFINITE; no other candidate is touched.
+ * Reproducibility: a candidate's results are the same bits whatever B is and wherever it stands in the batch (one kernel path,
+ * fixed summation order, nothing shared between lanes but read-only tables).
+ * Limits and errors are those of gpmpc_moment_rollout: D = 2, both environments, any X_r, at most 64 label rows, B < 2^31:
+ * GPMPC_E_UNSUPPORTED beyond, before any device work.  GPMPC_E_ARG (before any device work): NULL gp or env; a bad gp descriptor;
+ * B < 0 or H < 0; beta negative or not finite; with B > 0 NULL plan, X_r, x0, U (H > 0), X or info; env.nx / env.nu / g_ny that do
+ * not belong to env.env_id.  B == 0: nothing is launched and the array pointers are not looked at (the descriptors, sizes and beta
+ * are still checked); H == 0: X[:, :, 0] = x0.  No workspace, no allocation, no host round trip, everything goes to `stream`.
+ */
+int     gpmpc_optimistic_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                 int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                                 int32_t u_per_candidate, const double* eta /* (B|1, H, g_ny) or NULL */, int32_t eta_per_candidate,
+                                 double beta, double* X /* (B, nx, H+1) */, double* F /* (B, H, g_ny) or NULL */,
+                                 double* S /* (B, H, g_ny) or NULL */, int32_t* info /* (B) */, void* stream);
+
+/*
+ * gpmpc_optimistic_rollout_vjp - the reverse-mode derivative (vector-Jacobian product) of the map (x0, U, eta) -> X that
+ * gpmpc_optimistic_rollout computes, exactly as that kernel defines it (the variance floor and the feedback path included).  One
+ * candidate per lane, one backward sweep t = H-1..0 that reads x_t from the forward's X (the forward is not run again).  An additive
+ * entry point: the ABI version stays 12.
+ * Replaces: the sensitivities reference src/agent.py:886-935 (get_optimistic_dynamics_grad) hands to the SQP of
+ * utils/optimistic_ocp.py stage by stage, contracted here with any cotangent of the whole trajectory in one launch for B candidates.
+ * With lam = gX[b, :, H], for t = H-1..0:
+ *   df_o/dxi_d = dm_o/dxi_d + beta eta[b,t,o] e_{o,d} / (2 sqrt(s_o)),   e_o = d s_o / d xi = -2 (K^-1 k)^T dk / dxi;
+ *                where s_o was raised to the floor sigma is a constant: the second term is exactly 0 and nothing is divided (var_floor
+ *                may be 0);
+ *   A_t = the Jacobian of x -> env_step(x, fb(x), f(xi(x, fb(x)))) at x_t (step 5 of gpmpc_moment_rollout with f for m),
+ *   B_t = d x_{t+1} / d U[b,t] at fixed x_t;
+ *   gEta[b,t,o] = beta sqrt(s_o) (B_d(x_t)^T lam)_o:  pendulum1D lam[1], car x_t[3] lam[o]  (kept where clamped: the value depends on eta);
+ *   gU[b,t] = B_t^T lam;   lam = A_t^T lam + gX[b, :, t];
+ * and gx0[b] = lam after t = 0.  First order throughout: the forward uses no Jacobian, so no Hessian of the mean or of the variance
+ * is needed.  A_t and B_t are not output.
+ *   x0, x0_per_candidate, U, u_per_candidate, eta, eta_per_candidate, beta   the forward's inputs (x0 is only checked for non-finite
+ *                                       entries: x_0 is X[:, :, 0])
+ *   X    [dev] (B, nx, H+1)             the forward's output, read
+ *   gX   [dev] (B, nx, H+1) or NULL     cotangent of X; NULL is zero
+ *   gx0  [dev] (B, nx) or NULL          out: d / d x0
+ *   gU   [dev] (B, H, nu)               out: d / d U (the feed-forward input)      (may be NULL when H == 0)
+ *   gEta [dev] (B, H, g_ny) or NULL     out: d / d eta
+ *   info [dev] (B) int32                out: GPMPC_INFO_VAR_CLAMPED, GPMPC_INFO_NONFINITE
+ * Gradients are always per candidate, also when x0 / U / eta are shared (*_per_candidate == 0): the host sums over B for a shared
+ * input, the kernel needs no cross-lane reduction and no atomics.
+ * Non-finite values: a candidate whose x0, U, eta, X or gX hold a non-finite value, or for which one is computed, has NaN in all
+ * its gradients and GPMPC_INFO_NONFINITE; no other candidate is touched.
+ * Reproducibility: a candidate's gradient bits do not depend on B or on its place in the batch.
+ * Limits and errors are those of gpmpc_optimistic_rollout (required with B > 0: plan, X_r, x0, X, info, and U and gU when H > 0);
+ * GPMPC_E_ARG / GPMPC_E_UNSUPPORTED before any device work.  B == 0: nothing is launched and the array pointers are not looked at.
+ * H == 0: gx0 = gX[:, :, 0].  No workspace, no allocation, no host round trip, everything goes to `stream`.
+ */
+int     gpmpc_optimistic_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                                     int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
+                                     int32_t u_per_candidate, const double* eta /* (B|1, H, g_ny) or NULL */,
+                                     int32_t eta_per_candidate, double beta, const double* X /* (B, nx, H+1) */,
+                                     const double* gX /* (B, nx, H+1) or NULL */, double* gx0 /* (B, nx) or NULL */,
+                                     double* gU /* (B, H, nu) */, double* gEta /* (B, H, g_ny) or NULL */, int32_t* info /* (B) */,
+                                     void* stream);
+
+/*
  * gpmpc_pairwise_lipschitz - the sampled Lipschitz constant of G vector functions over N points: for every group g
  *   out_max[g] = max over i < j of |F[i,g,:] - F[j,g,:]|_2 / (|X[i,:] - X[j,:]|_2 + eps),
  * as a tiled sweep over the N (N - 1) / 2 pairs that never forms an N x N array.  Additive entry points: the ABI version stays 12.

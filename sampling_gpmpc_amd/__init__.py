@@ -22,6 +22,8 @@ from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats,
                        tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled)
 from .robust_tube import (RobustTube, robust_tube_rollout, robust_tube_rollout_plan, pairwise_lipschitz, estimate_lipschitz,  # noqa: F401
                           robust_tube_rollout_vjp, robust_tube_rollout_vjp_plan, plan_inputs_robust, plan_inputs_robust_plan)
+from .optimistic import (OptimisticTube, optimistic_rollout, optimistic_rollout_plan, optimistic_rollout_vjp,  # noqa: F401
+                         optimistic_rollout_vjp_plan, plan_inputs_optimistic, plan_inputs_optimistic_plan)
 from .terminal_set import (ContractionCheck, TerminalSet, contraction_rates, sample_terminal_jacobians, fit_terminal_set,  # noqa: F401
                            terminal_to_params)
 
@@ -38,4 +40,5 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "plan_inputs_sampled", "RobustTube", "robust_tube_rollout", "robust_tube_rollout_plan", "robust_tube_rollout_vjp",
            "robust_tube_rollout_vjp_plan", "plan_inputs_robust", "plan_inputs_robust_plan", "pairwise_lipschitz",
            "estimate_lipschitz", "ContractionCheck", "TerminalSet", "contraction_rates", "sample_terminal_jacobians", "fit_terminal_set",
-           "terminal_to_params"]
+           "terminal_to_params", "OptimisticTube", "optimistic_rollout", "optimistic_rollout_plan", "optimistic_rollout_vjp",
+           "optimistic_rollout_vjp_plan", "plan_inputs_optimistic", "plan_inputs_optimistic_plan"]

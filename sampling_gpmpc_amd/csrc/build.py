@@ -15,7 +15,8 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "rollout_one.hip", "rollout_indep.hip", "joint.hip",
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
            "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
-           "pathwise_stats.hip", "pathwise_grad.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip"]
+           "pathwise_stats.hip", "pathwise_grad.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip",
+           "optimistic.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce

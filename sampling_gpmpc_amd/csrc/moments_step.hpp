@@ -258,14 +258,15 @@ struct MomGpGrad {                         // one output at xi: the label sums w
 
 // The GP passes of a backward step for one output: pass 1 with the Hessian sums, the variance, and pass 2, w = L^-T acc column by
 // column and d s / d xi_d = -2 sum_j w_j d k_j / d xi_d (the kernel rows are formed again, one exponential per real point).
-template <int NRP, bool HG>
+// HESS = false leaves the Hessian sums of r.g at zero (optimistic_rollout_vjp_kernel, optimistic.hip: a first-order backward).
+template <int NRP, bool HG, bool HESS = true>
 __host__ __device__ __forceinline__ void mom_gp_grad(const GpParams& gp, const double* LT, const double* al, const double* xr_s, int n,
                                                      const double (&il)[2], double os, const double (&xi)[2], int& info_acc, MomGpGrad& r) {
     constexpr int TR = HG ? 3 : 1;
     double acc[MOM_ACC<NRP>];
 #pragma unroll
     for (int i = 0; i < NRP; ++i) acc[i] = 0.0;
-    const double ss = mom_gp_pass1<NRP, HG, true>(LT, al, xr_s, n, il, os, xi, acc, r.g);
+    const double ss = mom_gp_pass1<NRP, HG, HESS>(LT, al, xr_s, n, il, os, xi, acc, r.g);
     double k = 0.0, q[2] = {0.0, 0.0};
     const bool clamped = mom_variance(gp, os, ss, r.s, info_acc);
     double e0 = 0.0, e1 = 0.0;
