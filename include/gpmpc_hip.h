@@ -893,6 +893,51 @@ int     gpmpc_pathwise_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_de
                                    double* gU /* (Ns, H, nu) */, int32_t* info /* (Ns) */, void* stream);
 
 /*
+ * gpmpc_pathwise_rollout_cand / gpmpc_pathwise_rollout_cand_vjp - the pathwise rollout of B candidate input sequences against the same
+ * Ns samples in one launch, and its reverse-mode derivative in one launch: what a sampling-based planner (random shooting, CEM,
+ * multi-start Adam) evaluates per iteration.  Additive entry points: the ABI version stays 12.
+ * Replaces: B launches of gpmpc_pathwise_rollout (and of its VJP), or one launch over B Ns rows with B copies of the normals.
+ *   X_r, M, omega, Ns, H, Z, ldz, V   the samples, exactly as gpmpc_pathwise_rollout takes them
+ *   B                                  the number of candidates
+ *   x0 [dev] (B, nx) if x0_per_candidate else (nx)
+ *   U  [dev] (B, H, nu)                one sequence per candidate, shared by the samples (may be NULL when H == 0)
+ *   X_traj [dev] (B, Ns, nx, H+1)      out of the forward, read by the VJP
+ *   Y      [dev] (B, Ns, g_ny, H, 1 + D) or NULL   out of the forward; the VJP reads it, or evaluates again when NULL
+ *   gX     [dev] (B, Ns, nx, H+1) or NULL   cotangent of X_traj; NULL is zero
+ *   gx0    [dev] (B, Ns, nx) or NULL   out: d / d x0
+ *   gU     [dev] (B, Ns, H, nu)        out: d / d U[b]                              (may be NULL when H == 0)
+ *   info   [dev] (B, Ns) int32         out
+ * Layout: slice [b] of every array has the layout of gpmpc_pathwise_rollout / _rollout_vjp, so their consumers work on views.
+ * Semantics: slice [b] is what gpmpc_pathwise_rollout (X_traj, Y, info) or gpmpc_pathwise_rollout_vjp (gx0, gU, info) returns for the
+ * same samples with u_per_sample = 0 and U = U[b], and x0 (x0[b] when x0_per_candidate) shared by the samples, bit for bit: a
+ * (candidate, sample) pair runs the device functions of those kernels.  Y given or NULL gives the same gradient bits.
+ * Gradients are per (candidate, sample): the host sums over the samples (gU.sum(1)); no cross-wave reduction and no atomics.
+ * Reproducibility: the bits of a (candidate, sample) pair depend on its own inputs alone, not on B, Ns, its position or the tile of
+ * candidates its wave works on.
+ * Non-finite rule: a non-finite entry in sample s's Z row or in its V kills (., s) for every candidate; a non-finite entry in x0[b] or
+ * U[b, t] kills (b, .) - in the forward from step t on (x0: the whole pair), in the VJP all of the pair's gradients - as does anything
+ * non-finite that is read or computed for the pair (the rules of the two single-candidate calls).  Dead pairs carry
+ * GPMPC_INFO_NONFINITE; no other pair is touched.
+ * Limits and errors are those of gpmpc_pathwise_rollout: real_has_grad == 0; N_r <= 64; M a multiple of 128 and at most 1024; D = 2;
+ * the two environments; Ns < 2^31; and B * Ns < 2^31 (GPMPC_E_UNSUPPORTED), B >= 0 (GPMPC_E_ARG); GPMPC_E_UNSUPPORTED / GPMPC_E_ARG
+ * before any device work (required with work to do: X_r, omega, x0, Z, V, X_traj, info, and U - for the VJP also gU - when H > 0).
+ * Ns == 0 or B == 0: nothing is launched and the array pointers are not looked at.  H == 0: gx0 = gX[:, :, :, 0].  No workspace, no
+ * hidden allocation, no host round trip, everything goes to `stream`.
+ */
+int     gpmpc_pathwise_rollout_cand(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M,
+                                    const double* omega, int64_t Ns, int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate,
+                                    const double* U /* (B, H, nu) */, const double* Z, int64_t ldz, const double* V,
+                                    double* X_traj /* (B, Ns, nx, H+1) */, double* Y /* (B, Ns, g_ny, H, 1+D) or NULL */,
+                                    int32_t* info /* (B, Ns) */, void* stream);
+int     gpmpc_pathwise_rollout_cand_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M,
+                                        const double* omega, int64_t Ns, int64_t B, int32_t H, const double* x0,
+                                        int32_t x0_per_candidate, const double* U /* (B, H, nu) */, const double* Z, int64_t ldz,
+                                        const double* V, const double* X_traj /* (B, Ns, nx, H+1) */,
+                                        const double* Y /* (B, Ns, g_ny, H, 1+D) or NULL */,
+                                        const double* gX /* (B, Ns, nx, H+1) or NULL */, double* gx0 /* (B, Ns, nx) or NULL */,
+                                        double* gU /* (B, Ns, H, nu) */, int32_t* info /* (B, Ns) */, void* stream);
+
+/*
  * gpmpc_pathwise_tube_stats (ABI 12) - statistics of the tube of Ns pathwise samples WITHOUT the tube: per stage and state dimension
  * the largest deviation from a centre trajectory, the sample that attains it and the box of the samples; per sample the scaled
  * sup-norm deviation over the horizon, and how many samples stay within eps.  Normals, update vectors and trajectories of a sample

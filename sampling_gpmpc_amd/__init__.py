@@ -19,7 +19,8 @@ from .tube_qp import TubeQP, TubeQPResult, tube_gram, tube_apply, tube_cost, sol
 from .tube_rows import TubeRows, TubeRowsResult, TubeCheck, ocp_rows, check_tube  # noqa: F401
 from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F401
 from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats, pathwise_tube_stats, merge_tube_stats,  # noqa: F401
-                       tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled)
+                       tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled, pathwise_rollout_cand_vjp,
+                       plan_inputs_sampled_population)
 from .robust_tube import (RobustTube, robust_tube_rollout, robust_tube_rollout_plan, pairwise_lipschitz, estimate_lipschitz,  # noqa: F401
                           robust_tube_rollout_vjp, robust_tube_rollout_vjp_plan, plan_inputs_robust, plan_inputs_robust_plan)
 from .optimistic import (OptimisticTube, optimistic_rollout, optimistic_rollout_plan, optimistic_rollout_vjp,  # noqa: F401
@@ -37,7 +38,7 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "tube_gram", "tube_apply", "tube_cost", "solve_tube_qp", "ClosedLoop", "SurrogateSolver", "CondensedSolver",
            "TubeRows", "TubeRowsResult", "TubeCheck", "ocp_rows", "check_tube", "PathwiseSamples", "draw_omega", "rff_kernel_error",
            "TubeStats", "pathwise_tube_stats", "merge_tube_stats", "tube_stats_of", "pathwise_rollout_vjp", "sampled_tube_penalty",
-           "plan_inputs_sampled", "RobustTube", "robust_tube_rollout", "robust_tube_rollout_plan", "robust_tube_rollout_vjp",
+           "plan_inputs_sampled", "pathwise_rollout_cand_vjp", "plan_inputs_sampled_population", "RobustTube", "robust_tube_rollout", "robust_tube_rollout_plan", "robust_tube_rollout_vjp",
            "robust_tube_rollout_vjp_plan", "plan_inputs_robust", "plan_inputs_robust_plan", "pairwise_lipschitz",
            "estimate_lipschitz", "ContractionCheck", "TerminalSet", "contraction_rates", "sample_terminal_jacobians", "fit_terminal_set",
            "terminal_to_params", "OptimisticTube", "optimistic_rollout", "optimistic_rollout_plan", "optimistic_rollout_vjp",

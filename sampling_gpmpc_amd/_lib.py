@@ -120,6 +120,10 @@ SYMBOLS = {
                                          _P, _P, _P, _P]),
     "gpmpc_pathwise_rollout_vjp": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _I32, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I64,
                                              _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_pathwise_rollout_cand": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _I32, _P, _I64, _I64, _I32, _P, _I32, _P, _P, _I64,
+                                              _P, _P, _P, _P, _P]),
+    "gpmpc_pathwise_rollout_cand_vjp": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _I32, _P, _I64, _I64, _I32, _P, _I32, _P, _P,
+                                                  _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gpmpc_pathwise_tube_stats_workspace_bytes": (_SZ, [C.POINTER(GpDesc), _I32, _I32, _I32, _I32, _I32]),
     "gpmpc_pathwise_tube_stats": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _P, _I32, _P, C.c_uint64, _I64, _I64, _I32,
                                             _P, _P, _P, C.POINTER(C.c_double), _I32, C.POINTER(C.c_double), _P, _P, _P, _P, _P, _P, _P,

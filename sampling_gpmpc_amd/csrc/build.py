@@ -15,7 +15,7 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "rollout_one.hip", "rollout_indep.hip", "joint.hip",
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
            "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
-           "pathwise_stats.hip", "pathwise_grad.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip",
+           "pathwise_stats.hip", "pathwise_grad.hip", "pathwise_cand.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip",
            "optimistic.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
@@ -60,7 +60,10 @@ EXTRA_FLAGS = {"rollout_fast.hip": os.environ.get("GPMPC_FAST_FLAGS", "-mllvm -d
                # the pathwise VJP: with machine-LICM the step-invariant descriptor loads are hoisted over the backward sweep (161 / 241
                # VGPRs, 3 / 2 waves per SIMD); without it 120 / 201 VGPRs, 4 / 2 waves per SIMD, no scratch either way; measured on the
                # loop before its loads moved a step ahead: the car 3 - 6 % faster without, the pendulum 2 - 10 % slower
-               "pathwise_grad.hip": os.environ.get("GPMPC_PATHWISE_GRAD_FLAGS", "-mllvm -disable-machine-licm").split()}
+               "pathwise_grad.hip": os.environ.get("GPMPC_PATHWISE_GRAD_FLAGS", "-mllvm -disable-machine-licm").split(),
+               # the candidate kernels: with machine-LICM the invariants are hoisted over the candidate loop as well (forward 142 / 172,
+               # VJP 179 / 256 VGPRs, the car's VJP at one wave per SIMD); without it 99 / 129 and 136 / 216, no scratch either way
+               "pathwise_cand.hip": os.environ.get("GPMPC_PATHWISE_CAND_FLAGS", "-mllvm -disable-machine-licm").split()}
 
 
 STAMP = os.path.join(OBJDIR, "flags.stamp")

@@ -26,7 +26,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._planning import adam_update, check_planner_args, like_input, rollout_inputs, squared_violation
+from ._planning import adam_update, check_planner_args, like_input, plan_population, rollout_inputs, squared_violation
 
 F64 = torch.float64
 M_STEP, MAX_M, MAX_ROWS = 128, 1024, 64          # include/gpmpc_hip.h, gpmpc_pathwise_*: the limits
@@ -223,6 +223,23 @@ class PathwiseSamples:
                                               _lib.current_stream_ptr()), "gpmpc_pathwise_rollout")
         return X, Y, info
 
+    def rollout_candidates(self, x0, U, use_feedback: Optional[bool] = None, want_samples: bool = False, env_desc=None,
+                           differentiable: bool = False):
+        """The tubes ``X (B, Ns, nx, H+1)`` of ``B`` candidate input sequences ``U (B, H, nu)`` against the same ``Ns`` samples in one
+        launch (``gpmpc_pathwise_rollout_cand``); ``x0 (nx,)`` or one per candidate ``(B, nx)``.  Slice ``[b]`` has the bits of
+        ``self.rollout(x0 or x0[b], U[b])`` and its layout: ``sampled_tube_penalty``, ``check_tube``, ``convex_hulls`` and ``hull_query``
+        work on it as a view.  ``want_samples``: also ``Y (B, Ns, g_ny, H, 1 + D)``, returned as ``(X, Y)``.  ``self.last_info`` is
+        ``(B, Ns)`` int32.  ``differentiable=True``: ``X`` carries a ``grad_fn`` whose backward is one launch of
+        ``gpmpc_pathwise_rollout_cand_vjp``; a gradient for ``U`` is the sum over the samples, one for a shared ``x0`` the sum over
+        candidates and samples; the values are those of the default call, bit for bit."""
+        dev = _lib.require_hip_device(self.Z.device)
+        env_desc = self._env_desc(use_feedback, env_desc)
+        x0, U = _cand_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev)
+        X, Y, info = (_PathwiseRolloutCand.apply(x0, U, self, env_desc, bool(want_samples)) if differentiable
+                      else _launch_rollout_cand(self, x0, U, env_desc, want_samples))
+        self.last_info = info
+        return (X, Y) if want_samples else X
+
 
 def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
     """The arithmetic of ``evaluate`` (value and gradient at a shared ``(m, D)`` point set) in plain torch operations on the samples'
@@ -409,6 +426,122 @@ def plan_inputs_sampled(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: 
     with torch.no_grad():
         hist[steps] = mean_cost(samples.rollout(x0, U, env_desc=env_desc), U)
     return U, hist
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# B candidate input sequences against the same samples: one launch forward, one backward
+# ---------------------------------------------------------------------------------------------------------------------
+def _cand_inputs(x0, U, nx: int, nu: int, dev):
+    """``x0 (nx,) | (B, nx)`` and ``U (B, H, nu)`` as ``rollout_inputs`` prepares them; here ``U`` always has its candidate axis."""
+    U = torch.as_tensor(U, dtype=F64)
+    if U.dim() != 3:
+        raise _lib.GpmpcError(f"U must be (B, H, {nu}): one input sequence per candidate")
+    return rollout_inputs(x0, U, nx, nu, dev, n=int(U.shape[0]))
+
+
+def _launch_rollout_cand(samples: PathwiseSamples, x0, U, env_desc, want_samples):
+    """One launch of ``gpmpc_pathwise_rollout_cand`` for inputs ``_cand_inputs`` has prepared: ``(X_traj, Y or None, info)``."""
+    lib = _lib.load()
+    dev, d = samples.Z.device, samples.plan.desc
+    Ns, B, nx, H = samples.Ns, int(U.shape[0]), int(env_desc.nx), int(U.shape[1])
+    X = torch.empty(B, Ns, nx, H + 1, dtype=F64, device=dev)
+    Y = torch.empty(B, Ns, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
+    info = torch.zeros(B, Ns, dtype=torch.int32, device=dev)
+    _lib.check(lib.gpmpc_pathwise_rollout_cand(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, B,
+                                               H, _lib.dptr(x0), int(x0.dim() == 2), _lib.dptr(U), samples.Z.data_ptr(), samples._ldz(),
+                                               _lib.dptr(samples.V), _lib.dptr(X), _lib.dptr(Y), _lib.dptr(info),
+                                               _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_cand")
+    return X, Y, info
+
+
+def _rollout_cand_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
+    """One launch of ``gpmpc_pathwise_rollout_cand_vjp``: the gradients per (candidate, sample) ``(g_x0 (B, Ns, nx), g_U (B, Ns, H, nu),
+    info (B, Ns))``."""
+    lib = _lib.load()
+    dev = samples.Z.device
+    d = samples.plan.desc
+    Ns, B, nx, nu, H = samples.Ns, int(U.shape[0]), int(env_desc.nx), int(env_desc.nu), int(U.shape[1])
+    for name, t, shape in (("X_traj", X_traj, (B, Ns, nx, H + 1)), ("g_X", g_X, (B, Ns, nx, H + 1)),
+                           ("Y", Y, (B, Ns, d.g_ny, H, 1 + d.D))):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
+            raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
+    X_traj = X_traj.detach().contiguous()
+    Y = None if Y is None else Y.detach().contiguous()
+    g_X = None if g_X is None else g_X.detach().contiguous()
+    g_x0 = torch.empty(B, Ns, nx, dtype=F64, device=dev)
+    g_U = torch.empty(B, Ns, H, nu, dtype=F64, device=dev)
+    info = torch.zeros(B, Ns, dtype=torch.int32, device=dev)
+    _lib.check(lib.gpmpc_pathwise_rollout_cand_vjp(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns,
+                                                   B, H, _lib.dptr(x0.detach()), int(x0.dim() == 2), _lib.dptr(U.detach()),
+                                                   samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X_traj),
+                                                   _lib.dptr(Y), _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info),
+                                                   _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_cand_vjp")
+    return g_x0, g_U, info
+
+
+def _sum_cand(g_x0, g_U, x0_per_candidate: bool):
+    """The host's sums over the samples: ``g_U (B, H, nu)``, and ``g_x0 (B, nx)`` or - for a shared ``x0`` - ``(nx,)``."""
+    return (g_x0.sum(1) if x0_per_candidate else g_x0.sum((0, 1))), g_U.sum(1)
+
+
+class _PathwiseRolloutCand(torch.autograd.Function):
+    """``gpmpc_pathwise_rollout_cand`` with ``gpmpc_pathwise_rollout_cand_vjp`` as its backward; ``Y`` and ``info`` carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, U, samples, env_desc, want_samples):
+        X, Y, info = _launch_rollout_cand(samples, x0, U, env_desc, want_samples)
+        ctx.samples, ctx.env_desc, ctx.has_y = samples, env_desc, Y is not None
+        ctx.save_for_backward(x0, U, X, *(() if Y is None else (Y,)))
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(*(t for t in (Y, info) if t is not None))
+        return X, Y, info
+
+    @staticmethod
+    def backward(ctx, g_X, *_):
+        if g_X is None:
+            return (None,) * 5
+        x0, U, X = ctx.saved_tensors[:3]
+        Y = ctx.saved_tensors[3] if ctx.has_y else None
+        g_x0, g_U, _ = _rollout_cand_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X)
+        g_x0, g_U = _sum_cand(g_x0, g_U, x0.dim() == 2)
+        need = ctx.needs_input_grad
+        return g_x0 if need[0] else None, g_U if need[1] else None, None, None, None
+
+
+def pathwise_rollout_cand_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, use_feedback: Optional[bool] = None, env_desc=None):
+    """``gpmpc_pathwise_rollout_cand_vjp`` (include/gpmpc_hip.h): the gradients of ``sum(g_X * X_traj)`` with respect to the inputs the
+    tubes ``X_traj = samples.rollout_candidates(x0, U)`` were computed from.  Returns ``(g_x0, g_U, info)``: ``g_U (B, H, nu)`` and
+    ``g_x0`` - ``(B, nx)``, or ``(nx,)`` for a shared ``x0`` - are summed over the samples (the kernel writes per pair: no atomics), ``info
+    (B, Ns)`` is int32.  ``Y``: the rollout's samples (``want_samples=True``) spare their evaluation; the gradient bits are the same
+    without.  ``g_X`` None is zero.  One launch, no host synchronisation."""
+    dev = _lib.require_hip_device(samples.Z.device)
+    env_desc = samples._env_desc(use_feedback, env_desc)
+    x0, U = _cand_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev)
+    if not torch.is_tensor(X_traj):
+        raise _lib.GpmpcError("X_traj must be the tensor samples.rollout_candidates returned")
+    g_x0, g_U, info = _rollout_cand_backward(samples, env_desc, x0, U, X_traj, Y, g_X)
+    return (*_sum_cand(g_x0, g_U, x0.dim() == 2), info)
+
+
+def plan_inputs_sampled_population(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: float, use_feedback: Optional[bool] = None,
+                                   env_desc=None):
+    """``plan_inputs_sampled`` for a population: Adam on ``B`` input sequences ``U0 (B, H, nu)`` at once, each against the whole sampled
+    tube (multi-start, or the candidates of a sampling-based planner).  ``cost(X (B, Ns, nx, H+1), U (B, H, nu)) -> (B,)`` is any torch
+    function of the differentiable tubes ``samples.rollout_candidates(x0, U, differentiable=True)``, e.g. the mean over the samples of
+    ``sampled_tube_penalty`` of every slice.  The loop is ``_planning.plan_population``, that of ``plan_inputs``: returns the final
+    ``U (B, H, nu)``, the cost history ``(steps + 1, B)`` and the index of the best candidate.  One forward (which keeps ``Y``) and one
+    backward launch per iteration, no host round trip inside the loop."""
+    check_planner_args("plan_inputs_sampled_population", U0, 3, cost, steps, lr, "(B, H, nu): the population of input sequences")
+    dev = _lib.require_hip_device(samples.Z.device)
+    env_desc = samples._env_desc(use_feedback, env_desc)
+
+    def rollout(U, differentiable):
+        # with the samples kept: the backward then evaluates nothing again (same gradient bits: DESIGN 4.13c)
+        if differentiable:
+            return samples.rollout_candidates(x0, U, want_samples=True, env_desc=env_desc, differentiable=True)[0]
+        return samples.rollout_candidates(x0, U, env_desc=env_desc)
+
+    return plan_population("plan_inputs_sampled_population", rollout, U0, cost, steps, lr, dev)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,11 +1,11 @@
 // Stand-alone host program for a sanitizer run of the argument-check path of gpmpc_pathwise_fit / _eval / _rollout (csrc/pathwise.hip),
-// gpmpc_pathwise_rollout_vjp (csrc/pathwise_grad.hip) and gpmpc_pathwise_tube_stats (csrc/pathwise_stats.hip).  No call here reaches a
-// launch: every one must be decided before any device work, so the program needs no GPU.
+// gpmpc_pathwise_rollout_vjp (csrc/pathwise_grad.hip), gpmpc_pathwise_tube_stats (csrc/pathwise_stats.hip) and
+// gpmpc_pathwise_rollout_cand / _cand_vjp (csrc/pathwise_cand.hip).  No call here reaches a launch: every one must be decided before any device work, so the program needs no GPU.
 // Host code only - never run it on a GPU machine or load the instrumented object into Python.
 //
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //         -I include -I sampling_gpmpc_amd/csrc -x hip tools/sanitize_pathwise_args.cpp sampling_gpmpc_amd/csrc/pathwise.hip \
-//         sampling_gpmpc_amd/csrc/pathwise_grad.hip sampling_gpmpc_amd/csrc/pathwise_stats.hip \
+//         sampling_gpmpc_amd/csrc/pathwise_grad.hip sampling_gpmpc_amd/csrc/pathwise_stats.hip sampling_gpmpc_amd/csrc/pathwise_cand.hip \
 //         -fsanitize=address,undefined -o /tmp/sanitize_pathwise_args && /tmp/sanitize_pathwise_args
 #include <climits>
 #include <cstdint>
@@ -63,7 +63,9 @@ int main() {
         return gpmpc_pathwise_tube_stats(g, e, arr, arr, arr, M, arr, 7, offset, Ns, H, arr, arr, arr, scale, n_eps, eps ? eps : &half, arr, lp,
                                          arr, arr, arr, lp, lp, 2, arr, short_ws ? ws - 1 : ws, nullptr);
     };
-    // which: 0 fit, 1 eval, 2 rollout, 3 rollout_vjp, 4 tube_stats (it has no ldz: it sizes its own rows); ldz == -1: the exact width V
+    // which: 0 fit, 1 eval, 2 rollout, 3 rollout_vjp, 4 tube_stats (it has no ldz: it sizes its own rows), 5 rollout_cand, 6
+    // rollout_cand_vjp (B candidates); ldz == -1: the exact width V
+    int64_t B = 3;
     auto call = [&](int which, const gpmpc_gp_desc_t* g, int32_t M, int64_t Ns, int64_t ldz = -1, double* arr = (double*)8,
                     const gpmpc_env_desc_t* e = nullptr, int32_t m_or_H = 3, int64_t stride = 2) {
         const int64_t ld = ldz == -1 ? width(g, M) : ldz;
@@ -76,11 +78,17 @@ int main() {
         if (which == 3)
             return gpmpc_pathwise_rollout_vjp(g, e ? e : &ecar, arr, M, arr, Ns, m_or_H, arr, 1, arr, 1, arr, ld, arr, arr, nullptr, arr, arr,
                                               arr, arr ? ip : nullptr, nullptr);
+        if (which == 5)
+            return gpmpc_pathwise_rollout_cand(g, e ? e : &ecar, arr, M, arr, Ns, B, m_or_H, arr, 1, arr, arr, ld, arr, arr, nullptr,
+                                               arr ? ip : nullptr, nullptr);
+        if (which == 6)
+            return gpmpc_pathwise_rollout_cand_vjp(g, e ? e : &ecar, arr, M, arr, Ns, B, m_or_H, arr, 1, arr, arr, ld, arr, arr, nullptr, arr,
+                                                   arr, arr, arr ? ip : nullptr, nullptr);
         return stats(g, e ? e : &ecar, M, Ns, m_or_H, arr);
     };
-    const char* names[5] = {"gpmpc_pathwise_fit", "gpmpc_pathwise_eval", "gpmpc_pathwise_rollout", "gpmpc_pathwise_rollout_vjp",
-                            "gpmpc_pathwise_tube_stats"};
-    for (int which = 0; which < 5; ++which) {
+    const char* names[7] = {"gpmpc_pathwise_fit", "gpmpc_pathwise_eval", "gpmpc_pathwise_rollout", "gpmpc_pathwise_rollout_vjp",
+                            "gpmpc_pathwise_tube_stats", "gpmpc_pathwise_rollout_cand:", "gpmpc_pathwise_rollout_cand_vjp:"};
+    for (int which = 0; which < 7; ++which) {
         entry = names[which];
         expect("NULL gp", call(which, nullptr, 128, 4), GPMPC_E_ARG);
         expect("Ns < 0", call(which, &car, 128, -1), GPMPC_E_ARG);
@@ -117,7 +125,7 @@ int main() {
     gpmpc_gp_desc_t g4 = gp_desc(2, 4, 5, 10, 0);
     expect("D = 4, empty", call(1, &g4, 256, 0), GPMPC_OK);
     gpmpc_gp_desc_t g3 = gp_desc(3, 3, 4, 10, 0);
-    for (int which = 2; which < 5; ++which) {                          // the three entry points with an environment
+    for (int which = 2; which < 7; ++which) {                          // the five entry points with an environment
         entry = names[which];
         expect("H < 0", call(which, &car, 128, 4, -1, p, &ecar, INT32_MIN), GPMPC_E_ARG);
         expect("pendulum gp with the car's env", call(which, &pend, 128, 4, -1, p, &ecar), GPMPC_E_ARG);
@@ -128,6 +136,20 @@ int main() {
     entry = names[3];
     expect("gU NULL with H > 0", gpmpc_pathwise_rollout_vjp(&car, &ecar, p, 128, p, 4, 3, p, 1, p, 1, p, width(&car, 128), p, p, p, p, p,
                                                             nullptr, ip, nullptr), GPMPC_E_ARG);
+    for (int which = 5; which < 7; ++which) {                          // the candidate axis: B >= 0 and B * Ns < 2^31
+        entry = names[which];
+        const int64_t cases[][3] = {{-1, 4, GPMPC_E_ARG}, {INT64_MIN, 4, GPMPC_E_ARG}, {(int64_t)1 << 15, (int64_t)1 << 16, GPMPC_E_UNSUPPORTED},
+                                    {INT64_MAX, 2, GPMPC_E_UNSUPPORTED}, {INT64_MAX, INT_MAX, GPMPC_E_UNSUPPORTED},
+                                    {(int64_t)1 << 31, 1, GPMPC_E_UNSUPPORTED}, {INT64_MAX, 0, GPMPC_OK}, {0, INT_MAX, GPMPC_OK}, {0, 0, GPMPC_OK}};
+        for (const auto& c : cases) {
+            B = c[0];
+            expect("B and Ns", call(which, &car, 128, c[1], -1, c[2] == GPMPC_OK ? nullptr : p), (int)c[2]);
+        }
+        B = 3;
+    }
+    entry = names[6];
+    expect("gU NULL with H > 0", gpmpc_pathwise_rollout_cand_vjp(&car, &ecar, p, 128, p, 4, 3, 3, p, 1, p, p, width(&car, 128), p, p, p, p, p,
+                                                                 nullptr, ip, nullptr), GPMPC_E_ARG);
     entry = names[4];
     const double inf = __builtin_inf(), nan = __builtin_nan("");
     const double eps17[17] = {0.0}, eps_inf[1] = {inf}, eps_nan[1] = {nan}, eps_neg[1] = {-1.0};
