@@ -126,11 +126,40 @@ def _car_distinct(ag):
     ag["Dyn_gp_task_noises"]["val"] = [2.0, 5.0, 0.7]
 
 
+def _car_distinct_joint(ag):
+    """_car_distinct for the joint draw (tests/joint_variants.py): every index distinct, but with the rotated lengthscale rows at
+    their shipped size.  With the rows scaled by 0.35 the posterior covariance at the joint draws' scattered points lies where its
+    un-jittered Cholesky is a coin flip: the oracle alone, conditioning set reversed, passes it on 34 of 72 chains, changes its mind on
+    4 to 6 of them and moves its own samples by up to 6.5e-4 where both orders pass.  At the shipped size the attempt fails on every
+    chain in either order, as it does on the shipped car.  The outputscales move apart by (x 0.2, 0.4, 1.5) instead, which keeps the
+    case under the conditioning cap: cond = 3.63e6."""
+    ell = np.asarray(ag["Dyn_gp_lengthscale"]["both"], dtype=np.float64)            # (3, 1, 2)
+    ag["Dyn_gp_lengthscale"]["both"] = np.roll(ell, 1, axis=0).tolist()
+    ag["Dyn_gp_outputscale"]["both"] = [v * f for v, f in zip(ag["Dyn_gp_outputscale"]["both"], (0.2, 0.4, 1.5))]
+    ag["Dyn_gp_task_noises"]["val"] = [2.0, 5.0, 0.7]
+
+
+def _scale_os(f):
+    def apply(ag):
+        ag["Dyn_gp_outputscale"]["both"] = [v * f for v in ag["Dyn_gp_outputscale"]["both"]]
+    return apply
+
+
+def _pend_noise(ag):
+    """the pendulum ships task noises [3.8, 1.27, 3.8]: noise[2] == noise[0].  Only a draw that conditions on hallucinated gradient
+    labels reads noise[2] (tests/joint_variants.py; the rollouts' real data is value-only and mode I reads the first alone)."""
+    ag["Dyn_gp_task_noises"]["val"] = [3.8, 1.27, 0.6]
+
+
 HYPERS = {
     "shipped": lambda ag: None,
+    "pend_noise": _pend_noise,              # pendulum, joint draw
     "ell05": _scale_ell(0.5),               # pendulum
     "ell06": _scale_ell(0.6),               # car
+    "ell15": _scale_ell(1.5),               # pendulum, joint draw
     "distinct": _car_distinct,              # car
+    "distinct_joint": _car_distinct_joint,  # car, joint draw
+    "os025": _scale_os(0.25),               # car, joint draw: 49 and 63 real points under the conditioning cap at the shipped lengthscales
     # the u axis of the pendulum grid spans 10: il ((n1 - 1) h)^2 = 100 / ell_1^2 = 198.4 and 204.1, either side of the plan's
     # guard (200) on the equispaced-axis recurrence of mode I
     "guard_in": _pend_ell(1.84, 0.71),

@@ -11,6 +11,9 @@ from sampling_gpmpc_amd import _lib
 
 # (g_ny, T, N_r): the car (45 real points, value + two derivatives), the pendulum (36 real points), the car's value-only model
 CAR, PEND, CAR_T1 = (3, 3, 45), (1, 3, 36), (3, 1, 45)
+# (g_ny, T, N_r, real_has_grad): the boundaries of the real block - 64 / 65 observed real slots, value-only (n_r = N_r) and with gradient
+# labels (n_r = 3 N_r: 63 / 66)
+PEND_64, PEND_65, PEND_21G, PEND_22G = (1, 3, 64), (1, 3, 65), (1, 3, 21, True), (1, 3, 22, True)
 
 # (desc, Ns, n_h, n_ho, m, cache_rows (0: no caller cache), n_cached, pending, root_mode, eigh rank hint, knob, expected line)
 PLANS = [
@@ -115,6 +118,50 @@ PLANS = [
     # ... and the other four through the workspace's temporary cache
     (PEND, 4, 60, 180, 30, 0, 0, 0, 0, 0, '',
      'path=2 batches=1 | joint_kernel(FACTOR,nrow=180) joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # the boundaries of the real block (tests/joint_variants.py runs them on the device).  64 observed real slots: the matrix pipe, k = 0,
+    # 1, 2 of the pendulum 16 x 30 ...
+    (PEND_64, 16, 0, 0, 30, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_64, 16, 30, 90, 30, 256, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    (PEND_64, 16, 60, 180, 30, 384, 90, 3, 0, 0, '',
+     'path=2 batches=1 | joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # ... and a narrow test block with the matrix pipe pinned
+    (PEND_64, 16, 12, 36, 12, 256, 0, 2, 0, 0, 'pin=2',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # 65: no matrix-pipe kernel takes the real block - the VALU path at every k (90 rows cached at k = 2), also with the matrix pipe pinned
+    (PEND_65, 16, 0, 0, 30, 0, 0, 0, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=91) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_65, 16, 30, 90, 30, 256, 0, 2, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=181) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_65, 16, 60, 180, 30, 384, 90, 3, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=181) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_65, 16, 12, 36, 12, 256, 0, 2, 0, 0, 'pin=2',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=73) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # gradient labels on the real data: 21 points are 63 observed slots (the matrix pipe; k = 2 with pending rows off) ...
+    (PEND_21G, 16, 0, 0, 30, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_21G, 16, 30, 90, 30, 256, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    (PEND_21G, 16, 60, 180, 30, 384, 90, 0, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # ... 22 points are 66
+    (PEND_22G, 16, 0, 0, 30, 0, 0, 0, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=91) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_22G, 16, 30, 90, 30, 256, 0, 2, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=181) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_22G, 16, 60, 180, 30, 384, 90, 0, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=181) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    # the pair tables of joint_real_mfma_kernel (36 KB): 64 real points against m = 41 test points fit (36,128 B), k = 0 and 1 ...
+    (PEND_64, 3, 0, 0, 41, 0, 0, 0, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(TEST) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_64, 3, 41, 123, 41, 256, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_real_mfma(FACTOR) joint_chol_mfma(pend_use) joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
+    # ... against 42 they do not (37,320 B): the VALU head at k = 0, joint_test_mfma_kernel's factor mode at k = 1
+    (PEND_64, 3, 0, 0, 42, 0, 0, 0, 0, 0, '',
+     'path=1 batches=1 | joint_kernel(HEAD,nrow=127) joint_tail_mfma() | eigh=narrow+deferred pending_written=0'),
+    (PEND_64, 3, 42, 126, 42, 256, 0, 2, 0, 0, '',
+     'path=2 batches=1 | joint_test_mfma(FACTOR) joint_chol_mfma() joint_test_mfma(TEST,pend_write,Sv=cache) joint_tail_mfma(Sv=cache) | eigh=narrow+deferred pending_written=1'),
 ]
 
 
@@ -128,8 +175,8 @@ def _raw():
 @pytest.mark.parametrize("desc,Ns,n_h,n_ho,m,cache_rows,n_cached,pending,root_mode,rank,knob,expected", PLANS)
 def test_joint_plan(desc, Ns, n_h, n_ho, m, cache_rows, n_cached, pending, root_mode, rank, knob, expected):
     raw = _raw()
-    g_ny, T, N_r = desc
-    d = _lib.make_gp_desc(g_ny, 2, T, N_r, False, [[2.0, 1.1]] * g_ny, [0.05] * g_ny, [2e-7] * T, 1e-20)
+    g_ny, T, N_r, *has_grad = desc                              # (a fourth field: real_has_grad)
+    d = _lib.make_gp_desc(g_ny, 2, T, N_r, bool(has_grad and has_grad[0]), [[2.0, 1.1]] * g_ny, [0.05] * g_ny, [2e-7] * T, 1e-20)
     name, _, val = knob.partition("=")
     setters = {"pin": (raw.gpmpc_joint_pin_path, 0), "narrow": (raw.gpmpc_debug_eigh_narrow, -1),
                "real": (raw.gpmpc_debug_joint_real_kernel, -1)}
