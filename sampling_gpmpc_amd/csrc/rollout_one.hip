@@ -47,10 +47,16 @@
 //     both EXEC masks of every panel write, every lane pattern of the diagonal tiles' selects and the converter columns of
 //     the next entries are functions of t alone: section (vi) dispatches on t ONCE per step (bisection over the epoch's 3 - 6
 //     steps) into a block in which all of them are compile-time constants - masks are s_mov literals
-//     (rollout_one_gen.inc: OneRowMask; one_apply: one v_cndmask pair per value the step's pattern contains), converter
-//     writes take immediate offsets, no v_cmp / clamp / ballot remains.  n_h stays the run-time variable the shared part
+//     (rollout_one_gen.inc: OneRowMask; one_apply: one EXEC-masked v_mov_b64 in place per value the step's pattern contains),
+//     converter writes take immediate offsets, no v_cmp / clamp / ballot remains.  n_h stays the run-time variable the shared part
 //     (one_solve, the extraction) reads; GPMPC_ONE_DEBUG checks the invariant in every block.  The values written are the
 //     ones the run-time selects produced: results are bit-identical (profiles/one_append_steps.md).
+//
+//   * the inverse of group K's diagonal tiles (P.gd[K]) is not read before the NEXT step's forward substitution reaches the
+//     first tile row of group K: from epoch K = 3 on one_solve<K> computes it - the three MFMAs and six VALU instructions of
+//     inverse_tiles, same operands and order, in the wait states of tile rows 0 and 1 - and the append only selects ud / drow /
+//     dcol.  Inline it stays where nothing can hide it: in epoch 2, in the last step of an epoch and for the wrap block's
+//     group K + 1 (section (vi); profiles/one_inverse_in_solve.md).
 //
 // (A first version grouped FOUR TILE ROWS per MFMA with the solution tiles replicated in all blocks: 1.5x the MFMAs, three
 // times the masked writes; tools/experiments/rollout_one_superrow/.)
@@ -69,16 +75,21 @@ __device__ long long g_one_phase_cycles[16];
 __device__ double g_one_dbg[64 * 64];
 
 #ifdef GPMPC_PHASE_TIMERS
-#define OPH_DECL long long oph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long opht_ = __builtin_readcyclecounter()
+#define OPH_DECL long long oph_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; long long opht_ = __builtin_readcyclecounter()
 #define OPH(i) do { const long long n_ = __builtin_readcyclecounter(); oph_[i] += n_ - opht_; opht_ = n_; } while (0)
-#define OPH_STORE do { if (blockIdx.x == 0 && threadIdx.x == 0) for (int i_ = 0; i_ < 8; ++i_) g_one_phase_cycles[i_] = oph_[i_]; } while (0)
+// (timers only - the ISA marks of tools/one_phase_mix.py stay eight) slot 8 -> [10]: the append's selects and the blocks' ends,
+// split off "append: diagonal tiles" ([6]), which is then the inline tile inverse and its write alone
+#define OPH_T(i) OPH(i)
+#define OPH_STORE do { if (blockIdx.x == 0 && threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) g_one_phase_cycles[i_] = oph_[i_]; g_one_phase_cycles[10] = oph_[8]; } } while (0)
 #elif defined(GPMPC_ONE_PHASE_MARKS)                              // tools/one_phase_mix.py: the phases' ends as comments in the ISA
 #define OPH_DECL
 #define OPH(i) asm volatile("; one_phase_end " #i)
+#define OPH_T(i)
 #define OPH_STORE
 #else
 #define OPH_DECL
 #define OPH(i)
+#define OPH_T(i)
 #define OPH_STORE
 #endif
 #ifdef GPMPC_ONE_PHASE_MARKS
@@ -232,28 +243,74 @@ __device__ __forceinline__ void one_axis9(double& P0, double& P1, double R0, dou
 }
 // ---- the append's selects by PATTERN: in step t the factor has n_h = 3 t rows, so which lane of a register receives which of
 // the step's values is known when the step's block is compiled.  A pattern maps a lane (kq, bm, jq) to the id of the value it
-// receives (OV_KEEP: none); one_apply turns it into one select under a CONSTANT lane mask per value the pattern contains
-// (s_mov of the mask + v_cndmask: no compare, no index clamp).
+// receives (OV_KEEP: none); one_apply turns it into one move under a CONSTANT lane mask per value the pattern contains
+// (s_mov of the mask into EXEC + v_mov_b64: no compare, no index clamp).
 enum OneVal { OV_KEEP = 0, OV_C00, OV_C10, OV_C11, OV_C20, OV_C21, OV_C22, OV_CI0, OV_CI1, OV_CI2, OV_OLD, OV_COUNT, OV_ZERO = OV_KEEP };
-// lanes of M: a, the others b
-template <unsigned long long M>
-__device__ __forceinline__ double one_sel(double a, double b) {
-    return __builtin_amdgcn_inverse_ballot_w64(M) ? a : b;
+// the values a pattern contains, ascending: how many, the k-th one's id and lanes
+template <class Pat>
+struct OnePatIds {
+    static constexpr unsigned long long mask(int id) {
+        unsigned long long m = 0;
+        for (int l = 0; l < 64; ++l)
+            if (Pat::at(l >> 4, (l >> 2) & 3, l & 3) == id) m |= 1ull << l;
+        return m;
+    }
+    static constexpr int count() {
+        int n = 0;
+        for (int id = 1; id < OV_COUNT; ++id) n += mask(id) != 0;
+        return n;
+    }
+    static constexpr int nth(int k) {
+        for (int id = 1; id < OV_COUNT; ++id)
+            if (mask(id) != 0 && k-- == 0) return id;
+        return 0;
+    }
+};
+// x := v_i in the lanes M_i, IN PLACE: one EXEC-masked v_mov_b64 per value on the tied 64-bit operand (EXEC is all ones where
+// the append stands and is restored to -1).  As `lanes ? v : x` hipcc builds every selected double from two 32-bit v_cndmask
+// chains and moves the pair into the loop-carried register behind the step's block: two VALU instructions per value and nine
+// v_mov_b64 per step for the six doubles of the diagonal tiles' state.
+#define ONE_LN_I(i) "s_mov_b32 exec_lo, %[l" #i "]\n\ts_mov_b32 exec_hi, %[h" #i "]\n\tv_mov_b64 %[x], %[v" #i "]\n\t"
+#define ONE_LN_O(i) [v##i] "v"(v##i), [l##i] "n"((int)(unsigned)(M##i & 0xffffffffull)), [h##i] "n"((int)(unsigned)(M##i >> 32))
+template <unsigned long long M0>
+__device__ __forceinline__ void one_lanes(double& x, double v0) {
+    asm(ONE_LN_I(0) "s_mov_b64 exec, -1" : [x] "+v"(x) : ONE_LN_O(0));
 }
-template <class Pat, int ID>
-constexpr unsigned long long one_pat_mask() {
-    unsigned long long m = 0;
-    for (int l = 0; l < 64; ++l)
-        if (Pat::at(l >> 4, (l >> 2) & 3, l & 3) == ID) m |= 1ull << l;
-    return m;
+template <unsigned long long M0, unsigned long long M1>
+__device__ __forceinline__ void one_lanes(double& x, double v0, double v1) {
+    asm(ONE_LN_I(0) ONE_LN_I(1) "s_mov_b64 exec, -1" : [x] "+v"(x) : ONE_LN_O(0), ONE_LN_O(1));
+}
+template <unsigned long long M0, unsigned long long M1, unsigned long long M2>
+__device__ __forceinline__ void one_lanes(double& x, double v0, double v1, double v2) {
+    asm(ONE_LN_I(0) ONE_LN_I(1) ONE_LN_I(2) "s_mov_b64 exec, -1" : [x] "+v"(x) : ONE_LN_O(0), ONE_LN_O(1), ONE_LN_O(2));
+}
+template <unsigned long long M0, unsigned long long M1, unsigned long long M2, unsigned long long M3>
+__device__ __forceinline__ void one_lanes(double& x, double v0, double v1, double v2, double v3) {
+    asm(ONE_LN_I(0) ONE_LN_I(1) ONE_LN_I(2) ONE_LN_I(3) "s_mov_b64 exec, -1" : [x] "+v"(x) : ONE_LN_O(0), ONE_LN_O(1), ONE_LN_O(2), ONE_LN_O(3));
+}
+#undef ONE_LN_I
+#undef ONE_LN_O
+template <class Pat, int B = 0>
+__device__ __forceinline__ void one_apply_from(double& x, const double (&val)[OV_COUNT]) {
+    using I = OnePatIds<Pat>;
+    constexpr int N = I::count() - B;
+    // (constexpr locals: an id or a mask computed in an ordinary expression would be a run-time loop over the lanes)
+    constexpr int i0 = I::nth(B), i1 = I::nth(B + 1), i2 = I::nth(B + 2), i3 = I::nth(B + 3);
+    constexpr unsigned long long m0 = I::mask(i0), m1 = I::mask(i1), m2 = I::mask(i2), m3 = I::mask(i3);
+    if constexpr (N >= 4) {
+        one_lanes<m0, m1, m2, m3>(x, val[i0], val[i1], val[i2], val[i3]);
+        one_apply_from<Pat, B + 4>(x, val);
+    } else if constexpr (N == 3) {
+        one_lanes<m0, m1, m2>(x, val[i0], val[i1], val[i2]);
+    } else if constexpr (N == 2) {
+        one_lanes<m0, m1>(x, val[i0], val[i1]);
+    } else if constexpr (N == 1) {
+        one_lanes<m0>(x, val[i0]);
+    }
 }
 template <class Pat>
 __device__ __forceinline__ double one_apply(double x, const double (&val)[OV_COUNT]) {
-    one_for<1, OV_COUNT>([&](auto ic) {
-        constexpr int ID = decltype(ic)::value;
-        constexpr unsigned long long M = one_pat_mask<Pat, ID>();
-        if constexpr (M != 0) x = one_sel<M>(val[ID], x);
-    });
+    one_apply_from<Pat>(x, val);
     return x;
 }
 // A new row (index ri = 0 .. 2 counted from the first new row) against column rk (same origin): old columns (rk < 0) carry v of
@@ -625,7 +682,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         // ---- forward substitution, left-looking over tile rows: ONE hand-scheduled statement (tools/gen_rollout_one.py:
         // solve_stmt) - row r + 1's independent MFMAs stand in the wait states of row r, absent rows are left inside it -----
         double S0, S1;                                            // the Gram product's two accumulators (it rides in the last row's wait states)
-        one_solve<K>(P, Vu, RN, MK, n_h, S0, S1);
+        // (K >= kOneSolveInvK: the statement also inverts group K's diagonal tiles from ud / drow / dcol - what the previous
+        // step's append left - and writes P.gd[K], in the wait states of tile rows 0 and 1; see section (vi))
+        one_solve<K>(P, Vu, RN, MK, n_h, S0, S1, ud, drow, dcol, Inat);
         ODBG(0, Vu[0]);
         ODBG(1, Vu[1]);
         ODBG(2, Vu[2]);
@@ -776,6 +835,14 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 const double Pq = one_mfma_zero(Inat + Mt, Inat + M2);        // (I + M)(I + M^2)
                 return Pq * dcl;
             };
+            // WHERE the inverse runs.  P.gd[K] is not read before the next step's forward substitution reaches the first tile
+            // row of group K, behind the rows of the groups in front: from epoch 3 on one_solve<K> computes it there (same
+            // operations, operands and order - the same bits), for the price of its issue slots, and the append only selects.
+            // Inline it stays where nothing can hide it: in epoch 2 (group 2's rows are the statement's first), in the epoch's
+            // last step (the next step belongs to the statement of group K + 1, which reads gd[K] as it is) and for the wrap
+            // block's group K + 1.  Every exit of the step loop leaves P.gd[K] either final (inline) or recomputed by the
+            // statement that reads it next; the last step of a launch appends nothing.
+            constexpr bool INV_IN_SOLVE = K >= kOneSolveInvK;
             constexpr int TB = OneEpoch<K>::t_begin, TE = OneEpoch<K>::t_end < kOneAppendSteps ? OneEpoch<K>::t_end : kOneAppendSteps;
             one_pick_row<TB, TE>(t, [&](auto tc) {
                 constexpr int TT = decltype(tc)::value, NH = T * TT;
@@ -817,10 +884,14 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                     const double G1 = inverse_tiles(ud1, drow1, dcol1);
                     one_hset_gd<K + 1>(G1);                       // (hidden write under the dispatch, see above)
                 }
+                if constexpr (INV_IN_SOLVE && TT == OneEpoch<K>::t_end - 1) one_hset_gd<K>(inverse_tiles(ud, drow, dcol));
             });
             one_for<(R0 > 0 ? R0 : 0), (R0 + 5 < kOneNTR ? R0 + 5 : kOneNTR)>([&](auto rc) { one_touch_row<decltype(rc)::value>(P); });
             if constexpr (K < KLAST) one_touch_gd<K + 1>(P);
-            {
+            OPH_T(8);
+            if constexpr (INV_IN_SOLVE) {
+                one_touch_gd<K>(P);                               // (the last step's block may have written it)
+            } else {
                 const double Gt = inverse_tiles(ud, drow, dcol);
                 ODBG(8, ud);
                 ODBG(9, Gt);
@@ -841,7 +912,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     one_for<KFIRST, KLAST + 1>([&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
 #pragma unroll 1
-        while (t < H && ((NKT + (n_h >> 2)) >> 2) == K) step(Kc);
+        while (t < H && t < OneEpoch<K>::t_end) step(Kc);           // (n_h == 3 t: ((NKT + (n_h >> 2)) >> 2) == K as one compare)
         ud = ud1, drow = drow1, dcol = dcol1;                     // the next group becomes the current one
         ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
     });

@@ -18,9 +18,12 @@ for (ns, h) in CASES:
         # sample - the writes stand inside the step's append block; the next step's exponential runs inside "sample", in the
         # levels of pivots 2 and 3)
         names = ["entries: lds reads", "entries: vr+writes", "solve", "gram+1st extract", "sample+next exp", "append sets", "append diag", "state"]
-        tot = sum(out[:8])
+        # ([10]: the append's selects and the blocks' ends, split off "append diag" by a mark of the timers' build - what is left
+        # there is the inline tile inverse, its write and the copies behind the dispatch)
+        names.append("append selects"); vals = list(out[:8]) + [out[10]]
+        tot = sum(vals)
         print("   total cycles", tot, "per step", tot // h)
-        for n, v in zip(names, out[:8]): print(f"   {n:18s} {v:9d} {v // h:7d}/step {100.0 * v / max(tot, 1):5.1f}%%")
+        for n, v in zip(names, vals): print(f"   {n:18s} {v:9d} {v // h:7d}/step {100.0 * v / max(tot, 1):5.1f}%%")
         print(f"   prologue (kernel entry -> step loop) {out[8]} cycles, whole kernel of wave 0 {out[9]} cycles (the step loop {tot})")
 '''
 cases = [(1024, 30), (1024, 15), (2048, 30), (256, 30)]

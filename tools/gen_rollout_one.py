@@ -101,8 +101,30 @@ SOLVE_VU, SOLVE_T, SOLVE_T2, SOLVE_W, SOLVE_X, SOLVE_RNM, SOLVE_G = 216, 232, 23
 SOLVE_CLOBBER = list(range(232, 248))
 
 
+# The inverse of group K's diagonal tiles rides in the statement of every epoch K >= SOLVE_INV_KMIN (group 2's rows are the
+# statement's first rows: nothing stands in front of them to hide it behind).
+SOLVE_INV_KMIN = 3
+
+
 def vp(n):
     return f"v[{n}:{n + 1}]"
+
+
+def inverse_ops(m, K):
+    """The diagonal tiles of group K, inverted inside one_solve<K>: U^-1 = (I + M)(I + M^2) D^-1 with U = D (I - M) - the
+    operations, operands and order of rollout_one.hip's inverse_tiles (the same bits), as the stages solve_stmt places in the
+    wait states of tile rows 0 and 1.  Temporaries: RNm's register (a clobber of the statement) and the two Gram accumulators
+    (early-clobber outputs, free until the step's last tile row).  %[ud] / %[dr] / %[dc] / %[inat]: the kernel's loop-carried
+    L^T of the lane's tile, 1 / diag along its rows / columns, the identity in the natural map."""
+    X, Y, Z = SOLVE_RNM, SOLVE_G, SOLVE_G + 2
+    n = m.reg("gd", K, 0)
+    return {"m": [f"v_fma_f64 {vp(X)}, -%[dr], %[ud], %[inat]"],                       # M = I - drow ud
+            "f1": [f"{MF} {vp(Y)}, {vp(X)}, %[inat], 0"],                             # M^T
+            "f2": [f"{MF} {vp(Z)}, {vp(Y)}, {vp(X)}, 0"],                              # M M
+            "add": [f"v_add_f64 {vp(Y)}, %[inat], {vp(Y)}", f"v_add_f64 {vp(Z)}, %[inat], {vp(Z)}"],
+            "f3": [f"{MF} {vp(X)}, {vp(Y)}, {vp(Z)}, 0"],                              # (I + M)(I + M^2)
+            "put": [f"v_mul_f64 {vp(X)}, %[dc], {vp(X)}",
+                    f"v_accvgpr_write_b32 a{n}, v{X}", f"v_accvgpr_write_b32 a{n + 1}, v{X + 1}"]}
 
 
 def solve_stmt(f, m, K, member):
@@ -126,7 +148,9 @@ def solve_stmt(f, m, K, member):
     VU = lambda g: SOLVE_VU + 2 * g
     T, T2, W = SOLVE_T, SOLVE_T2, SOLVE_W
     accs = lambda r: (SOLVE_X + 4 * (r & 1), SOLVE_X + 4 * (r & 1) + 2)
-    NOUT = K + 1 + 2                                    # Vu[0 .. K], S0, S1
+    INV = K >= SOLVE_INV_KMIN and "noinv" not in VARIANT
+    inv = inverse_ops(m, K) if INV else {}
+    NOUT = K + 1 + 2 + (1 if INV else 0)                # Vu[0 .. K], S0, S1, (gd[K])
     rn_op = lambda g: f"%{NOUT + (g - m.gd[0])}"
     nh_op = f"%{NOUT + (K - m.gd[0] + 1)}"
     mk_op = lambda b: f"%{NOUT + (K - m.gd[0] + 1) + 1 + b}"      # 1.0 in the lanes of block b, 0.0 elsewhere
@@ -142,6 +166,7 @@ def solve_stmt(f, m, K, member):
     # added on the chain.  Measured (tools/ubench/one_solve_chain.hip, 22 rows): -3 cycles per row alone, +6 together with the
     # post-merge MFMA below - not shipped.
     FOLD = "rnfold" in VARIANT
+    assert not (FOLD and INV), "RNm's register holds the inverse's M"
 
     def ra_list(r):
         # (accumulator, A panel, B register, start value: None = accumulate)
@@ -184,9 +209,26 @@ def solve_stmt(f, m, K, member):
         post = q.pop() if (len(q) >= 3 and "nopost" not in VARIANT) else None
         keep = 1                                        # (one stays for behind the diagonal MFMA)
 
+        # The inverse of group K's tiles, spread over the wait states of rows 0 and 1 (always present for K >= 3, their slots
+        # are s_nop otherwise: the next row has two independent MFMAs).  Distances (tools/check_dpp_hazard.py, the strict
+        # count): M -> f1 4 states, f1 -> f2 9, f2 -> the adds 8, the adds -> f3 3, f3 -> the product 8; the pair of writes
+        # stands a whole tile row in front of the first MFMA that reads gd[K] (row 4 K - NKT >= 3).
+        stage = {}
+        if INV and r == 0:
+            stage = {1: inv["m"], 2: inv["f1"], "c": inv["f2"]}
+        elif INV and r == 1:
+            stage = {1: inv["add"], 2: inv["f3"], "c": inv["put"]}
+        assert not stage or (not last and len(q) <= 2)
+        nslot = [0]
+
         def slot(pad):
             """an MFMA of the next row where a wait would stand (it counts as one state for a VALU -> DPP / MFMA read)"""
-            if len(q) > keep and "noslots" not in VARIANT:
+            nslot[0] += 1
+            if nslot[0] in stage:                       # a stage of the inverse: every instruction is one state
+                L.extend(stage[nslot[0]])
+                if len(stage[nslot[0]]) <= pad:
+                    L.append(f"s_nop {pad - len(stage[nslot[0]])}")
+            elif len(q) > keep and "noslots" not in VARIANT:
                 emit_ra(q.pop(0))
                 L.append("s_nop 0")
             else:
@@ -220,6 +262,14 @@ def solve_stmt(f, m, K, member):
                 emit_ra(q.pop(0))
                 if q and "nomfmanop" not in VARIANT:
                     L.append("s_nop 1")
+            if "c" in stage:                            # behind an independent MFMA: nothing is left to pad for the merge
+                if stage["c"][0].startswith(MF):
+                    L.append("s_nop 1")
+                L.extend(stage["c"])
+        elif "c" in stage:
+            L.extend(stage["c"])
+            if not stage["c"][0].startswith(MF):
+                L.append(f"s_nop {5 - len(stage['c'])}")
         else:
             L.append("s_nop 5")
         L.append(f"v_mov_b32_dpp v{VU(g)}, v{W} quad_perm:[0,1,2,3] row_mask:0xf bank_mask:0x{1 << b:x}")
@@ -276,17 +326,24 @@ def solve_stmt(f, m, K, member):
     if GRAM:
         L.append("s_nop 5")                             # S0 / S1 are read by the compiler's code next
     seen, ins = set(), []
+    if INV:
+        seen.add(m.reg("gd", K, 0))                     # written here: an output
     for n, mem in used:
         if n not in seen:
             seen.add(n)
             ins.append(f'"{{a[{n}:{n + 1}]}}"({mem})')
     outs = ", ".join(f'"+{{v[{VU(g)}:{VU(g) + 1}]}}"(Vu[{g}])' for g in range(K + 1))
     outs += f', "=&{{v[{SOLVE_G}:{SOLVE_G + 1}]}}"(S0), "=&{{v[{SOLVE_G + 2}:{SOLVE_G + 3}]}}"(S1)'
+    if INV:
+        n = m.reg("gd", K, 0)
+        outs += f', "+{{a[{n}:{n + 1}]}}"(P.gd[{K}])'
     rn = ", ".join(f'"v"(RN[{g}])' for g in range(m.gd[0], K + 1))
     mk = ", ".join(f'"v"(MK[{b}])' for b in range(4))
+    if INV:
+        mk += ', [ud] "v"(ud), [dr] "v"(drow), [dc] "v"(dcol), [inat] "v"(inat)'
     clob = ", ".join(f'"v{n}"' for n in SOLVE_CLOBBER) + ', "scc"'
     body = "\n        ".join(f'"{x}\\n\\t"' for x in L[:-1]) + f'\n        "{L[-1]}"'
-    f.write(f"__device__ __forceinline__ void one_solve_{K}(OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1) {{\n")
+    f.write(f"__device__ __forceinline__ void one_solve_{K}(OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1, double ud, double drow, double dcol, double inat) {{\n")
     f.write(f"    asm volatile({body}\n        : {outs}\n        : {rn}, \"s\"(nh), {mk},\n          {', '.join(ins)}\n        : {clob});\n}}\n")
 
 
@@ -409,6 +466,7 @@ def emit(f):
     f.write(f"// ---- NKT = {NKT}, {NTR} tile rows: {m.count} panels in a[0:{2 * m.count - 1}] ----------------------------------------------------\n")
     f.write(f"struct OnePanels {{\n    double p[{m.count - len(m.gd)}];\n    double gd[{max(m.gd) + 1}];\n}};\n")
     f.write(f"constexpr int kOneNKT = {NKT}, kOneNTR = {NTR};\n")
+    f.write(f"constexpr int kOneSolveInvK = {SOLVE_INV_KMIN};      // one_solve<K> inverts group K's diagonal tiles for K >= this\n")
     member = lambda r, g: f"P.p[{m.idx[('p', r, g)]}]"
     for r in range(NTR):
         gs = m.groups[r]
@@ -471,7 +529,7 @@ def emit(f):
     disp("one_set_row", "void", "OnePanels& P, unsigned long long mBase, unsigned long long mLast, const double* V", "P, mBase, mLast, V", range(NTR))
     for K in m.gd:
         solve_stmt(f, m, K, member)
-    disp("one_solve", "void", "OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1", "P, Vu, RN, MK, nh, S0, S1", m.gd)
+    disp("one_solve", "void", "OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1, double ud, double drow, double dcol, double inat", "P, Vu, RN, MK, nh, S0, S1, ud, drow, dcol, inat", m.gd)
     disp("one_hset_row", "void", "unsigned long long mBase, unsigned long long mLast, const double* V", "mBase, mLast, V", range(NTR))
     disp("one_gdm", "double", "OnePanels& P, double acc", "P, acc", m.gd)
     disp("one_put_gd", "void", "OnePanels& P, double v", "P, v", m.gd)
