@@ -15,6 +15,9 @@
 // derivative labels), the triangle is zero-padded and the columns beyond n_r are skipped (a wave-uniform branch).
 // Work per candidate-step: g_ny (n_r (n_r + 1) / 2 + NRP - n_r rows of padding per column + ~12 N_r) FMA + g_ny N_r exp, then
 // ~2 NX^3 for A P A^T; memory: (NX + NX^2 [+ g_ny + NX^2]) doubles written, NU read.
+// The launch and the argument checks are the family's (mom_launch, mom_check_args, moments_step.hpp).  A P A^T and the tube store
+// stay written out here: with them as shared helpers this kernel's step loop compiled differently and was 0.3 - 0.5 % slower than
+// before in two separate measurements (profiles/lane_frame_ab.md).
 #include "moments_step.hpp"
 
 #include <cmath>
@@ -90,6 +93,7 @@ __global__ __launch_bounds__(64) void moment_rollout_kernel(const MomentArgs a) 
 #pragma unroll
         for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
 
+        // written out in each forward, not a shared mom_gp_outputs: in moment_rollout_kernel the helper cost the car 6 VGPRs (profiles/lane_frame_isa.md)
         double gm[G_NY], gs[G_NY], gd[G_NY][2];                        // posterior mean, variance, d mean / d xi per output
 #pragma unroll 1
         for (int o = 0; o < G_NY; ++o) {
@@ -167,14 +171,6 @@ __global__ __launch_bounds__(64) void moment_rollout_kernel(const MomentArgs a) 
     if (active) a.info[b] = info_acc;
 }
 
-template <int ENV, int NRP, bool HG>
-static int moment_launch(const MomentArgs& a, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.B + 63) / 64);
-    hipLaunchKernelGGL((moment_rollout_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
-}
-
 }  // namespace gpmpc
 
 using namespace gpmpc;
@@ -184,7 +180,7 @@ extern "C" {
 int gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r, int64_t B,
                          int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                          const double* P0, double* M, double* P, double* S, double* A, int32_t* info, void* stream) {
-    if (int rc = mom_check_args("gpmpc_moment_rollout: ", gp, env, plan, X_r, B, H, x0, U, M, P, info, false, nullptr)) return rc;
+    if (int rc = mom_check_args("gpmpc_moment_rollout: ", gp, env, plan, X_r, B, H, x0, U, "M, P", {M, P}, info, false, nullptr)) return rc;
     if (B == 0) return GPMPC_OK;
     MomentArgs a;
     mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
@@ -195,7 +191,7 @@ int gpmpc_moment_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env,
     a.A = A;
     a.info = (int*)info;
     return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
-        return moment_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+        return mom_launch(moment_rollout_kernel<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>, a, stream);
     });
 }
 

@@ -17,7 +17,10 @@
 //   xibar = sum_o (mbar_o grad m_o + Hess m_o gbar_o + sbar_o grad s_o) scattered through d xi / d x and the feedback gain,
 //   lambda_t = xbar + gM[:, t],  Lambda_t = Pbar + sym(gP[:, t]).
 // Gradients are per candidate (no cross-lane reduction, no atomics).  The step body is a __host__ __device__ function so that the
-// same arithmetic can be compiled for the host and compared with autograd without a GPU.
+// same arithmetic can be compiled for the host and compared with autograd without a GPU.  The launch and the argument checks are the
+// family's (mom_launch, mom_check_args, moments_step.hpp).  The lower-triangle code of the sweep stays written out here: with the
+// shared helpers of the robust VJP (sym_at, sym_load, sym_cotangent, ...) the pendulum's launch was 1 us slower than before in two
+// separate measurements (profiles/lane_frame_ab.md), and the tables as one MomTables argument change the instruction streams.
 #include "moments_step.hpp"
 
 #include <cmath>
@@ -76,6 +79,7 @@ __host__ __device__ __forceinline__ void mgv_candidate(const MomentGradArgs& a, 
         for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
 
         // ---- the GP at xi: mean, gradient, Hessian, variance and its gradient per output ----------------------------------------
+        // written out in both VJPs, not a shared mom_gp_grad_outputs: as a helper it costs the car 4 - 20 VGPRs (profiles/lane_frame_isa.md)
         double gm[G_NY], gs[G_NY], gd[G_NY][2], gh[G_NY][3], ge[G_NY][2];   // gh: H00, H01, H11; ge: d s / d xi (0 where clamped)
 #pragma unroll 1
         for (int o = 0; o < G_NY; ++o) {
@@ -204,14 +208,6 @@ __global__ __launch_bounds__(64) void moment_rollout_vjp_kernel(const MomentGrad
     mgv_candidate<ENV, NRP, HG>(a, Ltri, alpha_s, xr_s, active ? braw : a.B - 1, active);
 }
 
-template <int ENV, int NRP, bool HG>
-static int mgv_launch(const MomentGradArgs& a, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.B + 63) / 64);
-    hipLaunchKernelGGL((moment_rollout_vjp_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
-}
-
 }  // namespace gpmpc
 
 using namespace gpmpc;
@@ -222,7 +218,7 @@ int gpmpc_moment_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
                              int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                              const double* M, const double* P, const double* gM, const double* gP, double* gx0, double* gU,
                              double* gP0, int32_t* info, void* stream) {
-    if (int rc = mom_check_args("gpmpc_moment_rollout_vjp: ", gp, env, plan, X_r, B, H, x0, U, M, P, info, true, gU)) return rc;
+    if (int rc = mom_check_args("gpmpc_moment_rollout_vjp: ", gp, env, plan, X_r, B, H, x0, U, "M, P", {M, P}, info, true, gU)) return rc;
     if (B == 0) return GPMPC_OK;
     MomentGradArgs a;
     mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
@@ -235,7 +231,7 @@ int gpmpc_moment_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
     a.gP0 = gP0;
     a.info = (int*)info;
     return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
-        return mgv_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+        return mom_launch(moment_rollout_vjp_kernel<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>, a, stream);
     });
 }
 

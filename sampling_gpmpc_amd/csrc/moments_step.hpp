@@ -3,10 +3,20 @@
 // variance, clamp decision and A_t are the forward's because both kernels call the functions below; so are the packed-triangle
 // layout, the staging, the instantiation set and the argument checks.  pathwise_rollout_kernel (pathwise.hip) takes the environment
 // facts and env_step_ct from here.  Everything is __host__ __device__ (the VJP's candidate body compiles for the host) or constexpr.
+//
+// It also serves every lane-per-candidate kernel - the moment pair, the robust pair (robust_tube.hip, robust_tube_grad.hip, with
+// robust_step.hpp) and the optimistic pair (optimistic.hip) - with the one launcher (mom_launch), the one argument check
+// (mom_check_args); the robust VJP also takes the staged tables as one value (MomTables), and the robust pair the small symmetric matrices kept as
+// lower triangles in registers (sym_at, sym_congruence, the tube's load, the cotangent's read and final write; the moment and the
+// optimistic kernels keep theirs written out, measured slower with the helpers).  The staging prologue (the three __shared__ tables,
+// mom_stage, the lane's candidate) stays written out in each kernel: inside a helper the compiler forms the staging loop's addresses
+// differently and every launch was 0.5 - 2 us slower (profiles/lane_frame_ab.md).
 #pragma once
 #include "gpmpc_host.hpp"
 
 #include <climits>
+#include <cmath>
+#include <initializer_list>
 #include <type_traits>
 
 namespace gpmpc {
@@ -171,6 +181,12 @@ __host__ __device__ __forceinline__ void mom_stage(const MomentStepArgs& a, doub
     for (int e = tid; e < 2 * NRP; e += nt) xr_s[e] = (e < 2 * gp.N_r) ? a.X_r[e] : 0.0;
 }
 
+struct MomTables {                         // the staged tables (LDS on the device): packed triangles, alpha, X_r
+    const double *Ltri, *alpha, *xr;
+};
+
+constexpr double MOM_NAN = __builtin_nan("");
+
 // ---------------------------------------------------------------------------------------------------------------
 // the GP of one output at xi
 // ---------------------------------------------------------------------------------------------------------------
@@ -246,6 +262,72 @@ __host__ __device__ __forceinline__ bool mom_variance(const GpParams& gp, double
         info_acc |= GPMPC_INFO_VAR_CLAMPED;
     }
     return clamped;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// symmetric NX x NX matrices held as their lower triangle [i][j], j <= i (P_t, Q_t and their cotangents); every index is a compile-
+// time constant once the loops are unrolled, and each entry is one fma chain in a fixed order
+// ---------------------------------------------------------------------------------------------------------------
+template <int NX>
+__host__ __device__ __forceinline__ double sym_at(const double (&S)[NX][NX], int i, int j) {
+    return (j <= i) ? S[i][j] : S[j][i];
+}
+
+// AS = A S (full) and the lower triangle of out = A S A^T (every chain starts from zero)
+template <int NX>
+__host__ __device__ __forceinline__ void sym_congruence(const double (&A)[NX][NX], const double (&S)[NX][NX], double (&AS)[NX][NX],
+                                                        double (&out)[NX][NX]) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int c = 0; c < NX; ++c) {
+            double s_ = 0.0;
+#pragma unroll
+            for (int kk = 0; kk < NX; ++kk) s_ = fma(A[i][kk], sym_at<NX>(S, kk, c), s_);
+            AS[i][c] = s_;
+        }
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s_ = 0.0;
+#pragma unroll
+            for (int kk = 0; kk < NX; ++kk) s_ = fma(AS[i][kk], A[j][kk], s_);
+            out[i][j] = s_;
+        }
+}
+
+// a tube's matrix (row-major, NX * NX doubles at p): the lower triangle read (chk += |entry|)
+template <int NX>
+__host__ __device__ __forceinline__ void sym_load(const double* p, double (&S)[NX][NX], double& chk) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            S[i][j] = p[i * NX + j];
+            chk += fabs(S[i][j]);
+        }
+}
+
+// entry (i, j) of the symmetrised cotangent 0.5 (g + g^T) of a tube's matrix; g == NULL: zero
+template <int NX>
+__host__ __device__ __forceinline__ double sym_cotangent(const double* g, int i, int j) {
+    return g ? 0.5 * (g[i * NX + j] + g[j * NX + i]) : 0.0;
+}
+
+// The gradient with respect to the initial matrix, whose lower triangle the forward reads: both mirrored copies of an off-diagonal
+// entry count for the lower one, the upper triangle gets zero; a dead candidate's triangle is NaN.
+template <int NX>
+__host__ __device__ __forceinline__ void sym_store_grad0(double* p, const double (&Lam)[NX][NX], bool dead) {
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+#pragma unroll
+        for (int j = 0; j < NX; ++j) p[i * NX + j] = (j > i) ? 0.0 : dead ? MOM_NAN : (j == i) ? Lam[i][i] : 2.0 * Lam[i][j];
+}
+
+// a dead candidate's per-step gradients (written step by step during the sweep) are NaN throughout
+__host__ __device__ __forceinline__ void mom_fill_nan(double* p, int n) {
+    for (int e = 0; e < n; ++e) p[e] = MOM_NAN;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -356,7 +438,7 @@ __host__ __device__ __forceinline__ void mom_step_tail(const EnvParams& e, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host: the instantiation set, the argument block and the argument checks of the two entry points
+// host: the instantiation set, the launch, the argument block and the argument checks of the entry points
 // ---------------------------------------------------------------------------------------------------------------
 // launch(env, nrp, hg) with integral constants: n_r rounded up to a multiple of 8 (16 with derivative labels)
 template <class Launch>
@@ -383,18 +465,31 @@ int mom_dispatch(int env_id, int n, bool real_has_grad, Launch&& launch) {
     return rows(std::integral_constant<int, GPMPC_ENV_CAR_RESIDUAL>{});
 }
 
-// The checks of gpmpc_moment_rollout and gpmpc_moment_rollout_vjp; `me` names the entry point in the message.  M and P are the
-// forward's outputs and the VJP's inputs; the VJP (need_gU) also requires gU when there are steps.
+// The one launch of the family: one 64-lane workgroup per 64 candidates
+template <class Args>
+int mom_launch(void (*kernel)(Args), const Args& a, void* stream) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+    GPMPC_HIP_CHECK(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// The checks of the six entry points; `me` names the entry point in the message.  tubes: the entry point's required tube arrays (the
+// forward's outputs, the VJP's inputs) and tube_names their names in the message; a VJP (need_gU) also requires gU when there are
+// steps; beta: NULL where the entry point has none or does not check it.
 inline int mom_check_args(const std::string& me, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan,
-                          const double* X_r, int64_t B, int32_t H, const double* x0, const double* U, const double* M, const double* P,
-                          const int32_t* info, bool need_gU, const double* gU) {
+                          const double* X_r, int64_t B, int32_t H, const double* x0, const double* U, const char* tube_names,
+                          std::initializer_list<const void*> tubes, const int32_t* info, bool need_gU, const double* gU,
+                          const double* beta = nullptr) {
     if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
     if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
     if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
     if (B < 0 || H < 0) return fail(GPMPC_E_ARG, me + "B and H must be >= 0");
+    if (beta && (!(*beta >= 0.0) || !std::isfinite(*beta))) return fail(GPMPC_E_ARG, me + "beta must be finite and >= 0");
+    bool missing = !plan || !X_r || !x0 || !info || (H > 0 && (!U || (need_gU && !gU)));
+    for (const void* t : tubes) missing = missing || !t;
     // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
-    if (B > 0 && (!plan || !X_r || !x0 || !M || !P || !info || (H > 0 && (!U || (need_gU && !gU)))))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, x0, U, M, P" + (need_gU ? ", gU" : "") + " and info are required)");
+    if (B > 0 && missing)
+        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, x0, U, " + tube_names + (need_gU ? ", gU" : "") + " and info are required)");
     if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
     if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
     const long n = (long)gp->N_r * (gp->real_has_grad ? gp->T : 1);      // in 64 bits: N_r is the caller's

@@ -5,7 +5,7 @@
 //
 // Mapping and staging are those of moment_rollout_kernel (moments.hip): ONE CANDIDATE PER LANE, 64-lane workgroups, the packed
 // L_rr^-1 triangles, alpha and X_r staged once in LDS by mom_stage and read as broadcast ds_read_b128, the instantiation set of
-// mom_dispatch, x (NX) in registers across the step loop.
+// mom_dispatch, the launch and the argument checks (mom_launch, mom_check_args with beta), x (NX) in registers across the step loop.
 //   * forward, per step and output: mom_gp_pass1<NRP, HG, false> (the kernel row, acc = L^-1 k, the mean) and mom_variance - the very
 //     calls of moment_rollout_kernel, so with eta = 0 the trajectory is that kernel's mean bit for bit; then one square root and one
 //     FMA.  No Jacobian, no A P A^T.
@@ -102,6 +102,7 @@ __global__ __launch_bounds__(64) void optimistic_rollout_kernel(const Optimistic
         store_state(t);                                                // behind the wait for this step's inputs: nothing waits for the stores
         if (t + 1 < H) opt_load_inputs<NU, G_NY>(a, b, t + 1, uff, et);
 
+        // written out in each forward, not a shared mom_gp_outputs: in moment_rollout_kernel (not tried here) the helper cost the car 6 VGPRs (profiles/lane_frame_isa.md)
         double gm[G_NY], gs[G_NY];                                     // posterior mean and variance per output
 #pragma unroll 1
         for (int o = 0; o < G_NY; ++o) {
@@ -278,38 +279,6 @@ __global__ __launch_bounds__(64) void optimistic_rollout_vjp_kernel(const Optimi
     a.info[b] = info_acc;
 }
 
-template <int ENV, int NRP, bool HG>
-static int optimistic_launch(const OptimisticArgs& a, bool vjp, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.B + 63) / 64);
-    if (vjp)
-        hipLaunchKernelGGL((optimistic_rollout_vjp_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    else
-        hipLaunchKernelGGL((optimistic_rollout_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
-}
-
-// The checks of the two entry points, in the order of mom_check_args; the VJP also requires gU when there are steps.
-static int optimistic_check_args(const std::string& me, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan,
-                                 const double* X_r, int64_t B, int32_t H, const double* x0, const double* U, double beta, const double* X,
-                                 const int32_t* info, bool vjp, const double* gU) {
-    if (!gp) return fail(GPMPC_E_ARG, me + "gp descriptor is NULL");
-    if (!env) return fail(GPMPC_E_ARG, me + "env descriptor is NULL");
-    if (check_gp(gp) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    if (B < 0 || H < 0) return fail(GPMPC_E_ARG, me + "B and H must be >= 0");
-    if (!(beta >= 0.0) || !std::isfinite(beta)) return fail(GPMPC_E_ARG, me + "beta must be finite and >= 0");
-    // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
-    if (B > 0 && (!plan || !X_r || !x0 || !X || !info || (H > 0 && (!U || (vjp && !gU)))))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (plan, X_r, x0, U, X" + (vjp ? ", gU" : "") + " and info are required)");
-    if (gp->D != 2) return fail(GPMPC_E_UNSUPPORTED, me + "only D = 2 is instantiated");
-    if (check_env(gp, env) != GPMPC_OK) return fail(GPMPC_E_ARG, me + last_error());
-    const long n = (long)gp->N_r * (gp->real_has_grad ? gp->T : 1);      // in 64 bits: N_r is the caller's
-    if (n > MOM_MAX_ROWS)
-        return fail(GPMPC_E_UNSUPPORTED, me + "more than 64 label rows (N_r value-only, N_r * T with real_has_grad) are not instantiated");
-    if (B > (int64_t)INT_MAX) return fail(GPMPC_E_UNSUPPORTED, me + "B must be < 2^31 (split the candidates over calls)");
-    return GPMPC_OK;
-}
-
 static int optimistic_run(OptimisticArgs& a, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
                           int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                           const double* eta, int32_t eta_per_candidate, double beta, int32_t* info, bool vjp, void* stream) {
@@ -319,7 +288,9 @@ static int optimistic_run(OptimisticArgs& a, const gpmpc_gp_desc_t* gp, const gp
     a.beta = beta;
     a.info = (int*)info;
     return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
-        return optimistic_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, vjp, (hipStream_t)stream);
+        constexpr int ENV = decltype(e)::value, NRP = decltype(nrp)::value;
+        constexpr bool HG = decltype(hg)::value;
+        return mom_launch(vjp ? optimistic_rollout_vjp_kernel<ENV, NRP, HG> : optimistic_rollout_kernel<ENV, NRP, HG>, a, stream);
     });
 }
 
@@ -333,8 +304,7 @@ int gpmpc_optimistic_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* 
                              int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                              const double* eta, int32_t eta_per_candidate, double beta, double* X, double* F, double* S, int32_t* info,
                              void* stream) {
-    if (int rc = optimistic_check_args("gpmpc_optimistic_rollout: ", gp, env, plan, X_r, B, H, x0, U, beta, X, info, false, nullptr))
-        return rc;
+    if (int rc = mom_check_args("gpmpc_optimistic_rollout: ", gp, env, plan, X_r, B, H, x0, U, "X", {X}, info, false, nullptr, &beta)) return rc;
     if (B == 0) return GPMPC_OK;
     OptimisticArgs a{};
     a.X = X;
@@ -348,7 +318,7 @@ int gpmpc_optimistic_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc
                                  int32_t H, const double* x0, int32_t x0_per_candidate, const double* U, int32_t u_per_candidate,
                                  const double* eta, int32_t eta_per_candidate, double beta, const double* X, const double* gX, double* gx0,
                                  double* gU, double* gEta, int32_t* info, void* stream) {
-    if (int rc = optimistic_check_args("gpmpc_optimistic_rollout_vjp: ", gp, env, plan, X_r, B, H, x0, U, beta, X, info, true, gU)) return rc;
+    if (int rc = mom_check_args("gpmpc_optimistic_rollout_vjp: ", gp, env, plan, X_r, B, H, x0, U, "X", {X}, info, true, gU, &beta)) return rc;
     if (B == 0) return GPMPC_OK;
     OptimisticArgs a{};
     a.X = const_cast<double*>(X);

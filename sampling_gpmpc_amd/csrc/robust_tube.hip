@@ -3,13 +3,14 @@
 // gpmpc_robust_tube_rollout).  gfx950, wave64.
 //
 // Mapping and staging are those of moment_rollout_kernel (moments.hip): ONE CANDIDATE PER LANE, the packed L_rr^-1 triangles, alpha and
-// X_r staged in LDS by mom_stage, the GP of a step by mom_gp_pass1 / mom_variance, the environment by the env_*_ct functions of
-// moments_step.hpp - so the centres p_t are the means of the moment rollout bit for bit.  What is new is the shape matrix: instead of
+// X_r staged in LDS by mom_stage, the GP of a step by mom_gp_pass1 / mom_variance, the environment by the env_*_ct functions,
+// the launch and the argument checks of moments_step.hpp - so the centres p_t are the means of the moment rollout bit for bit.  What is new is the shape matrix: instead of
 // P+ = A P A^T + G diag(s) G^T the step sums three ellipsoids by their trace-minimal outer ellipsoid,
 //   Q+ = (nx diag(sb^2) (+) nx diag(ub^2)) (+) A Q A^T,
 // the boxes sb (confidence interval of the GP plus the Lipschitz remainder of its standard deviation) and ub (the remainder of the
 // linearisation of the mean) growing with r2 = lambda_max(W Q W^T), the largest squared distance |(x - p, K (x - p))|^2 over the set.
 // lambda_max of the symmetric nx x nx matrix (nx <= 4) is taken in registers by cyclic Jacobi sweeps with compile-time indices.
+// The shape step is robust_shape_step (robust_step.hpp), which the VJP calls as well.
 // The centre (NX) and the lower triangle of Q (NX (NX + 1) / 2 <= 10 entries) stay in registers across the step loop.
 // Work per candidate-step: the GP pass of the moment rollout, then ~4 NX^3 for A Q A^T and W Q W^T and JAC_SWEEPS NX (NX - 1) / 2 rotations.
 #include "robust_step.hpp"
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
-            for (int j = 0; j < NX; ++j) Qt[i * NX + j] = (j <= i) ? Q[i][j] : Q[j][i];
+            for (int j = 0; j < NX; ++j) Qt[i * NX + j] = sym_at<NX>(Q, i, j);
     };
 
 #pragma unroll 1
@@ -87,6 +88,7 @@ __global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
 
+        // written out in each forward, not a shared mom_gp_outputs: in moment_rollout_kernel (not tried here) the helper cost the car 6 VGPRs (profiles/lane_frame_isa.md)
         double gm[G_NY], gs[G_NY], gd[G_NY][2];                        // posterior mean, variance, d mean / d xi per output
 #pragma unroll 1
         for (int o = 0; o < G_NY; ++o) {
@@ -109,87 +111,15 @@ __global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
         env_step_ct<ENV>(a.env, x, u, gm, xn);
         env_noise_diag_ct<ENV>(x, gs, gdiag);
 
-        // ---- Qbar = A Q A^T, lower triangle --------------------------------------------------------------------------------
-        double AQ[NX][NX], Qn[NX][NX];
-        double tr_bar = 0.0;
+        // ---- Q+ = (nx diag(sb^2) (+) nx diag(ub^2)) (+) A Q A^T: the shape step of robust_step.hpp ------------------------------------
+        RobustShape<NX> sh;
+        robust_shape_step<NX, false>(A, Q, gdiag, lmu, lsig, beta, a.W, sh);
+        const double r2 = sh.r2;
+        chk += sh.lam_abs;
 #pragma unroll
         for (int i = 0; i < NX; ++i)
 #pragma unroll
-            for (int c = 0; c < NX; ++c) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < NX; ++kk) s_ = fma(A[i][kk], (c <= kk) ? Q[kk][c] : Q[c][kk], s_);
-                AQ[i][c] = s_;
-            }
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < NX; ++kk) s_ = fma(AQ[i][kk], A[j][kk], s_);
-                Qn[i][j] = s_;
-                if (i == j) tr_bar += s_;
-            }
-
-        // ---- r2 = lambda_max(W Q W^T), W upper triangular ------------------------------------------------------------------
-        double WQ[NX][NX], T[NX][NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int c = 0; c < NX; ++c) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = i; kk < NX; ++kk) s_ = fma(a.W[i][kk], (c <= kk) ? Q[kk][c] : Q[c][kk], s_);
-                WQ[i][c] = s_;
-            }
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int j = 0; j < NX; ++j) {
-                double s_ = 0.0;
-                if (j <= i) {
-#pragma unroll
-                    for (int kk = j; kk < NX; ++kk) s_ = fma(WQ[i][kk], a.W[j][kk], s_);
-                }
-                T[i][j] = s_;
-            }
-        double lam_abs;
-        double r2 = sym_lambda_max<NX>(T, lam_abs);
-        chk += lam_abs;
-        r2 = (r2 < 0.0) ? 0.0 : r2;                                    // NaN stays (and is in chk)
-        const double r1 = sqrt(r2);
-
-        // ---- the remainder boxes, their outer ellipsoids nx diag(b^2), and the two sums --------------------------------------
-        double qs[NX], qm[NX];
-        double tr_s = 0.0, tr_m = 0.0;
-#pragma unroll
-        for (int d = 0; d < NX; ++d) {
-            const double ub = 0.5 * lmu[d] * r2;
-            const double sb = beta * (sqrt(gdiag[d]) + lsig[d] * r1);
-            qs[d] = (double)NX * (sb * sb);
-            qm[d] = (double)NX * (ub * ub);
-            tr_s += qs[d];
-            tr_m += qm[d];
-        }
-        double ws, wm, wd, wb;
-        ellipsoid_sum_weights(tr_s, tr_m, ws, wm);
-        double tr_d = 0.0;
-#pragma unroll
-        for (int d = 0; d < NX; ++d) {
-            qs[d] = ws * qs[d] + wm * qm[d];                           // Q_sig (+) Q_mu, diagonal
-            tr_d += qs[d];
-        }
-        ellipsoid_sum_weights(tr_d, tr_bar, wd, wb);
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) {
-                double v = wb * Qn[i][j];
-                if (i == j) v += wd * qs[i];
-                Qn[i][j] = v;
-                chk += fabs(v);
-            }
+            for (int j = 0; j <= i; ++j) chk += fabs(sh.Qnext[i][j]);
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             chk += fabs(xn[i]);
@@ -227,19 +157,11 @@ __global__ __launch_bounds__(64) void robust_tube_kernel(const RobustArgs a) {
         for (int i = 0; i < NX; ++i) {
             x[i] = dead ? nan : xn[i];
 #pragma unroll
-            for (int j = 0; j <= i; ++j) Q[i][j] = dead ? nan : Qn[i][j];
+            for (int j = 0; j <= i; ++j) Q[i][j] = dead ? nan : sh.Qnext[i][j];
         }
     }
     store_state(H);
     if (active) a.info[b] = info_acc;
-}
-
-template <int ENV, int NRP, bool HG>
-static int robust_launch(const RobustArgs& a, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.B + 63) / 64);
-    hipLaunchKernelGGL((robust_tube_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
 }
 
 }  // namespace gpmpc
@@ -253,17 +175,12 @@ int gpmpc_robust_tube_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t*
                               const double* Q0, const double* l_mu, const double* l_sigma, int32_t l_per_candidate, double beta,
                               double* M, double* Q, double* R2, double* Sd, double* Jz, int32_t* info, void* stream) {
     const std::string me = "gpmpc_robust_tube_rollout: ";
-    if (int rc = mom_check_args(me, gp, env, plan, X_r, B, H, x0, U, M, Q, info, false, nullptr)) return rc;
-    if (B > 0 && (!l_mu || !l_sigma)) return fail(GPMPC_E_ARG, me + "NULL pointer (l_mu and l_sigma are required)");
-    if (B == 0) return GPMPC_OK;
+    // "M, P": the message has always named the shape array as the moment rollout does, and stays as it is
+    if (int rc = mom_check_args(me, gp, env, plan, X_r, B, H, x0, U, "M, P", {M, Q}, info, false, nullptr)) return rc;
     RobustArgs a;
     mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
-    a.Q0 = Q0;
-    a.l_mu = l_mu;
-    a.l_sigma = l_sigma;
-    a.l_per = l_per_candidate != 0;
-    a.beta = beta;
-    if (!robust_fill_w(a, env)) return fail(GPMPC_E_ARG, me + "the feedback gain K is not finite");
+    if (int rc = robust_fill_args(me, a, env, B, Q0, l_mu, l_sigma, l_per_candidate, beta)) return rc;
+    if (B == 0) return GPMPC_OK;
     a.M = M;
     a.Q = Q;
     a.R2 = R2;
@@ -271,7 +188,7 @@ int gpmpc_robust_tube_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t*
     a.Jz = Jz;
     a.info = (int*)info;
     return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
-        return robust_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+        return mom_launch(robust_tube_kernel<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>, a, stream);
     });
 }
 

@@ -7,12 +7,14 @@
 // triangle of the symmetric Lambda (cotangent of Q_{t+1}) in registers; p_t and Q_t are read from the forward's M and Q, the forward
 // is not run again.  Per step:
 //   * the GP passes of the moment VJP (mom_gp_grad, moments_step.hpp): mean, gradient, Hessian, clamped variance and its gradient;
-//   * the forward's step 2 - 6 again from Q_t (Qbar, r2 with its eigenvector by sym_lambda_max_vec, the boxes, the two ellipsoid sums);
+//   * the forward's step 2 - 6 again from Q_t by the function the forward calls (robust_shape_step, robust_step.hpp: Qbar, r2 - here
+//     with its eigenvector -, the boxes, the two ellipsoid sums), so the values and clamp decisions differentiated are the forward's;
 //   * their adjoints in reverse order - the sum weights through ellipsoid_sum_weights_adj, the boxes to r2, gdiag, l_mu and l_sigma,
 //     r2 to Q_t through the eigenvector, Qbar to Q_t and A_t;
 //   * the tail of the moment VJP (mom_step_tail) from Abar, the cotangent of gdiag and lambda to the cotangents of x_t and u_t.
 // Gradients are per candidate (no cross-lane reduction, no atomics, no workspace).  The step body is a __host__ __device__ function,
-// as mgv_candidate is.
+// as mgv_candidate is.  The launch, the argument checks and the symmetric-matrix helpers are those of moments_step.hpp; the robust
+// pair's own checks are robust_fill_args.
 #include "robust_step.hpp"
 
 namespace gpmpc {
@@ -23,16 +25,15 @@ struct RobustGradArgs : RobustStepArgs {
     int* info;
 };
 
-// The whole backward sweep of candidate b.  Ltri / alpha_s / xr_s: the staged tables (LDS on the device).
+// The whole backward sweep of candidate b.  tb: the staged tables (LDS on the device).
 template <int ENV, int NRP, bool HG>
-__host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, const double* Ltri, const double* alpha_s,
-                                                        const double* xr_s, const long b, const bool active) {
+__host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, const MomTables& tb, const long b, const bool active) {
     constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
     constexpr int TRI = mom_col_ofs<NRP>(NRP);
     const GpParams& gp = a.gp;
     const int n = gp.n_r;
     const int H = a.H;
-    const double nan = __builtin_nan("");
+    const double nan = MOM_NAN;
     const double beta = a.beta;
 
     double lam[NX], Lam[NX][NX];                                       // Lam: the lower triangle [i][j], j <= i, is live
@@ -56,12 +57,11 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
         for (int i = 0; i < NX; ++i)
 #pragma unroll
             for (int j = 0; j <= i; ++j) {
-                Lam[i][j] = g ? 0.5 * (g[i * NX + j] + g[j * NX + i]) : 0.0;
+                Lam[i][j] = sym_cotangent<NX>(g, i, j);
                 chk += fabs(Lam[i][j]) + fabs(QH[i * NX + j]);
                 if (a.Q0) chk += fabs(a.Q0[(b * NX + i) * NX + j]);
             }
     }
-#define RTV_SYM(S, i, j) (((j) <= (i)) ? S[i][j] : S[j][i])
 
 #pragma unroll 1
     for (int t = H - 1; t >= 0; --t) {
@@ -77,12 +77,13 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
         for (int i = 0; i < NU; ++i) chk += fabs(u[i]);
 
         // ---- the GP at xi: mean, gradient, Hessian, variance and its gradient per output ----------------------------------------
+        // written out in both VJPs, not a shared mom_gp_grad_outputs: as a helper it costs the car 4 - 20 VGPRs (profiles/lane_frame_isa.md)
         double gm[G_NY], gs[G_NY], gd[G_NY][2], gh[G_NY][3], ge[G_NY][2];   // gh: H00, H01, H11; ge: d s / d xi (0 where clamped)
 #pragma unroll 1
         for (int o = 0; o < G_NY; ++o) {
             const double il[2] = {gp.inv_l2[o][0], gp.inv_l2[o][1]};
             MomGpGrad r;
-            mom_gp_grad<NRP, HG>(gp, Ltri + o * TRI, alpha_s + o * NRP, xr_s, n, il, gp.os[o], xi, info_acc, r);
+            mom_gp_grad<NRP, HG>(gp, tb.Ltri + o * TRI, tb.alpha + o * NRP, tb.xr, n, il, gp.os[o], xi, info_acc, r);
             const MomGpSums& g = r.g;
             chk += fabs(g.m) + fabs(r.s) + fabs(g.d0) + fabs(g.d1) + fabs(g.h00) + fabs(g.h01) + fabs(g.h11) + fabs(r.e0) + fabs(r.e1);
 #pragma unroll
@@ -97,133 +98,57 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
         env_jacobian_ct<ENV>(a.env, x, gm, gd, dxi, A);
         env_noise_diag_ct<ENV>(x, gs, gdiag);
 
-        // ---- the forward's steps 2 - 6 from Q_t, written as robust_tube_kernel writes them ------------------------------------------
+        // ---- the forward's steps 2 - 6 from Q_t: the shape step the forward runs (robust_step.hpp), with the eigenvector ----------------
         double Q[NX][NX];                                              // Q_t, the lower triangle as the forward keeps it
-        {
-            const double* Qt = a.Q + (b * (H + 1) + t) * (NX * NX);
-#pragma unroll
-            for (int i = 0; i < NX; ++i)
-#pragma unroll
-                for (int j = 0; j <= i; ++j) {
-                    Q[i][j] = Qt[i * NX + j];
-                    chk += fabs(Q[i][j]);
-                }
-        }
-        double AQ[NX][NX], Qn[NX][NX];
-        double tr_bar = 0.0;
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int c = 0; c < NX; ++c) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < NX; ++kk) s_ = fma(A[i][kk], RTV_SYM(Q, kk, c), s_);
-                AQ[i][c] = s_;
-            }
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = 0; kk < NX; ++kk) s_ = fma(AQ[i][kk], A[j][kk], s_);
-                Qn[i][j] = s_;
-                if (i == j) tr_bar += s_;
-            }
+        sym_load<NX>(a.Q + (b * (H + 1) + t) * (NX * NX), Q, chk);
+        RobustShape<NX> sh;
+        robust_shape_step<NX, true>(A, Q, gdiag, lmu, lsig, beta, a.W, sh);
+        chk += sh.lam_abs;
         double wv[NX];                                                 // W^T v, v the unit eigenvector of W Q_t W^T for lambda_max
-        double r2;
-        {
-            double WQ[NX][NX], T[NX][NX], v[NX];
 #pragma unroll
-            for (int i = 0; i < NX; ++i)
+        for (int c = 0; c < NX; ++c) {
+            double s_ = 0.0;
 #pragma unroll
-                for (int c = 0; c < NX; ++c) {
-                    double s_ = 0.0;
-#pragma unroll
-                    for (int kk = i; kk < NX; ++kk) s_ = fma(a.W[i][kk], RTV_SYM(Q, kk, c), s_);
-                    WQ[i][c] = s_;
-                }
-#pragma unroll
-            for (int i = 0; i < NX; ++i)
-#pragma unroll
-                for (int j = 0; j < NX; ++j) {
-                    double s_ = 0.0;
-                    if (j <= i) {
-#pragma unroll
-                        for (int kk = j; kk < NX; ++kk) s_ = fma(WQ[i][kk], a.W[j][kk], s_);
-                    }
-                    T[i][j] = s_;
-                }
-            double lam_abs;
-            r2 = sym_lambda_max_vec<NX>(T, lam_abs, v);
-            chk += lam_abs;
-            r2 = (r2 < 0.0) ? 0.0 : r2;                                // NaN stays (and is in chk)
-#pragma unroll
-            for (int c = 0; c < NX; ++c) {
-                double s_ = 0.0;
-#pragma unroll
-                for (int kk = 0; kk <= c; ++kk) s_ = fma(a.W[kk][c], v[kk], s_);
-                wv[c] = s_;
-            }
+            for (int kk = 0; kk <= c; ++kk) s_ = fma(a.W[kk][c], sh.v[kk], s_);
+            wv[c] = s_;
         }
-        const double r1 = sqrt(r2);
-        double ub[NX], sb[NX], qs[NX], qm[NX], qd[NX];
-        double tr_s = 0.0, tr_m = 0.0;
-#pragma unroll
-        for (int d = 0; d < NX; ++d) {
-            ub[d] = 0.5 * lmu[d] * r2;
-            sb[d] = beta * (sqrt(gdiag[d]) + lsig[d] * r1);
-            qs[d] = (double)NX * (sb[d] * sb[d]);
-            qm[d] = (double)NX * (ub[d] * ub[d]);
-            tr_s += qs[d];
-            tr_m += qm[d];
-        }
-        double ws, wm, wd, wb;
-        ellipsoid_sum_weights(tr_s, tr_m, ws, wm);
-        double tr_d = 0.0;
-#pragma unroll
-        for (int d = 0; d < NX; ++d) {
-            qd[d] = ws * qs[d] + wm * qm[d];                           // Q_sig (+) Q_mu, diagonal
-            tr_d += qd[d];
-        }
-        ellipsoid_sum_weights(tr_d, tr_bar, wd, wb);
 
         // ---- step 6 and the two sums' weights: Lambda -> Qbb (cotangent of Qbar, lower triangle) and the cotangents of the boxes ---
         double wbbar = 0.0, wdbar = 0.0;
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-            wdbar = fma(Lam[i][i], qd[i], wdbar);
+            wdbar = fma(Lam[i][i], sh.qd[i], wdbar);
 #pragma unroll
-            for (int j = 0; j <= i; ++j) wbbar = fma((i == j) ? Lam[i][j] : 2.0 * Lam[i][j], Qn[i][j], wbbar);
+            for (int j = 0; j <= i; ++j) wbbar = fma((i == j) ? Lam[i][j] : 2.0 * Lam[i][j], sh.Qn[i][j], wbbar);
         }
         double trdbar, trbbar, trsbar, trmbar;
-        ellipsoid_sum_weights_adj(tr_d, tr_bar, wdbar, wbbar, trdbar, trbbar);
+        ellipsoid_sum_weights_adj(sh.tr_d, sh.tr_bar, wdbar, wbbar, trdbar, trbbar);
         double Qbb[NX][NX], qdbar[NX];
         double wsbar = 0.0, wmbar = 0.0;
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
-            qdbar[i] = fma(wd, Lam[i][i], trdbar);
-            wsbar = fma(qdbar[i], qs[i], wsbar);
-            wmbar = fma(qdbar[i], qm[i], wmbar);
+            qdbar[i] = fma(sh.wd, Lam[i][i], trdbar);
+            wsbar = fma(qdbar[i], sh.qs[i], wsbar);
+            wmbar = fma(qdbar[i], sh.qm[i], wmbar);
 #pragma unroll
-            for (int j = 0; j <= i; ++j) Qbb[i][j] = (i == j) ? fma(wb, Lam[i][j], trbbar) : wb * Lam[i][j];
+            for (int j = 0; j <= i; ++j) Qbb[i][j] = (i == j) ? fma(sh.wb, Lam[i][j], trbbar) : sh.wb * Lam[i][j];
         }
-        ellipsoid_sum_weights_adj(tr_s, tr_m, wsbar, wmbar, trsbar, trmbar);
+        ellipsoid_sum_weights_adj(sh.tr_s, sh.tr_m, wsbar, wmbar, trsbar, trmbar);
 
         // ---- steps 5 and 4: the boxes -> r2, gdiag, l_mu, l_sigma ---------------------------------------------------------------
         double dbar[NX];                                               // cotangent of gdiag
         double r2bar = 0.0, r1bar = 0.0;
 #pragma unroll
         for (int d = 0; d < NX; ++d) {
-            const double sbbar = 2.0 * (double)NX * sb[d] * fma(ws, qdbar[d], trsbar);
-            const double ubbar = 2.0 * (double)NX * ub[d] * fma(wm, qdbar[d], trmbar);
+            const double sbbar = 2.0 * (double)NX * sh.sb[d] * fma(sh.ws, qdbar[d], trsbar);
+            const double ubbar = 2.0 * (double)NX * sh.ub[d] * fma(sh.wm, qdbar[d], trmbar);
             r2bar = fma(0.5 * lmu[d], ubbar, r2bar);
             r1bar = fma(beta * lsig[d], sbbar, r1bar);
             dbar[d] = (gdiag[d] > 0.0) ? beta * sbbar / (2.0 * sqrt(gdiag[d])) : 0.0;    // nothing through sqrt(0)
-            glm[d] = fma(0.5 * r2, ubbar, glm[d]);
-            gls[d] = fma(beta * r1, sbbar, gls[d]);
+            glm[d] = fma(0.5 * sh.r2, ubbar, glm[d]);
+            gls[d] = fma(beta * sh.r1, sbbar, gls[d]);
         }
-        r2bar = (r2 > 0.0) ? r2bar + r1bar / (2.0 * r1) : 0.0;         // r2 == 0 (clamped, Q_t = 0): nothing passes to Q_t
+        r2bar = (sh.r2 > 0.0) ? r2bar + r1bar / (2.0 * sh.r1) : 0.0;   // r2 == 0 (clamped, Q_t = 0): nothing passes to Q_t
 
         // ---- steps 3 and 2: Qtbar = r2bar (W^T v)(W^T v)^T + A^T Qbb A (lower triangle),  Abar = 2 Qbb A Q ----------------------------
         double Abar[NX][NX], Qtbar[NX][NX];
@@ -236,8 +161,8 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
                     double s_ = 0.0, l_ = 0.0;
 #pragma unroll
                     for (int kk = 0; kk < NX; ++kk) {
-                        s_ = fma(RTV_SYM(Qbb, i, kk), AQ[kk][c], s_);
-                        l_ = fma(RTV_SYM(Qbb, i, kk), A[kk][c], l_);
+                        s_ = fma(sym_at<NX>(Qbb, i, kk), sh.AQ[kk][c], s_);
+                        l_ = fma(sym_at<NX>(Qbb, i, kk), A[kk][c], l_);
                     }
                     Abar[i][c] = 2.0 * s_;
                     LA[i][c] = l_;
@@ -271,12 +196,11 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
             chk += fabs(lam[i]) + fabs(glm[i]) + fabs(gls[i]);
 #pragma unroll
             for (int j = 0; j <= i; ++j) {
-                Lam[i][j] = Qtbar[i][j] + (g ? 0.5 * (g[i * NX + j] + g[j * NX + i]) : 0.0);
+                Lam[i][j] = Qtbar[i][j] + sym_cotangent<NX>(g, i, j);
                 chk += fabs(Lam[i][j]);
             }
         }
     }
-#undef RTV_SYM
 
     const bool dead = !mom_finite(chk);
     if (dead) info_acc |= GPMPC_INFO_NONFINITE;
@@ -287,16 +211,8 @@ __host__ __device__ __forceinline__ void rtv_candidate(const RobustGradArgs& a, 
         if (a.glmu) a.glmu[b * NX + i] = dead ? nan : glm[i];
         if (a.glsig) a.glsig[b * NX + i] = dead ? nan : gls[i];
     }
-    if (a.gQ0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-#pragma unroll
-            for (int j = 0; j < NX; ++j)        // both mirrored copies of an off-diagonal entry are read from the lower triangle
-                a.gQ0[(b * NX + i) * NX + j] = (j > i) ? 0.0 : dead ? nan : (j == i) ? Lam[i][i] : 2.0 * Lam[i][j];
-    }
-    if (dead) {
-        for (int e = 0; e < H * NU; ++e) a.gU[b * H * NU + e] = nan;
-    }
+    if (a.gQ0) sym_store_grad0<NX>(a.gQ0 + b * (NX * NX), Lam, dead);
+    if (dead) mom_fill_nan(a.gU + b * H * NU, H * NU);
     a.info[b] = info_acc;
 }
 
@@ -311,15 +227,7 @@ __global__ __launch_bounds__(64) void robust_tube_vjp_kernel(const RobustGradArg
     __syncthreads();
     const long braw = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = braw < a.B;
-    rtv_candidate<ENV, NRP, HG>(a, Ltri, alpha_s, xr_s, active ? braw : a.B - 1, active);
-}
-
-template <int ENV, int NRP, bool HG>
-static int rtv_launch(const RobustGradArgs& a, hipStream_t st) {
-    const unsigned grid = (unsigned)((a.B + 63) / 64);
-    hipLaunchKernelGGL((robust_tube_vjp_kernel<ENV, NRP, HG>), dim3(grid), dim3(64), 0, st, a);
-    GPMPC_HIP_CHECK(hipGetLastError());
-    return GPMPC_OK;
+    rtv_candidate<ENV, NRP, HG>(a, MomTables{Ltri, alpha_s, xr_s}, active ? braw : a.B - 1, active);
 }
 
 }  // namespace gpmpc
@@ -334,17 +242,12 @@ int gpmpc_robust_tube_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_des
                                   const double* M, const double* Q, const double* gM, const double* gQ, double* g_x0, double* g_U,
                                   double* g_Q0, double* g_l_mu, double* g_l_sigma, int32_t* info, void* stream) {
     const std::string me = "gpmpc_robust_tube_rollout_vjp: ";
-    if (int rc = mom_check_args(me, gp, env, plan, X_r, B, H, x0, U, M, Q, info, true, g_U)) return rc;
-    if (B > 0 && (!l_mu || !l_sigma)) return fail(GPMPC_E_ARG, me + "NULL pointer (l_mu and l_sigma are required)");
-    if (B == 0) return GPMPC_OK;
+    // "M, P": as in gpmpc_robust_tube_rollout, the message's name for Q stays as it was
+    if (int rc = mom_check_args(me, gp, env, plan, X_r, B, H, x0, U, "M, P", {M, Q}, info, true, g_U)) return rc;
     RobustGradArgs a;
     mom_fill_args(a, gp, env, plan, X_r, B, H, x0, x0_per_candidate, U, u_per_candidate);
-    a.Q0 = Q0;
-    a.l_mu = l_mu;
-    a.l_sigma = l_sigma;
-    a.l_per = l_per_candidate != 0;
-    a.beta = beta;
-    if (!robust_fill_w(a, env)) return fail(GPMPC_E_ARG, me + "the feedback gain K is not finite");
+    if (int rc = robust_fill_args(me, a, env, B, Q0, l_mu, l_sigma, l_per_candidate, beta)) return rc;
+    if (B == 0) return GPMPC_OK;
     a.M = M;
     a.Q = Q;
     a.gM = gM;
@@ -356,7 +259,7 @@ int gpmpc_robust_tube_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_des
     a.glsig = g_l_sigma;
     a.info = (int*)info;
     return mom_dispatch(env->env_id, a.gp.n_r, a.gp.real_has_grad != 0, [&](auto e, auto nrp, auto hg) {
-        return rtv_launch<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>(a, (hipStream_t)stream);
+        return mom_launch(robust_tube_vjp_kernel<decltype(e)::value, decltype(nrp)::value, decltype(hg)::value>, a, stream);
     });
 }
 

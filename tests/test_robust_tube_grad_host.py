@@ -151,9 +151,11 @@ def test_symbol_is_declared_exported_and_bound_and_the_abi_stays_12(lib):
     csrc = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
     assert '"robust_tube_grad.hip"' in open(os.path.join(csrc, "build.py")).read()
     src = open(os.path.join(csrc, "robust_tube_grad.hip")).read()
-    for fn in ("mom_stage<", "mom_gp_grad<", "mom_step_tail<", "mom_dispatch(", "mom_check_args(", "mom_fill_args(", "robust_fill_w(",
-               "env_jacobian_ct<", "env_noise_diag_ct<", "env_input_ct<", "sym_lambda_max_vec<"):
+    for fn in ("mom_stage<", "mom_gp_grad<", "mom_step_tail<", "mom_dispatch(", "mom_launch(", "mom_check_args(", "mom_fill_args(",
+               "robust_fill_args(", "env_jacobian_ct<", "env_noise_diag_ct<", "env_input_ct<", "robust_shape_step<"):
         assert fn in src, fn                                                # the GP passes, the tail and the environment are not copied
+    for copied in ("hipLaunchKernelGGL", "sym_lambda_max<", "ellipsoid_sum_weights("):
+        assert copied not in src, copied                                    # the launch and the forward's shape step are not written out again
     grad = open(os.path.join(csrc, "moments_grad.hip")).read()
     assert "mom_gp_grad<" in grad and "mom_step_tail<" in grad              # both VJP kernels call the shared backward step
     for name in ("robust_tube_rollout_vjp", "robust_tube_rollout_vjp_plan", "plan_inputs_robust", "plan_inputs_robust_plan"):

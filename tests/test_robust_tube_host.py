@@ -56,8 +56,9 @@ def test_header_documents_both_entry_points_and_the_sources_are_built():
     build = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "build.py")).read()
     assert '"robust_tube.hip"' in build and '"lipschitz.hip"' in build
     src = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "robust_tube.hip")).read()
-    for fn in ("mom_stage<", "mom_gp_pass1<", "mom_variance(", "mom_dispatch(", "mom_check_args(", "mom_fill_args(", "env_jacobian_ct<",
-               "env_input_jacobian_ct<", "env_noise_diag_ct<", "env_step_ct<", "env_input_ct<"):
+    for fn in ("mom_stage<", "mom_gp_pass1<", "mom_variance(", "mom_dispatch(", "mom_launch(", "mom_check_args(", "mom_fill_args(",
+               "robust_fill_args(", "robust_shape_step<", "env_jacobian_ct<", "env_input_jacobian_ct<", "env_noise_diag_ct<",
+               "env_step_ct<", "env_input_ct<"):
         assert fn in src, fn                                                # the GP pass and the environment are not copied
 
 
