@@ -261,13 +261,12 @@ int gpmpc_pathwise_rollout(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* en
                            const double* Z, int64_t ldz, const double* V, double* X_traj, double* Y, int32_t* info, void* stream) {
     const std::string me = "gpmpc_pathwise_rollout: ";
     if (int rc = pw_rollout_check(me, gp, env, M, Ns, ldz, H)) return rc;
-    if (Ns > 0 && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && !U)))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj and info are required)");
+    if (int rc = pw_null_check(me, Ns > 0, H, {X_r, omega, x0, Z, V, X_traj, info}, {U}, "X_r, omega, x0, U, Z, V, X_traj and info")) return rc;
     if (int rc = pw_rollout_check_env(me, gp, env, M, Ns)) return rc;
     if (Ns == 0) return GPMPC_OK;
     PwRollArgs a;
-    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_sample, U, u_per_sample, Z, ldz, V, info);
-    a.X_traj = X_traj, a.Y = Y;
+    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_sample, U, Z, ldz, V, info);
+    a.X_traj = X_traj, a.Y = Y, a.u_per = u_per_sample != 0;
     const dim3 grid((unsigned)((Ns + 3) / 4)), block(256);
     return pw_launch_env(env->env_id, [&](auto e) {
         hipLaunchKernelGGL(pathwise_rollout_kernel<decltype(e)::value>, grid, block, 0, (hipStream_t)stream, a);

@@ -2,9 +2,10 @@
 // include/gpmpc_hip.h, gpmpc_pathwise_rollout_cand / _cand_vjp).  gfx950, wave64, FP64 on the vector pipe.
 //
 // Slice [b] of every output is what gpmpc_pathwise_rollout / gpmpc_pathwise_rollout_vjp give for U = U[b] shared by the samples, bit for
-// bit: a (candidate, sample) pair runs pw_rollout_step and pw_eval_point (pathwise_step.hpp), the functions of those kernels, on its
-// own inputs; the adjoint algebra of a step and the glue (the initial state, the stores, the loads one step ahead of the backward
-// sweep) are the statements of pathwise_rollout_kernel and pathwise_rollout_vjp_kernel.
+// bit: a (candidate, sample) pair runs pw_rollout_step and pw_adjoint_step (pathwise_step.hpp), the functions of those
+// kernels, on its own inputs, so the arithmetic of a pair is theirs by construction; the glue around a step (the initial state, the
+// stores, the loads one step ahead of the backward sweep) is written as in those kernels and not shared (as one
+// function it cost time in one kernel or the other).
 // Mapping: ONE WAVE PER (SAMPLE, TILE OF PW_CB CANDIDATES), four waves (four samples of one tile) per workgroup, a linear grid of
 // ceil(Ns / 4) * ceil(B / PW_CB) workgroups (tiles are the slow index: neighbouring workgroups read neighbouring rows of Z).  What
 // belongs to the sample and not to the candidate is done once per wave: the non-finite scan of its Z row and of V (a whole row of
@@ -103,92 +104,17 @@ __global__ __launch_bounds__(256) void pathwise_rollout_cand_kernel(const PwCand
     }
 }
 
-// The adjoint of one step (uniform over the wave): gu = B_t^T lam and lam <- A_t^T lam + gxt at the point rebuilt from x = x_t and
-// ut = U[t].  These are the statements of the sweep of pathwise_rollout_vjp_kernel (pathwise_grad.hip), restated and not shared: that
-// kernel keeps its text, and under -ffp-contract=on the same statements are the same operations.  y: the forward's
-// Y[:, t], read when have_y, else the sample is evaluated again with the forward's function.  False when anything is not finite.
-template <int ENV>
-__device__ __forceinline__ bool pw_cand_adjoint_step(const GpParams& gp, const EnvParams& env, const double* omega, const double* zrow,
-                                                     int F, int stride_o, int lane, bool has_row, const double (&xr)[2],
-                                                     const double (&vn)[EnvDims<ENV>::G_NY], const double (&x)[EnvDims<ENV>::NX],
-                                                     const double (&ut)[EnvDims<ENV>::NU], bool have_y,
-                                                     const double (&y)[EnvDims<ENV>::G_NY][3], bool have_gx,
-                                                     const double (&gxt)[EnvDims<ENV>::NX], double (&lam)[EnvDims<ENV>::NX],
-                                                     double (&gu)[EnvDims<ENV>::NU]) {
-    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
-    constexpr int D = 2;
-    double u[NU], xi[D], g[G_NY], gg[G_NY][D];
-    bool fin = true;
-#pragma unroll
-    for (int i = 0; i < NU; ++i) {
-        const double ufi = ut[i];
-        if (env.use_feedback) {                                         // uniform
-            double acc = 0.0;
-#pragma unroll
-            for (int j = 0; j < NX; ++j) acc += (env.x_goal[j] - x[j]) * env.K[i][j];
-            u[i] = -acc + ufi;
-        } else {
-            u[i] = ufi;
-        }
-        fin = fin && pw_finite(u[i]);
-    }
-    xi[0] = x[EnvDims<ENV>::SEL];
-    xi[1] = u[0];
-#pragma unroll
-    for (int o = 0; o < G_NY; ++o) {
-        if (have_y) {                                                   // uniform
-            g[o] = y[o][0], gg[o][0] = y[o][1], gg[o][1] = y[o][2];
-        } else {
-            pw_eval_point<D, true>(omega + (long)o * F * D, zrow + (long)o * stride_o, F, lane, sqrt(gp.os[o] / (double)F), gp.os[o],
-                                   gp.inv_l2[o], has_row, xr, vn[o], xi, g[o], gg[o]);
-        }
-        fin = fin && pw_finite(g[o]) && pw_finite(gg[o][0]) && pw_finite(gg[o][1]);
-    }
-    double dxi[D][NX], A[NX][NX], B[NX][NU];
-    env_jacobian_ct<ENV>(env, x, g, gg, dxi, A);
-    env_input_jacobian_ct<ENV>(env, x, gg, B);
-    double ln[NX];
-#pragma unroll
-    for (int i = 0; i < NU; ++i) {                                       // gU[t] = B_t^T lam, rows in ascending order
-        double acc = B[0][i] * lam[0];
-#pragma unroll
-        for (int r = 1; r < NX; ++r) acc = fma(B[r][i], lam[r], acc);
-        gu[i] = acc;
-        fin = fin && pw_finite(acc);
-    }
-#pragma unroll
-    for (int c = 0; c < NX; ++c) {                                       // lam = A_t^T lam + gX[:, t]
-        double acc = A[0][c] * lam[0];
-#pragma unroll
-        for (int r = 1; r < NX; ++r) acc = fma(A[r][c], lam[r], acc);
-        if (have_gx) acc += gxt[c];
-        ln[c] = acc;
-        fin = fin && pw_finite(acc);
-    }
-#pragma unroll
-    for (int c = 0; c < NX; ++c) lam[c] = ln[c];
-    return fin;
-}
-
 template <int ENV>
 __global__ __launch_bounds__(256) void pathwise_rollout_cand_vjp_kernel(const PwCandArgs a) {
     constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
     constexpr int D = 2;
-    const GpParams& gp = a.gp;
-    const EnvParams& env = a.env;
-    const int n = gp.N_r, F = a.M / 2, stride_o = a.M + n, H = a.H;
+    const int H = a.H;
     const int lane = threadIdx.x & 63;
     long s, b0, b1;
     if (!pw_cand_wave(a, s, b0, b1)) return;                            // (no workgroup barrier below)
-    const double* zrow = a.Z + s * a.ldz;
     const double nan = __builtin_nan("");
-    const bool has_row = lane < n;
-    const int row = has_row ? lane : n - 1;
-    const double xr[D] = {a.X_r[(long)row * D], a.X_r[(long)row * D + 1]};
-    double vn[G_NY];
-#pragma unroll
-    for (int o = 0; o < G_NY; ++o) vn[o] = a.V[(s * G_NY + o) * n + row];
-    const bool sample_dead = !(pw_row_finite(zrow, (long)G_NY * stride_o, lane) && pw_row_finite(a.V + s * G_NY * n, (long)G_NY * n, lane));
+    PwSampleFrame<G_NY> f;
+    pw_sample_frame(f, a.gp, a.X_r, a.Z, a.ldz, a.V, a.M, s, lane);
 
 #pragma unroll 1
     for (long b = b0; b < b1; ++b) {
@@ -198,7 +124,7 @@ __global__ __launch_bounds__(256) void pathwise_rollout_cand_vjp_kernel(const Pw
         const double* us = a.U + b * H * NU;                             // (never read when H == 0)
         const double* ys = a.Y ? a.Y + p * G_NY * H * (1 + D) : nullptr;
 
-        bool dead = sample_dead || !(pw_row_finite(a.x0 + (a.x0_per ? b * NX : 0), NX, lane) && pw_row_finite(xs, (long)NX * (H + 1), lane));
+        bool dead = f.dead || !(pw_row_finite(a.x0 + (a.x0_per ? b * NX : 0), NX, lane) && pw_row_finite(xs, (long)NX * (H + 1), lane));
         if (H > 0) dead = dead || !pw_row_finite(us, (long)H * NU, lane);
         if (gxs) dead = dead || !pw_row_finite(gxs, (long)NX * (H + 1), lane);
         if (ys) dead = dead || !pw_row_finite(ys, (long)G_NY * H * (1 + D), lane);
@@ -236,8 +162,8 @@ __global__ __launch_bounds__(256) void pathwise_rollout_cand_vjp_kernel(const Pw
 #pragma unroll
                 for (int k = 0; k < 1 + D; ++k) y[o][k] = yq[o][k];
             if (t > 0) load_step(t - 1);
-            const bool fin = pw_cand_adjoint_step<ENV>(gp, env, a.omega, zrow, F, stride_o, lane, has_row, xr, vn, x, ut, ys != nullptr, y,
-                                                       gxs != nullptr, gxt, lam, gu);
+            const bool fin = pw_adjoint_step<ENV>(a.gp, a.env, a.omega, f.zrow, f.F, f.stride_o, lane, f.has_row, f.xr, f.vn, x, ut,
+                                                  ys != nullptr, y, gxs != nullptr, gxt, lam, gu);
             if (!fin) dead = true;
             double mine = gu[0];                                        // lane i stores input dimension i
 #pragma unroll
@@ -274,15 +200,6 @@ static int pw_cand_check_env(const std::string& me, const gpmpc_gp_desc_t* gp, c
     return GPMPC_OK;
 }
 
-static void pw_cand_fill(PwCandArgs& a, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M,
-                         const double* omega, int64_t Ns, int64_t B, int32_t H, const double* x0, int32_t x0_per_candidate, const double* U,
-                         const double* Z, int64_t ldz, const double* V, int32_t* info) {
-    a = PwCandArgs{};
-    a.gp = make_gp_params(gp), a.env = make_env_params(env);
-    a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.info = (int*)info;
-    a.Ns = Ns, a.B = B, a.ldz = ldz, a.sblocks = (Ns + 3) / 4, a.M = M, a.H = H, a.x0_per = x0_per_candidate != 0;
-}
-
 template <class Launch>
 static int pw_cand_launch(const PwCandArgs& a, int env_id, Launch&& launch) {
     const long blocks = a.sblocks * ((a.B + PW_CB - 1) / PW_CB);          // < 2^30 for B Ns < 2^31: a linear grid, no 65535 cap
@@ -300,15 +217,13 @@ int gpmpc_pathwise_rollout_cand(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_
                                 const double* Z, int64_t ldz, const double* V, double* X_traj, double* Y, int32_t* info, void* stream) {
     const std::string me = "gpmpc_pathwise_rollout_cand: ";
     if (int rc = pw_cand_check(me, gp, env, M, Ns, B, ldz, H)) return rc;
-    // an empty batch reads and writes nothing: its (empty) arrays may have no address at all
     const bool work = Ns > 0 && B > 0;
-    if (work && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && !U)))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj and info are required)");
+    if (int rc = pw_null_check(me, work, H, {X_r, omega, x0, Z, V, X_traj, info}, {U}, "X_r, omega, x0, U, Z, V, X_traj and info")) return rc;
     if (int rc = pw_cand_check_env(me, gp, env, M, Ns, B)) return rc;
     if (!work) return GPMPC_OK;
     PwCandArgs a;
-    pw_cand_fill(a, gp, env, X_r, M, omega, Ns, B, H, x0, x0_per_candidate, U, Z, ldz, V, info);
-    a.X_out = X_traj, a.Y_out = Y;
+    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_candidate, U, Z, ldz, V, info);
+    a.B = B, a.sblocks = (Ns + 3) / 4, a.X_out = X_traj, a.Y_out = Y;
     return pw_cand_launch(a, env->env_id, [&](auto e, dim3 grid, dim3 block) {
         hipLaunchKernelGGL(pathwise_rollout_cand_kernel<decltype(e)::value>, grid, block, 0, (hipStream_t)stream, a);
     });
@@ -321,13 +236,12 @@ int gpmpc_pathwise_rollout_cand_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_d
     const std::string me = "gpmpc_pathwise_rollout_cand_vjp: ";
     if (int rc = pw_cand_check(me, gp, env, M, Ns, B, ldz, H)) return rc;
     const bool work = Ns > 0 && B > 0;
-    if (work && (!X_r || !omega || !x0 || !Z || !V || !X_traj || !info || (H > 0 && (!U || !gU))))
-        return fail(GPMPC_E_ARG, me + "NULL pointer (X_r, omega, x0, U, Z, V, X_traj, gU and info are required)");
+    if (int rc = pw_null_check(me, work, H, {X_r, omega, x0, Z, V, X_traj, info}, {U, gU}, "X_r, omega, x0, U, Z, V, X_traj, gU and info")) return rc;
     if (int rc = pw_cand_check_env(me, gp, env, M, Ns, B)) return rc;
     if (!work) return GPMPC_OK;
     PwCandArgs a;
-    pw_cand_fill(a, gp, env, X_r, M, omega, Ns, B, H, x0, x0_per_candidate, U, Z, ldz, V, info);
-    a.X_traj = X_traj, a.Y = Y, a.gX = gX, a.gx0 = gx0, a.gU = gU;
+    pw_fill_args(a, gp, env, X_r, M, omega, Ns, H, x0, x0_per_candidate, U, Z, ldz, V, info);
+    a.B = B, a.sblocks = (Ns + 3) / 4, a.X_traj = X_traj, a.Y = Y, a.gX = gX, a.gx0 = gx0, a.gU = gU;
     return pw_cand_launch(a, env->env_id, [&](auto e, dim3 grid, dim3 block) {
         hipLaunchKernelGGL(pathwise_rollout_cand_vjp_kernel<decltype(e)::value>, grid, block, 0, (hipStream_t)stream, a);
     });

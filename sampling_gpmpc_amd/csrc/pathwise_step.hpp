@@ -1,8 +1,9 @@
 // The device code of the pathwise GP samples that more than one kernel runs, defined once: the evaluation of a sample at a point, the
 // fit of one output's update vector and one step of the rollout.  pathwise_fit_kernel / pathwise_eval_kernel / pathwise_rollout_kernel
 // (pathwise.hip) and pathwise_tube_stats_kernel (pathwise_stats.hip) call the functions below, so the fused kernel's update vectors
-// and trajectories have the bits of the unfused path by construction.  The limits and the argument checks the entry points share
-// live here too.
+// and trajectories have the bits of the unfused path by construction.  The adjoint of a step (pw_adjoint_step) and what a wave holds
+// of its sample (pw_sample_frame) are here as well: the VJP of the sample kernels (pathwise_grad.hip) and that of the candidate kernels
+// (pathwise_cand.hip) call the same two.  The limits and the argument checks the entry points share live here too.
 #pragma once
 #include "moments_step.hpp"
 
@@ -220,6 +221,173 @@ __device__ __forceinline__ void pw_rollout_step(const GpParams& gp, const EnvPar
     for (int d = 0; d < NX; ++d) x[d] = dead ? nan : xn[d];
 }
 
+// The adjoint of one step (uniform over the wave): gu = B_t^T lam and lam <- A_t^T lam + gxt at the point rebuilt from x = x_t and
+// ut = U[t] with the statements of pw_rollout_step (restated, not shared: DESIGN 4.13d), so Y is the sample at exactly this point.
+// y: the forward's Y[:, t], read when have_y, else the sample is evaluated again with the forward's function.  False when anything
+// is not finite.
+template <int ENV>
+__device__ __forceinline__ bool pw_adjoint_step(const GpParams& gp, const EnvParams& env, const double* omega, const double* zrow, int F,
+                                                int stride_o, int lane, bool has_row, const double (&xr)[2],
+                                                const double (&vn)[EnvDims<ENV>::G_NY], const double (&x)[EnvDims<ENV>::NX],
+                                                const double (&ut)[EnvDims<ENV>::NU], bool have_y,
+                                                const double (&y)[EnvDims<ENV>::G_NY][3], bool have_gx,
+                                                const double (&gxt)[EnvDims<ENV>::NX], double (&lam)[EnvDims<ENV>::NX],
+                                                double (&gu)[EnvDims<ENV>::NU]) {
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
+    constexpr int D = 2;
+    double u[NU], xi[D], g[G_NY], gg[G_NY][D];
+    bool fin = true;
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+        const double ufi = ut[i];
+        if (env.use_feedback) {                                         // uniform
+            double acc = 0.0;
+#pragma unroll
+            for (int j = 0; j < NX; ++j) acc += (env.x_goal[j] - x[j]) * env.K[i][j];
+            u[i] = -acc + ufi;
+        } else {
+            u[i] = ufi;
+        }
+        fin = fin && pw_finite(u[i]);
+    }
+    xi[0] = x[EnvDims<ENV>::SEL];
+    xi[1] = u[0];
+#pragma unroll
+    for (int o = 0; o < G_NY; ++o) {
+        if (have_y) {                                                   // uniform
+            g[o] = y[o][0], gg[o][0] = y[o][1], gg[o][1] = y[o][2];
+        } else {
+            pw_eval_point<D, true>(omega + (long)o * F * D, zrow + (long)o * stride_o, F, lane, sqrt(gp.os[o] / (double)F), gp.os[o],
+                                   gp.inv_l2[o], has_row, xr, vn[o], xi, g[o], gg[o]);
+        }
+        fin = fin && pw_finite(g[o]) && pw_finite(gg[o][0]) && pw_finite(gg[o][1]);
+    }
+    double dxi[D][NX], A[NX][NX], B[NX][NU];
+    env_jacobian_ct<ENV>(env, x, g, gg, dxi, A);
+    env_input_jacobian_ct<ENV>(env, x, gg, B);
+    double ln[NX];
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {                                       // gU[t] = B_t^T lam, rows in ascending order
+        double acc = B[0][i] * lam[0];
+#pragma unroll
+        for (int r = 1; r < NX; ++r) acc = fma(B[r][i], lam[r], acc);
+        gu[i] = acc;
+        fin = fin && pw_finite(acc);
+    }
+#pragma unroll
+    for (int c = 0; c < NX; ++c) {                                       // lam = A_t^T lam + gX[:, t]
+        double acc = A[0][c] * lam[0];
+#pragma unroll
+        for (int r = 1; r < NX; ++r) acc = fma(A[r][c], lam[r], acc);
+        if (have_gx) acc += gxt[c];
+        ln[c] = acc;
+        fin = fin && pw_finite(acc);
+    }
+#pragma unroll
+    for (int c = 0; c < NX; ++c) lam[c] = ln[c];
+    return fin;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rollout: what a wave holds of its sample (both VJP kernels), and the backward sweep of one (inputs, sample) pair through all H
+// steps (pathwise_rollout_vjp_kernel).  The glue of a pair around pw_rollout_step / pw_adjoint_step is NOT one function for
+// the sample and the candidate kernels: DESIGN 4.13d has what was measured.
+// ---------------------------------------------------------------------------------------------------------------------
+template <int G_NY>
+struct PwSampleFrame {
+    const double* zrow;                                                 // the sample's normals
+    double xr[2], vn[G_NY];                                             // this lane's training row and the sample's update weights at it
+    int F, stride_o;
+    bool has_row, dead;                                                 // dead: the sample's row of Z or of V is not finite
+};
+
+template <int G_NY>
+__device__ __forceinline__ void pw_sample_frame(PwSampleFrame<G_NY>& f, const GpParams& gp, const double* X_r, const double* Z, long ldz,
+                                                const double* V, int M, long s, int lane) {
+    const int n = gp.N_r;                                               // n <= 64 (host)
+    f.F = M / 2, f.stride_o = M + n;
+    f.zrow = Z + s * ldz;
+    f.has_row = lane < n;
+    const int row = f.has_row ? lane : n - 1;
+    f.xr[0] = X_r[(long)row * 2], f.xr[1] = X_r[(long)row * 2 + 1];
+#pragma unroll
+    for (int o = 0; o < G_NY; ++o) f.vn[o] = V[(s * G_NY + o) * n + row];
+    f.dead = !(pw_row_finite(f.zrow, (long)G_NY * f.stride_o, lane) && pw_row_finite(V + s * G_NY * n, (long)G_NY * n, lane));
+}
+
+// Backward: xs [NX][H+1] is the pair's trajectory, ys its Y (or NULL: evaluated again), gxs its cotangent (or NULL: zero); gU [H][NU],
+// gx0 [NX] (or NULL) and info are the outputs and p the pair's row in them.
+template <int ENV>
+__device__ __forceinline__ void pw_backward_pair(const GpParams& gp, const EnvParams& env, const double* omega,
+                                                 const PwSampleFrame<EnvDims<ENV>::G_NY>& f, int lane, int H, const double* x0,
+                                                 const double* us, const double* xs, const double* ys, const double* gxs, long p,
+                                                 double* gx0, double* gU, int* info) {
+    constexpr int NX = EnvDims<ENV>::NX, NU = EnvDims<ENV>::NU, G_NY = EnvDims<ENV>::G_NY;
+    constexpr int D = 2;
+    const double nan = __builtin_nan("");
+    bool dead = f.dead || !(pw_row_finite(x0, NX, lane) && pw_row_finite(xs, (long)NX * (H + 1), lane));
+    if (H > 0) dead = dead || !pw_row_finite(us, (long)H * NU, lane);
+    if (gxs) dead = dead || !pw_row_finite(gxs, (long)NX * (H + 1), lane);
+    if (ys) dead = dead || !pw_row_finite(ys, (long)G_NY * H * (1 + D), lane);
+
+    double lam[NX];
+#pragma unroll
+    for (int d = 0; d < NX; ++d) lam[d] = gxs ? gxs[d * (H + 1) + H] : 0.0;
+
+    // The loads of a step - x_t, U[t], gX[:, t] and (given) Y[:, t] - do not depend on the recursion: they are issued one step ahead, so
+    // their latency runs under the evaluation of the step before and not in front of every step's sincos
+    double xq[NX], uq[NU], gq[NX], yq[G_NY][1 + D];
+    auto load_step = [&](int t) {
+#pragma unroll
+        for (int d = 0; d < NX; ++d) {
+            xq[d] = xs[d * (H + 1) + t];
+            gq[d] = gxs ? gxs[d * (H + 1) + t] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < NU; ++i) uq[i] = us[t * NU + i];
+#pragma unroll
+        for (int o = 0; o < G_NY; ++o)
+#pragma unroll
+            for (int k = 0; k < 1 + D; ++k) yq[o][k] = ys ? ys[(o * H + t) * (1 + D) + k] : 0.0;
+    };
+    if (H > 0) load_step(H - 1);
+
+#pragma unroll 1
+    for (int t = H - 1; t >= 0; --t) {
+        double x[NX], ut[NU], gxt[NX], y[G_NY][1 + D], gu[NU];
+#pragma unroll
+        for (int d = 0; d < NX; ++d) x[d] = xq[d], gxt[d] = gq[d];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) ut[i] = uq[i];
+#pragma unroll
+        for (int o = 0; o < G_NY; ++o)
+#pragma unroll
+            for (int k = 0; k < 1 + D; ++k) y[o][k] = yq[o][k];
+        if (t > 0) load_step(t - 1);
+        if (!pw_adjoint_step<ENV>(gp, env, omega, f.zrow, f.F, f.stride_o, lane, f.has_row, f.xr, f.vn, x, ut, ys != nullptr, y,
+                                  gxs != nullptr, gxt, lam, gu))
+            dead = true;
+        double mine = gu[0];                                            // lane i stores input dimension i
+#pragma unroll
+        for (int i = 1; i < NU; ++i)
+            if (lane == i) mine = gu[i];
+        if (lane < NU) gU[(p * H + t) * NU + lane] = dead ? nan : mine;
+    }
+    if (dead) {                              // (wave-uniform) all of the pair's gradients are NaN: the lane that wrote an entry writes it again
+#pragma unroll 1
+        for (int t = 0; t < H; ++t)
+            if (lane < NU) gU[(p * H + t) * NU + lane] = nan;
+    }
+    if (gx0) {
+        double mine = lam[0];                                           // lane d stores state dimension d
+#pragma unroll
+        for (int d = 1; d < NX; ++d)
+            if (lane == d) mine = lam[d];
+        if (lane < NX) gx0[p * NX + lane] = dead ? nan : mine;
+    }
+    if (lane == 0) info[p] = dead ? GPMPC_INFO_NONFINITE : 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host: the checks the entry points share; `me` names the entry point in the message
 // ---------------------------------------------------------------------------------------------------------------------
@@ -258,14 +426,25 @@ inline int pw_rollout_check_env(const std::string& me, const gpmpc_gp_desc_t* gp
     return pw_supported(me, gp, M, Ns);
 }
 
-// the fields PwRollArgs and PwGradArgs share (each keeps its own layout)
+// The NULL-pointer test between the two, of the four rollout entry points: an empty batch (`work` false) reads and writes nothing, so
+// its (empty) arrays may have no address at all; else every pointer of `required` must be set, those of `with_steps` when H > 0
+inline int pw_null_check(const std::string& me, bool work, int32_t H, std::initializer_list<const void*> required,
+                         std::initializer_list<const void*> with_steps, const char* names) {
+    bool ok = true;
+    for (const void* p : required) ok = ok && p;
+    for (const void* p : with_steps) ok = ok && (H <= 0 || p);
+    return work && !ok ? fail(GPMPC_E_ARG, me + "NULL pointer (" + names + " are required)") : GPMPC_OK;
+}
+
+// the fields PwRollArgs, PwGradArgs and PwCandArgs share (each keeps its own layout; what is not set here is zero)
 template <class Args>
 void pw_fill_args(Args& a, const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const double* X_r, int32_t M, const double* omega,
-                  int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample, const double* U, int32_t u_per_sample, const double* Z,
-                  int64_t ldz, const double* V, int32_t* info) {
+                  int64_t Ns, int32_t H, const double* x0, int32_t x0_per, const double* U, const double* Z, int64_t ldz, const double* V,
+                  int32_t* info) {
+    a = Args{};
     a.gp = make_gp_params(gp), a.env = make_env_params(env);
     a.X_r = X_r, a.omega = omega, a.x0 = x0, a.U = U, a.Z = Z, a.V = V, a.info = (int*)info;
-    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per_sample != 0, a.u_per = u_per_sample != 0;
+    a.Ns = Ns, a.ldz = ldz, a.M = M, a.H = H, a.x0_per = x0_per != 0;
 }
 
 // launch(env) with the environment as an integral constant (as mom_dispatch), then the launch's status

@@ -204,24 +204,13 @@ class PathwiseSamples:
         dev = _lib.require_hip_device(self.Z.device)
         env_desc = self._env_desc(use_feedback, env_desc)
         x0, U = rollout_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev, n=self.Ns)
-        X, Y, info = (_PathwiseRollout.apply(x0, U, self, env_desc, bool(want_samples)) if differentiable
-                      else self._launch_rollout(x0, U, env_desc, want_samples))
+        return self._rollout(x0, U, env_desc, want_samples, differentiable, False)
+
+    def _rollout(self, x0, U, env_desc, want_samples, differentiable, cand):
+        X, Y, info = (_PathwiseRollout.apply(x0, U, self, env_desc, bool(want_samples), cand) if differentiable
+                      else _launch_rollout(self, x0, U, env_desc, want_samples, cand))
         self.last_info = info
         return (X, Y) if want_samples else X
-
-    def _launch_rollout(self, x0, U, env_desc, want_samples):
-        """One launch of ``gpmpc_pathwise_rollout`` for inputs ``rollout_inputs`` has prepared: ``(X_traj, Y or None, info)``."""
-        lib = _lib.load()
-        dev, d = self.Z.device, self.plan.desc
-        nx, H = int(env_desc.nx), int(U.shape[-2])
-        X = torch.empty(self.Ns, nx, H + 1, dtype=F64, device=dev)
-        Y = torch.empty(self.Ns, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
-        info = torch.zeros(self.Ns, dtype=torch.int32, device=dev)
-        _lib.check(lib.gpmpc_pathwise_rollout(d, env_desc, _lib.dptr(self.plan.X_r), self.n_features, _lib.dptr(self.omega), self.Ns, H,
-                                              _lib.dptr(x0), int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), self.Z.data_ptr(),
-                                              self._ldz(), _lib.dptr(self.V), _lib.dptr(X), _lib.dptr(Y), _lib.dptr(info),
-                                              _lib.current_stream_ptr()), "gpmpc_pathwise_rollout")
-        return X, Y, info
 
     def rollout_candidates(self, x0, U, use_feedback: Optional[bool] = None, want_samples: bool = False, env_desc=None,
                            differentiable: bool = False):
@@ -235,10 +224,7 @@ class PathwiseSamples:
         dev = _lib.require_hip_device(self.Z.device)
         env_desc = self._env_desc(use_feedback, env_desc)
         x0, U = _cand_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev)
-        X, Y, info = (_PathwiseRolloutCand.apply(x0, U, self, env_desc, bool(want_samples)) if differentiable
-                      else _launch_rollout_cand(self, x0, U, env_desc, want_samples))
-        self.last_info = info
-        return (X, Y) if want_samples else X
+        return self._rollout(x0, U, env_desc, want_samples, differentiable, True)
 
 
 def torch_evaluate(samples: PathwiseSamples, x: torch.Tensor) -> torch.Tensor:
@@ -307,36 +293,83 @@ def torch_rollout(samples: PathwiseSamples, x0: torch.Tensor, U: torch.Tensor, e
 # ---------------------------------------------------------------------------------------------------------------------
 # the reverse-mode gradient of the rollout and what it is for
 # ---------------------------------------------------------------------------------------------------------------------
-def _rollout_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
-    """One launch of ``gpmpc_pathwise_rollout_vjp``: per-sample gradients ``(g_x0 (Ns, nx), g_U (Ns, H, nu), info (Ns))``."""
+def _launch_rollout(samples: PathwiseSamples, x0, U, env_desc, want_samples, cand: bool):
+    """One forward launch: ``(X_traj, Y or None, info)``.  ``cand`` False: ``gpmpc_pathwise_rollout`` for inputs ``rollout_inputs`` has
+    prepared, one pair per sample and every output with the leading shape ``(Ns,)``; True: ``gpmpc_pathwise_rollout_cand`` for those of
+    ``_cand_inputs``, one pair per candidate and sample, ``(B, Ns)``."""
     lib = _lib.load()
-    dev = samples.Z.device
-    d = samples.plan.desc
+    dev, d = samples.Z.device, samples.plan.desc
+    Ns, nx, H = samples.Ns, int(env_desc.nx), int(U.shape[-2])
+    lead = (int(U.shape[0]), Ns) if cand else (Ns,)                      # (sizes are passed unpacked: a shape tuple costs 0.8 us more)
+    X = torch.empty(*lead, nx, H + 1, dtype=F64, device=dev)
+    Y = torch.empty(*lead, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
+    info = torch.zeros(*lead, dtype=torch.int32, device=dev)
+    if cand:
+        rc, name = lib.gpmpc_pathwise_rollout_cand(
+            d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, lead[0], H, _lib.dptr(x0),
+            int(x0.dim() == 2), _lib.dptr(U), samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X), _lib.dptr(Y),
+            _lib.dptr(info), _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_cand"
+    else:
+        rc, name = lib.gpmpc_pathwise_rollout(
+            d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, H, _lib.dptr(x0),
+            int(x0.dim() == 2), _lib.dptr(U), int(U.dim() == 3), samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X),
+            _lib.dptr(Y), _lib.dptr(info), _lib.current_stream_ptr()), "gpmpc_pathwise_rollout"
+    _lib.check(rc, name)
+    return X, Y, info
+
+
+def _rollout_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X, cand: bool = False):
+    """One launch of the VJP of ``_launch_rollout``'s forward: the gradients per pair ``(g_x0 (..., nx), g_U (..., H, nu), info (...))``,
+    ``...`` the leading shape ``(Ns,)`` or ``(B, Ns)``."""
+    lib = _lib.load()
+    dev, d = samples.Z.device, samples.plan.desc
     Ns, nx, nu, H = samples.Ns, int(env_desc.nx), int(env_desc.nu), int(U.shape[-2])
-    for name, t, shape in (("X_traj", X_traj, (Ns, nx, H + 1)), ("g_X", g_X, (Ns, nx, H + 1)), ("Y", Y, (Ns, d.g_ny, H, 1 + d.D))):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
+    lead = (int(U.shape[0]), Ns) if cand else (Ns,)
+    for name, t, shape in (("X_traj", X_traj, lead + (nx, H + 1)), ("g_X", g_X, lead + (nx, H + 1)), ("Y", Y, lead + (d.g_ny, H, 1 + d.D))):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
             raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
     X_traj = X_traj.detach().contiguous()
     Y = None if Y is None else Y.detach().contiguous()
     g_X = None if g_X is None else g_X.detach().contiguous()
-    g_x0 = torch.empty(Ns, nx, dtype=F64, device=dev)
-    g_U = torch.empty(Ns, H, nu, dtype=F64, device=dev)
-    info = torch.zeros(Ns, dtype=torch.int32, device=dev)
-    _lib.check(lib.gpmpc_pathwise_rollout_vjp(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, H,
-                                              _lib.dptr(x0.detach()), int(x0.dim() == 2), _lib.dptr(U.detach()), int(U.dim() == 3),
-                                              samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X_traj), _lib.dptr(Y),
-                                              _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info), _lib.current_stream_ptr()),
-               "gpmpc_pathwise_rollout_vjp")
+    g_x0 = torch.empty(*lead, nx, dtype=F64, device=dev)
+    g_U = torch.empty(*lead, H, nu, dtype=F64, device=dev)
+    info = torch.zeros(*lead, dtype=torch.int32, device=dev)
+    if cand:
+        rc, name = lib.gpmpc_pathwise_rollout_cand_vjp(
+            d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, lead[0], H, _lib.dptr(x0.detach()),
+            int(x0.dim() == 2), _lib.dptr(U.detach()), samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X_traj),
+            _lib.dptr(Y), _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info), _lib.current_stream_ptr()), \
+            "gpmpc_pathwise_rollout_cand_vjp"
+    else:
+        rc, name = lib.gpmpc_pathwise_rollout_vjp(
+            d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, H, _lib.dptr(x0.detach()),
+            int(x0.dim() == 2), _lib.dptr(U.detach()), int(U.dim() == 3), samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V),
+            _lib.dptr(X_traj), _lib.dptr(Y), _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info),
+            _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_vjp"
+    _lib.check(rc, name)
     return g_x0, g_U, info
 
 
+def _rollout_cand_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
+    return _rollout_backward(samples, env_desc, x0, U, X_traj, Y, g_X, True)
+
+
+def _reduce(g_x0, g_U, x0, U, cand: bool, need=(True, True)):
+    """The per-pair gradients as gradients of the inputs ``(x0, U)``; ``None`` where ``need`` says the input takes none.  Samples: summed
+    where the input was shared.  Candidates: the host's sums over the samples, ``g_U (B, H, nu)``, and ``g_x0 (B, nx)`` or - for a
+    shared ``x0`` - ``(nx,)``."""
+    if cand:
+        return ((g_x0.sum(1) if x0.dim() == 2 else g_x0.sum((0, 1))) if need[0] else None), (g_U.sum(1) if need[1] else None)
+    return (like_input(g_x0, x0.dim() == 2) if need[0] else None), (like_input(g_U, U.dim() == 3) if need[1] else None)
+
+
 class _PathwiseRollout(torch.autograd.Function):
-    """``gpmpc_pathwise_rollout`` with ``gpmpc_pathwise_rollout_vjp`` as its backward; ``Y`` and ``info`` carry no gradient."""
+    """``_launch_rollout`` with ``_rollout_backward`` as its backward, in either form; ``Y`` and ``info`` carry no gradient."""
 
     @staticmethod
-    def forward(ctx, x0, U, samples, env_desc, want_samples):
-        X, Y, info = samples._launch_rollout(x0, U, env_desc, want_samples)
-        ctx.samples, ctx.env_desc, ctx.has_y = samples, env_desc, Y is not None
+    def forward(ctx, x0, U, samples, env_desc, want_samples, cand):
+        X, Y, info = _launch_rollout(samples, x0, U, env_desc, want_samples, cand)
+        ctx.samples, ctx.env_desc, ctx.has_y, ctx.cand = samples, env_desc, Y is not None, cand
         ctx.save_for_backward(x0, U, X, *(() if Y is None else (Y,)))
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(*(t for t in (Y, info) if t is not None))
@@ -345,13 +378,11 @@ class _PathwiseRollout(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_X, *_):
         if g_X is None:
-            return (None,) * 5
+            return (None,) * 6
         x0, U, X = ctx.saved_tensors[:3]
         Y = ctx.saved_tensors[3] if ctx.has_y else None
-        g_x0, g_U, _ = _rollout_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X)
-        need = ctx.needs_input_grad
-        return (like_input(g_x0, x0.dim() == 2) if need[0] else None, like_input(g_U, U.dim() == 3) if need[1] else None,
-                None, None, None)
+        g_x0, g_U, _ = _rollout_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X, ctx.cand)
+        return (*_reduce(g_x0, g_U, x0, U, ctx.cand, ctx.needs_input_grad), None, None, None, None)
 
 
 def pathwise_rollout_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, use_feedback: Optional[bool] = None, env_desc=None):
@@ -366,7 +397,7 @@ def pathwise_rollout_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, u
     if not torch.is_tensor(X_traj):
         raise _lib.GpmpcError("X_traj must be the tensor samples.rollout returned")
     g_x0, g_U, info = _rollout_backward(samples, env_desc, x0, U, X_traj, Y, g_X)
-    return like_input(g_x0, x0.dim() == 2), like_input(g_U, U.dim() == 3), info
+    return (*_reduce(g_x0, g_U, x0, U, False), info)
 
 
 def sampled_tube_penalty(X_traj: torch.Tensor, rows) -> torch.Tensor:
@@ -439,75 +470,6 @@ def _cand_inputs(x0, U, nx: int, nu: int, dev):
     return rollout_inputs(x0, U, nx, nu, dev, n=int(U.shape[0]))
 
 
-def _launch_rollout_cand(samples: PathwiseSamples, x0, U, env_desc, want_samples):
-    """One launch of ``gpmpc_pathwise_rollout_cand`` for inputs ``_cand_inputs`` has prepared: ``(X_traj, Y or None, info)``."""
-    lib = _lib.load()
-    dev, d = samples.Z.device, samples.plan.desc
-    Ns, B, nx, H = samples.Ns, int(U.shape[0]), int(env_desc.nx), int(U.shape[1])
-    X = torch.empty(B, Ns, nx, H + 1, dtype=F64, device=dev)
-    Y = torch.empty(B, Ns, d.g_ny, H, 1 + d.D, dtype=F64, device=dev) if want_samples else None
-    info = torch.zeros(B, Ns, dtype=torch.int32, device=dev)
-    _lib.check(lib.gpmpc_pathwise_rollout_cand(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns, B,
-                                               H, _lib.dptr(x0), int(x0.dim() == 2), _lib.dptr(U), samples.Z.data_ptr(), samples._ldz(),
-                                               _lib.dptr(samples.V), _lib.dptr(X), _lib.dptr(Y), _lib.dptr(info),
-                                               _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_cand")
-    return X, Y, info
-
-
-def _rollout_cand_backward(samples: PathwiseSamples, env_desc, x0, U, X_traj, Y, g_X):
-    """One launch of ``gpmpc_pathwise_rollout_cand_vjp``: the gradients per (candidate, sample) ``(g_x0 (B, Ns, nx), g_U (B, Ns, H, nu),
-    info (B, Ns))``."""
-    lib = _lib.load()
-    dev = samples.Z.device
-    d = samples.plan.desc
-    Ns, B, nx, nu, H = samples.Ns, int(U.shape[0]), int(env_desc.nx), int(env_desc.nu), int(U.shape[1])
-    for name, t, shape in (("X_traj", X_traj, (B, Ns, nx, H + 1)), ("g_X", g_X, (B, Ns, nx, H + 1)),
-                           ("Y", Y, (B, Ns, d.g_ny, H, 1 + d.D))):
-        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != F64 or t.device != dev):
-            raise _lib.GpmpcError(f"{name} must be a float64 tensor {shape} on {dev}")
-    X_traj = X_traj.detach().contiguous()
-    Y = None if Y is None else Y.detach().contiguous()
-    g_X = None if g_X is None else g_X.detach().contiguous()
-    g_x0 = torch.empty(B, Ns, nx, dtype=F64, device=dev)
-    g_U = torch.empty(B, Ns, H, nu, dtype=F64, device=dev)
-    info = torch.zeros(B, Ns, dtype=torch.int32, device=dev)
-    _lib.check(lib.gpmpc_pathwise_rollout_cand_vjp(d, env_desc, _lib.dptr(samples.plan.X_r), samples.n_features, _lib.dptr(samples.omega), Ns,
-                                                   B, H, _lib.dptr(x0.detach()), int(x0.dim() == 2), _lib.dptr(U.detach()),
-                                                   samples.Z.data_ptr(), samples._ldz(), _lib.dptr(samples.V), _lib.dptr(X_traj),
-                                                   _lib.dptr(Y), _lib.dptr(g_X), _lib.dptr(g_x0), _lib.dptr(g_U), _lib.dptr(info),
-                                                   _lib.current_stream_ptr()), "gpmpc_pathwise_rollout_cand_vjp")
-    return g_x0, g_U, info
-
-
-def _sum_cand(g_x0, g_U, x0_per_candidate: bool):
-    """The host's sums over the samples: ``g_U (B, H, nu)``, and ``g_x0 (B, nx)`` or - for a shared ``x0`` - ``(nx,)``."""
-    return (g_x0.sum(1) if x0_per_candidate else g_x0.sum((0, 1))), g_U.sum(1)
-
-
-class _PathwiseRolloutCand(torch.autograd.Function):
-    """``gpmpc_pathwise_rollout_cand`` with ``gpmpc_pathwise_rollout_cand_vjp`` as its backward; ``Y`` and ``info`` carry no gradient."""
-
-    @staticmethod
-    def forward(ctx, x0, U, samples, env_desc, want_samples):
-        X, Y, info = _launch_rollout_cand(samples, x0, U, env_desc, want_samples)
-        ctx.samples, ctx.env_desc, ctx.has_y = samples, env_desc, Y is not None
-        ctx.save_for_backward(x0, U, X, *(() if Y is None else (Y,)))
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(*(t for t in (Y, info) if t is not None))
-        return X, Y, info
-
-    @staticmethod
-    def backward(ctx, g_X, *_):
-        if g_X is None:
-            return (None,) * 5
-        x0, U, X = ctx.saved_tensors[:3]
-        Y = ctx.saved_tensors[3] if ctx.has_y else None
-        g_x0, g_U, _ = _rollout_cand_backward(ctx.samples, ctx.env_desc, x0, U, X, Y, g_X)
-        g_x0, g_U = _sum_cand(g_x0, g_U, x0.dim() == 2)
-        need = ctx.needs_input_grad
-        return g_x0 if need[0] else None, g_U if need[1] else None, None, None, None
-
-
 def pathwise_rollout_cand_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=None, use_feedback: Optional[bool] = None, env_desc=None):
     """``gpmpc_pathwise_rollout_cand_vjp`` (include/gpmpc_hip.h): the gradients of ``sum(g_X * X_traj)`` with respect to the inputs the
     tubes ``X_traj = samples.rollout_candidates(x0, U)`` were computed from.  Returns ``(g_x0, g_U, info)``: ``g_U (B, H, nu)`` and
@@ -519,8 +481,8 @@ def pathwise_rollout_cand_vjp(samples: PathwiseSamples, X_traj, x0, U, g_X, Y=No
     x0, U = _cand_inputs(x0, U, int(env_desc.nx), int(env_desc.nu), dev)
     if not torch.is_tensor(X_traj):
         raise _lib.GpmpcError("X_traj must be the tensor samples.rollout_candidates returned")
-    g_x0, g_U, info = _rollout_cand_backward(samples, env_desc, x0, U, X_traj, Y, g_X)
-    return (*_sum_cand(g_x0, g_U, x0.dim() == 2), info)
+    g_x0, g_U, info = _rollout_backward(samples, env_desc, x0, U, X_traj, Y, g_X, True)
+    return (*_reduce(g_x0, g_U, x0, U, True), info)
 
 
 def plan_inputs_sampled_population(samples: PathwiseSamples, x0, U0, cost, steps: int, lr: float, use_feedback: Optional[bool] = None,

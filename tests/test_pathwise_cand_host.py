@@ -75,10 +75,21 @@ def test_header_and_sources_carry_the_declarations_and_the_contract():
         assert text in doc, text
     csrc = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
     src = open(os.path.join(csrc, "pathwise_cand.hip")).read()
-    assert '#include "pathwise_step.hpp"' in src and "pw_rollout_step<ENV>(" in src and "pw_eval_point<D, true>(" in src
-    assert "env_jacobian_ct<ENV>" in src and "env_input_jacobian_ct<ENV>" in src
+    step = open(os.path.join(csrc, "pathwise_step.hpp")).read()
+    body = lambda head: step[step.index(head):step.index("\n}\n", step.index(head))]        # a function of the header, to its closing brace
+    # the forward runs the shared step and the VJP the shared adjoint step on the shared sample frame - the functions of the sample
+    # kernels - and the evaluation and the Jacobians are found in those
+    assert '#include "pathwise_step.hpp"' in src and "pw_sample_frame(" in src
+    assert "pw_rollout_step<ENV>(" in src and "pw_adjoint_step<ENV>(" in src
+    grad = open(os.path.join(csrc, "pathwise_grad.hip")).read()
+    assert "pw_backward_pair<ENV>(" in grad and "pw_adjoint_step<ENV>(" in body("void pw_backward_pair(")
+    adjoint = body("bool pw_adjoint_step(")
+    assert "pw_eval_point<D, true>(" in body("void pw_rollout_step(") and "pw_eval_point<D, true>(" in adjoint
+    assert "env_jacobian_ct<ENV>" in adjoint and "env_input_jacobian_ct<ENV>" in adjoint
+    assert "adjoint_step(const" not in src and "pw_eval_point" not in src   # no adjoint step or evaluation of its own
     assert "pw_rollout_check(" in src and "pw_rollout_check_env(" in src
-    assert "atomicAdd" not in src and "__hip_atomic" not in src and "__atomic" not in src and "__shared__" not in src
+    for text in (src, step):                                            # the kernel file and everything it can call
+        assert "atomicAdd" not in text and "__hip_atomic" not in text and "__atomic" not in text and "__shared__" not in text
     assert '"pathwise_cand.hip"' in open(os.path.join(csrc, "build.py")).read()
     assert f"PW_CB = {cref.CB};" in src
 

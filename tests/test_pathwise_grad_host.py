@@ -84,13 +84,19 @@ def test_header_and_sources_carry_the_declaration_and_the_contract():
         assert text in doc, text
     csrc = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
     src = open(os.path.join(csrc, "pathwise_grad.hip")).read()
-    assert "pw_eval_point<D, true>" in src and "env_jacobian_ct<ENV>" in src and "env_input_jacobian_ct<ENV>" in src
-    assert "pw_rollout_check(" in src and "pw_rollout_check_env(" in src
     step = open(os.path.join(csrc, "pathwise_step.hpp")).read()
+    body = lambda head: step[step.index(head):step.index("\n}\n", step.index(head))]        # a function of the header, to its closing brace
+    # the kernel runs the shared backward pair, the pair the shared adjoint step, and that step the forward's evaluation and the Jacobians
+    assert "pw_backward_pair<ENV>(" in src and "pw_sample_frame(" in src and '#include "pathwise_step.hpp"' in src
+    pair, adjoint = body("void pw_backward_pair("), body("bool pw_adjoint_step(")
+    assert "pw_adjoint_step<ENV>(" in pair and "load_step(t - 1)" in pair
+    assert "pw_eval_point<D, true>" in adjoint and "env_jacobian_ct<ENV>" in adjoint and "env_input_jacobian_ct<ENV>" in adjoint
+    assert "pw_rollout_check(" in src and "pw_rollout_check_env(" in src
     first = step[step.index("inline int pw_rollout_check("):step.index("inline int pw_rollout_check_env(")]
     second = step[step.index("inline int pw_rollout_check_env("):step.index("void pw_fill_args(")]
     assert "pw_check(" in first and "pw_supported(" in second
-    assert "atomicAdd" not in src and "__hip_atomic" not in src and "__atomic" not in src and "__shared__" not in src
+    for text in (src, step):                                            # the kernel file and everything it can call
+        assert "atomicAdd" not in text and "__hip_atomic" not in text and "__atomic" not in text and "__shared__" not in text
     assert '"pathwise_grad.hip"' in open(os.path.join(csrc, "build.py")).read()
     assert "env_input_jacobian_ct" in open(os.path.join(csrc, "moments_step.hpp")).read()
 

@@ -72,7 +72,10 @@ def test_header_carries_the_declarations_the_citations_and_the_limits():
         assert text in doc, text
     src = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "pathwise.hip")).read()
     assert "PW_MAX_ROWS = 64" in src and "PW_MAX_M = 1024" in src
-    assert "atomicAdd" not in src and "__hip_atomic" not in src and "__atomic" not in src
+    step = open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "pathwise_step.hpp")).read()
+    assert "pw_rollout_step<ENV>(" in src
+    for text in (src, step):                                            # the kernel file and the shared functions it runs
+        assert "atomicAdd" not in text and "__hip_atomic" not in text and "__atomic" not in text
     assert '"pathwise.hip"' in open(os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "build.py")).read()
 
 
