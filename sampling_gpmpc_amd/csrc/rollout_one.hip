@@ -75,12 +75,13 @@ __device__ long long g_one_phase_cycles[16];
 __device__ double g_one_dbg[64 * 64];
 
 #ifdef GPMPC_PHASE_TIMERS
-#define OPH_DECL long long oph_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; long long opht_ = __builtin_readcyclecounter()
+#define OPH_DECL long long oph_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long opht_ = __builtin_readcyclecounter()
 #define OPH(i) do { const long long n_ = __builtin_readcyclecounter(); oph_[i] += n_ - opht_; opht_ = n_; } while (0)
 // (timers only - the ISA marks of tools/one_phase_mix.py stay eight) slot 8 -> [10]: the append's selects and the blocks' ends,
-// split off "append: diagonal tiles" ([6]), which is then the inline tile inverse and its write alone
+// split off "append: diagonal tiles" ([6]), which is then the inline tile inverse and its write alone; slot 9 -> [11]: the masked
+// moves of the step's selects, so that [10] is what stands behind them - the block's end and the join of the dispatch
 #define OPH_T(i) OPH(i)
-#define OPH_STORE do { if (blockIdx.x == 0 && threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) g_one_phase_cycles[i_] = oph_[i_]; g_one_phase_cycles[10] = oph_[8]; } } while (0)
+#define OPH_STORE do { if (blockIdx.x == 0 && threadIdx.x == 0) { for (int i_ = 0; i_ < 8; ++i_) g_one_phase_cycles[i_] = oph_[i_]; g_one_phase_cycles[10] = oph_[8]; g_one_phase_cycles[11] = oph_[9]; } } while (0)
 #elif defined(GPMPC_ONE_PHASE_MARKS)                              // tools/one_phase_mix.py: the phases' ends as comments in the ISA
 #define OPH_DECL
 #define OPH(i) asm volatile("; one_phase_end " #i)
@@ -461,6 +462,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     double* HSb = smem + OneLds::HS;
 
     // ---- per-lane constants ------------------------------------------------------------------------------------------
+    // The prologue ISSUES its global loads here (the *_ld values and qa / qb / x / zq / uq: every address is valid in every lane)
+    // and uses none of them before one_init below has written the 244 panel registers - those writes need the lane id alone and
+    // run while the plan's tables are in flight; the selects on the loaded values follow the statement that ends the wait.
     const double il0 = gp.inv_l2[0][0], il1 = gp.inv_l2[0][1], os = gp.os[0];
     // lane = real point (ga, gc) of the grid: columns of Qa / Qb, os / sqrt(D) and the whitened label of the point
     const int lr = (lane < NR) ? lane : 0, ga = lr / N1, gc = lr - ga * N1;
@@ -469,8 +473,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     for (int j = 0; j < N0; ++j) qa[j] = plan_grid_Qa(a.plan, gp, 0)[j * N0 + ga];
 #pragma unroll
     for (int j = 0; j < N1; ++j) qb[j] = plan_grid_Qb(a.plan, gp, 0)[j * N1 + gc];
-    const double dsc = (lane < NR) ? plan_grid_dsc(a.plan, gp, 0)[lr] : 0.0;
-    const double w_lane = (lane < NR) ? plan_grid_w(a.plan, gp, 0)[lr] : 0.0;
+    double dsc_ld = plan_grid_dsc(a.plan, gp, 0)[lr], w_ld = plan_grid_w(a.plan, gp, 0)[lr];
     // axis lanes: lane j < N0 holds axis-0 point j (real point N1 j), lane N0 + j axis-1 point j
     const bool g_ax0 = lane < N0;
     const int g_pt = g_ax0 ? lane * N1 : ((lane < N0 + N1) ? lane - N0 : 0);
@@ -478,7 +481,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     // of appended points are ever overwritten) and measures it against the GP input's own axis (g_sel0: coordinate 0) with
     // its axis' inverse length scale, the second term switched off by a zero scale; a point lane has both terms
     const bool g_axis = lane < N0 + N1, g_sel0 = g_ax0 || !g_axis;
-    const double g_x = a.X_r[g_pt * D + (g_ax0 ? 0 : 1)];
+    double g_x = a.X_r[g_pt * D + (g_ax0 ? 0 : 1)];
     const double il0_lane = g_axis ? (g_ax0 ? il0 : il1) : il0, il1_lane = g_axis ? 0.0 : il1;
     const int bp_addr = (lane & 15) << 2;                         // ds_bpermute address of "my lane of DPP row 0"
     // appended point j lives in lane kPt0 + j: behind the N0 + N1 axis lanes, so that ONE exponential per step serves both roles
@@ -501,10 +504,10 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     for (int d = 0; d < NX; ++d) x[d] = a.x0[(a.x0_per_sample ? s * NX : 0) + d];
     double xq[NX] = {0.0, 0.0};                                   // trajectory, one step per lane
     double zq[T], uq;
+    const int lz = (lane < H) ? lane : 0;                         // (H >= 2: step 0 exists; the lanes behind the horizon get zeros below)
 #pragma unroll
-    for (int c = 0; c < T; ++c) zq[c] = (lane < H) ? a.z[(long)lane * a.z_step_stride + s * T + c] : 0.0;
-    uq = (lane < H) ? a.u_ff[lane] : 0.0;
-    double xh[D] = {g_axis ? g_x : 0.0, 0.0}, yt[T] = {0.0, 0.0, 0.0};           // lane = appended point: its GP input and labels
+    for (int c = 0; c < T; ++c) zq[c] = a.z[(long)lz * a.z_step_stride + s * T + c];
+    uq = a.u_ff[lz];
     // the diagonal tiles of the group being appended to (one tile per block): L^T in the natural map and 1 / diag along its
     // rows / columns; the same for the next group (rows that wrap into it)
     double ud = Inat, drow = 1.0, dcol = 1.0, ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
@@ -520,6 +523,15 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
     ek.load();
     OnePanels P;
     one_init(P, Inat);
+    // the first use of the loaded values: the prologue's wait for its loads stands here, behind one_init
+    asm volatile("" : "+v"(qa[0]), "+v"(qa[1]), "+v"(qa[2]), "+v"(qa[3]), "+v"(qb[0]), "+v"(qb[1]), "+v"(qb[2]), "+v"(qb[3]), "+v"(qb[4]),
+                 "+v"(qb[5]), "+v"(qb[6]), "+v"(qb[7]), "+v"(qb[8]), "+v"(dsc_ld), "+v"(w_ld), "+v"(g_x), "+v"(x[0]), "+v"(x[1]),
+                 "+v"(zq[0]), "+v"(zq[1]), "+v"(zq[2]), "+v"(uq));
+    const double dsc = (lane < NR) ? dsc_ld : 0.0, w_lane = (lane < NR) ? w_ld : 0.0;
+#pragma unroll
+    for (int c = 0; c < T; ++c) zq[c] = (lane < H) ? zq[c] : 0.0;
+    uq = (lane < H) ? uq : 0.0;
+    double xh[D] = {g_axis ? g_x : 0.0, 0.0}, yt[T] = {0.0, 0.0, 0.0};           // lane = appended point: its GP input and labels
     OPH_DECL;
 #ifdef GPMPC_PHASE_TIMERS
     if (blockIdx.x == 0 && threadIdx.x == 0) g_one_phase_cycles[8] = opht_ - opk0_;
@@ -877,6 +889,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 ud = one_apply<OnePatDiag<lo>>(ud, sv);
                 drow = one_apply<OnePatInvRow<lo>>(drow, sv);
                 dcol = one_apply<OnePatInvCol<lo>>(dcol, sv);
+                OPH_T(9);
                 if constexpr (K < KLAST && lo + 3 > 16) {         // (once per epoch) rows wrapped into group K + 1: its first diagonal tile
                     ud1 = one_apply<OnePatDiag<lo - 16>>(ud1, sv);            // (all of its columns are new: no old value)
                     drow1 = one_apply<OnePatInvRow<lo - 16>>(drow1, sv);

@@ -20,14 +20,18 @@ for (ns, h) in CASES:
         names = ["entries: lds reads", "entries: vr+writes", "solve", "gram+1st extract", "sample+next exp", "append sets", "append diag", "state"]
         # ([10]: the append's selects and the blocks' ends, split off "append diag" by a mark of the timers' build - what is left
         # there is the inline tile inverse, its write and the copies behind the dispatch)
-        names.append("append selects"); vals = list(out[:8]) + [out[10]]
+        # ([11]: the masked moves of the selects alone; [10] is then what stands behind them in the block and at the join)
+        names += ["append masked moves", "append ends + join"]; vals = list(out[:8]) + [out[11], out[10]]
         tot = sum(vals)
         print("   total cycles", tot, "per step", tot // h)
         for n, v in zip(names, vals): print(f"   {n:18s} {v:9d} {v // h:7d}/step {100.0 * v / max(tot, 1):5.1f}%%")
         print(f"   prologue (kernel entry -> step loop) {out[8]} cycles, whole kernel of wave 0 {out[9]} cycles (the step loop {tot})")
 '''
 cases = [(1024, 30), (1024, 15), (2048, 30), (256, 30)]
-for mode in ("1", "0"):
+modes = ("1", "0")
+if "--headline" in sys.argv:                                     # the headline case through rollout_one_kernel alone
+    cases, modes = cases[:1], ("1",)
+for mode in modes:
     env = dict(os.environ, GPMPC_ROLLOUT_ONE=mode)
     print("== GPMPC_ROLLOUT_ONE=%s" % mode, flush=True)
     subprocess.run([sys.executable, "-c", code.replace("CASES", repr(cases)) % (TOOLS, TOOLS)], env=env)
