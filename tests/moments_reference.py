@@ -358,6 +358,16 @@ CASES = {
 }
 SHIPPED = ("pend_nofb", "pend_fb", "car_nofb", "car_fb", "pend_full", "car_full", "pend_p0", "car_p0")
 RAW = ("raw7", "raw17", "raw33", "grad5", "grad5_pend")
+# training sets that fill a row-count instantiation of the lane-per-candidate family exactly (n_r == NRP: no zero padding) and that
+# no other case reaches; forward tests only (all B = 5, H = 7): they stay out of the VJP modules' NAMED
+_FILL = {"pend_raw24": (PEND, 24, False, False, 300), "pend_raw32": (PEND, 32, False, True, 310),
+         "pend_raw48": (PEND, 48, False, False, 320), "pend_raw64": (PEND, 64, False, True, 330),
+         "car_raw8": (CAR, 8, False, True, 340), "car_raw16": (CAR, 16, False, False, 350),
+         "car_raw40": (CAR, 40, False, True, 360), "car_raw56": (CAR, 56, False, False, 370),
+         "pend_grad16": (PEND, 16, True, True, 380), "car_grad10": (CAR, 10, True, False, 390)}
+CASES.update({nm: functools.lru_cache(None)(functools.partial(raw_case, env, n, hg, 5, 7, fb, seed))
+              for nm, (env, n, hg, fb, seed) in _FILL.items()})      # (env, N_r, derivative labels, feedback, seed)
+RAW_FILL = tuple(_FILL)
 
 
 def measure_ab(name):

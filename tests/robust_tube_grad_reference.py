@@ -29,8 +29,7 @@ from tests.robust_tube_reference import RobustCase
 _t = rref._t
 # Lipschitz constants of the raw cases (all B = 5, H = 7): small enough that Q stays of the order of the noise ellipsoid over seven
 # steps, large enough that both remainder boxes and both ellipsoid sums carry weight in the gradient
-_PEND_RAW_L = (_t(0.3, 0.3), _t(0.05, 0.05))
-_CAR_RAW_L = (_t(0.1, 0.1, 0.1, 0.1), _t(0.05, 0.05, 0.05, 0.05))
+_PEND_RAW_L, _CAR_RAW_L = rref.PEND_RAW_L, rref.CAR_RAW_L   # (0.3, 0.05) and (0.1, 0.05) per dimension: shared with the forward's raw cases
 
 
 def _raw(name):
@@ -40,8 +39,11 @@ def _raw(name):
 # grad14 (42 label rows): a second case of the (48, derivative labels) instantiation - grad16, the car, misses 1e-5 by the cancellation
 # in its variance.  Registered in the forward module's table because its helpers look a case up there by name
 gref.CASES.update({"grad14": functools.lru_cache(None)(lambda: ref.raw_case(PEND, 14, True, 5, 7, True, 220))})
-RAW = tuple(n for n in gref.ref.RAW + gref.RAW_GRAD + ("grad14",) if n not in rref.CASES)
-CASES = dict(rref.CASES)
+# the forward module's per-instantiation cases are forward-only: the sets of RAW_GRAD keep their place in this table, the exact fits
+# of moments_reference.RAW_FILL do not enter it
+_FORWARD = {n: f for n, f in rref.CASES.items() if n not in rref.INSTANTIATION_CASES}
+RAW = tuple(n for n in gref.ref.RAW + gref.RAW_GRAD + ("grad14",) if n not in _FORWARD)
+CASES = dict(_FORWARD)
 CASES.update({n: _raw(n) for n in RAW})
 NAMED = tuple(CASES)
 SETTINGS = ("mean", "cov", "both")

@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from tests import moments_grad_reference as _mgref
 from tests import moments_reference as mref
 
 F64 = torch.float64
@@ -59,6 +60,19 @@ CASES = {
     "pend_lper": lambda: RobustCase("pend_nofb", 7, _per_candidate(PEND_L[0], 257, 3), _per_candidate(PEND_L[1], 257, 4), 1.5),
     "grad5": lambda: RobustCase("grad5", 7, _t(0.1, 0.1, 0.1, 0.1), _t(0.05, 0.05, 0.05, 0.05), 2.0),
 }
+# one raw training set per remaining row-count instantiation of the lane-per-candidate family (all B = 5, H = 7): the sets the VJP
+# modules register (importing moments_grad_reference puts them into moments_reference.CASES) and the exact fits of
+# moments_reference.RAW_FILL, with the constants tests/robust_tube_grad_reference.py gives its raw cases
+PEND_RAW_L = (_t(0.3, 0.3), _t(0.05, 0.05))
+CAR_RAW_L = (_t(0.1, 0.1, 0.1, 0.1), _t(0.05, 0.05, 0.05, 0.05))
+INSTANTIATION_CASES = _mgref.RAW_GRAD + mref.RAW_FILL
+
+
+def _raw(name):
+    return lambda: RobustCase(name, 7, *(PEND_RAW_L if mref.CASES[name]().env_id == mref.PEND else CAR_RAW_L), 2.0)
+
+
+CASES.update({n: _raw(n) for n in INSTANTIATION_CASES})
 Q_LIMIT = 1e6                          # reference A stays finite with max|Q| below this over the horizon of every case
 
 

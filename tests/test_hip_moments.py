@@ -22,6 +22,34 @@ outputscale), P relative to max|P| of the step.  The kernel gets 8 x that for an
     raw33        2.5e-12  5.4e-08  3.4e-12  4.0e-14   33 random points, pendulum1D map
     grad5        1.4e-12  4.0e-08  3.0e-12  5.2e-14   5 points with value and gradient labels (15 rows), car map
     grad5_pend   3.2e-13  1.2e-08  1.1e-12  4.5e-15   ... pendulum1D map
+
+``mom_dispatch`` (csrc/moments_step.hpp) compiles the kernel per (environment, label rows rounded up to NRP, derivative labels): 24
+instantiations.  The cases above reach the pendulum's value-only 8 (raw7) and 40 (raw33, the shipped 36 points), the car's 24 (raw17)
+and 48 (the shipped 45 points), and both derivative-label 16 (grad5, grad5_pend).  ``test_every_row_count_instantiation`` compares the
+rest with reference A (B 5, H 7 each): the training sets of ``moments_grad_reference.RAW_GRAD``, which the VJP tests only run as the
+producer of their input, and the exact fits of ``moments_reference.RAW_FILL`` (n_r == NRP: no zero row, the odd-length column
+tail ``(NRP - j) & 1`` at every second column; raw48 and raw64 are exact fits too).  fb: with the feedback law.
+
+    case         mean      P        S        A         environment, labels -> NRP
+    raw12        1.2e-13  1.1e-10  1.8e-13  2.0e-15   pendulum1D, 12 values -> 16
+    raw29        1.8e-12  1.3e-08  4.5e-12  4.7e-14   car, 29 values -> 32, fb
+    raw48        5.6e-12  2.1e-07  6.6e-12  1.2e-13   car, 48 values -> 48 exactly, fb
+    raw56        2.2e-12  2.9e-08  5.7e-12  2.8e-14   pendulum1D, 56 values -> 56 exactly, fb
+    raw64        7.4e-12  1.9e-07  1.2e-11  1.1e-13   car, 64 values -> 64 exactly: the limit, fb
+    grad10       1.3e-12  2.6e-08  1.7e-12  8.9e-15   pendulum1D, 10 points x 3 labels = 30 -> 32 with derivative labels, fb
+    grad16       3.9e-12  1.7e-07  7.0e-12  1.4e-13   car, 16 x 3 = 48 -> 48 with derivative labels, exactly
+    grad21       7.5e-12  1.6e-07  3.9e-12  5.6e-14   pendulum1D, 21 x 3 = 63 -> 64 with derivative labels, fb
+    grad21car    8.7e-12  1.2e-07  6.2e-12  1.8e-13   car, 63 -> 64 with derivative labels, fb
+    pend_raw24   5.2e-13  3.6e-09  2.6e-12  9.0e-15   pendulum1D, 24 values -> 24 exactly
+    pend_raw32   2.3e-12  1.7e-08  4.8e-12  1.6e-14   pendulum1D, 32 -> 32 exactly, fb
+    pend_raw48   1.2e-12  4.1e-08  4.8e-12  9.0e-14   pendulum1D, 48 -> 48 exactly
+    pend_raw64   3.7e-12  1.0e-07  8.7e-12  5.2e-14   pendulum1D, 64 -> 64 exactly: the limit, fb
+    car_raw8     6.1e-14  8.0e-12  2.1e-13  3.0e-15   car, 8 -> 8 exactly, fb
+    car_raw16    4.5e-13  8.0e-10  5.9e-13  2.3e-14   car, 16 -> 16 exactly
+    car_raw40    5.7e-12  3.3e-08  6.3e-12  9.2e-14   car, 40 -> 40 exactly, fb: the first of the car's large forms
+    car_raw56    4.3e-12  1.9e-07  1.2e-11  1.4e-13   car, 56 -> 56 exactly
+    pend_grad16  1.8e-12  9.7e-08  4.0e-12  3.5e-14   pendulum1D, 16 x 3 = 48 -> 48 with derivative labels, exactly, fb
+    car_grad10   1.9e-12  4.1e-08  4.4e-12  6.9e-14   car, 10 x 3 = 30 -> 32 with derivative labels
 """
 import numpy as np
 import pytest
@@ -33,6 +61,7 @@ from sampling_gpmpc_amd.gp_model import GPHyperParams, RealDataPlan
 from sampling_gpmpc_amd.moments import MomentTube, moment_rollout, moment_rollout_plan
 from tests import moments_reference as ref
 from tests.helpers import load_params
+from tests.moments_grad_reference import RAW_GRAD            # the import registers these sets in ref.CASES
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -51,6 +80,34 @@ WORST_AB = {
     "raw33": {"mean": 2.5e-12, "P": 5.4e-08, "S": 3.4e-12, "A": 4.0e-14},
     "grad5": {"mean": 1.4e-12, "P": 4.0e-08, "S": 3.0e-12, "A": 5.2e-14},
     "grad5_pend": {"mean": 3.2e-13, "P": 1.2e-08, "S": 1.1e-12, "A": 4.5e-15},
+    "raw12": {"mean": 1.2e-13, "P": 1.1e-10, "S": 1.8e-13, "A": 2.0e-15},
+    "raw29": {"mean": 1.8e-12, "P": 1.3e-08, "S": 4.5e-12, "A": 4.7e-14},
+    "raw48": {"mean": 5.6e-12, "P": 2.1e-07, "S": 6.6e-12, "A": 1.2e-13},
+    "raw56": {"mean": 2.2e-12, "P": 2.9e-08, "S": 5.7e-12, "A": 2.8e-14},
+    "raw64": {"mean": 7.4e-12, "P": 1.9e-07, "S": 1.2e-11, "A": 1.1e-13},
+    "grad10": {"mean": 1.3e-12, "P": 2.6e-08, "S": 1.7e-12, "A": 8.9e-15},
+    "grad16": {"mean": 3.9e-12, "P": 1.7e-07, "S": 7.0e-12, "A": 1.4e-13},
+    "grad21": {"mean": 7.5e-12, "P": 1.6e-07, "S": 3.9e-12, "A": 5.6e-14},
+    "grad21car": {"mean": 8.7e-12, "P": 1.2e-07, "S": 6.2e-12, "A": 1.8e-13},
+    "pend_raw24": {"mean": 5.2e-13, "P": 3.6e-09, "S": 2.6e-12, "A": 9.0e-15},
+    "pend_raw32": {"mean": 2.3e-12, "P": 1.7e-08, "S": 4.8e-12, "A": 1.6e-14},
+    "pend_raw48": {"mean": 1.2e-12, "P": 4.1e-08, "S": 4.8e-12, "A": 9.0e-14},
+    "pend_raw64": {"mean": 3.7e-12, "P": 1.0e-07, "S": 8.7e-12, "A": 5.2e-14},
+    "car_raw8": {"mean": 6.1e-14, "P": 8.0e-12, "S": 2.1e-13, "A": 3.0e-15},
+    "car_raw16": {"mean": 4.5e-13, "P": 8.0e-10, "S": 5.9e-13, "A": 2.3e-14},
+    "car_raw40": {"mean": 5.7e-12, "P": 3.3e-08, "S": 6.3e-12, "A": 9.2e-14},
+    "car_raw56": {"mean": 4.3e-12, "P": 1.9e-07, "S": 1.2e-11, "A": 1.4e-13},
+    "pend_grad16": {"mean": 1.8e-12, "P": 9.7e-08, "S": 4.0e-12, "A": 3.5e-14},
+    "car_grad10": {"mean": 1.9e-12, "P": 4.1e-08, "S": 4.4e-12, "A": 6.9e-14},
+}
+# (environment, NRP, derivative labels) of every case that stands for an instantiation of mom_dispatch: all 24 of them
+INSTANTIATION = {
+    "raw7": (ref.PEND, 8, False), "raw12": (ref.PEND, 16, False), "pend_raw24": (ref.PEND, 24, False), "pend_raw32": (ref.PEND, 32, False),
+    "raw33": (ref.PEND, 40, False), "pend_raw48": (ref.PEND, 48, False), "raw56": (ref.PEND, 56, False), "pend_raw64": (ref.PEND, 64, False),
+    "car_raw8": (ref.CAR, 8, False), "car_raw16": (ref.CAR, 16, False), "raw17": (ref.CAR, 24, False), "raw29": (ref.CAR, 32, False),
+    "car_raw40": (ref.CAR, 40, False), "raw48": (ref.CAR, 48, False), "car_raw56": (ref.CAR, 56, False), "raw64": (ref.CAR, 64, False),
+    "grad5_pend": (ref.PEND, 16, True), "grad10": (ref.PEND, 32, True), "pend_grad16": (ref.PEND, 48, True), "grad21": (ref.PEND, 64, True),
+    "grad5": (ref.CAR, 16, True), "car_grad10": (ref.CAR, 32, True), "grad16": (ref.CAR, 48, True), "grad21car": (ref.CAR, 64, True),
 }
 DEV = "cuda"
 _AGENTS, _PLANS = {}, {}
@@ -161,6 +218,24 @@ def test_unstructured_training_sets_and_derivative_labels(name):
     plan, _ = plan_env_of(name)
     assert (plan.desc.grid_n0, plan.desc.grid_n1) == (0, 0) and plan.desc.real_has_grad == int(c.has_grad)
     assert plan.n_r == c.n_rows and c.X.shape[0] in (5, 7, 17, 33)
+    mt = run(name)
+    check_against_reference(name, mt)
+    assert int(mt.info.cpu().abs().max()) == 0
+
+
+def nrp_of(n_rows, has_grad):
+    """mom_dispatch's rounding: up to a multiple of 8, of 16 with derivative labels."""
+    step = 16 if has_grad else 8
+    return (n_rows + step - 1) // step * step
+
+
+@pytest.mark.parametrize("name", RAW_GRAD + ref.RAW_FILL)
+def test_every_row_count_instantiation(name):
+    """The forward kernel itself against reference A at the instantiations the cases above do not reach."""
+    c = ref.CASES[name]()
+    plan, _ = plan_env_of(name)
+    env, nrp, hg = INSTANTIATION[name]
+    assert plan.n_r == c.n_rows and nrp_of(plan.n_r, hg) == nrp and plan.desc.real_has_grad == int(hg) and c.env_id == env
     mt = run(name)
     check_against_reference(name, mt)
     assert int(mt.info.cpu().abs().max()) == 0

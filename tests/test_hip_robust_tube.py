@@ -20,6 +20,32 @@ has condition 1e7 and s goes down to 2e-6 of the outputscale (tests/test_hip_mom
     car_lper    1.4e-10  1.8e-04  1.8e-04  2.6e-04  9.3e-11   per-candidate l_mu / l_sigma (0.5 .. 1.5 x the car's), beta 2.5 (4e-2)
     pend_lper   1.1e-14  1.2e-08  1.3e-08  1.3e-08  1.5e-14   per-candidate constants, pendulum1D, beta 1.5 (2e-3)
     grad5       1.4e-12  4.0e-08  8.0e-09  4.9e-08  5.2e-14   5 points with value and gradient labels (15 rows), car map, B 5 (0.2)
+
+The rollout is compiled per (environment, label rows rounded up to NRP, derivative labels) like the moment rollout: the cases above
+run the pendulum's value-only 40, the car's 48 and the car's derivative-label 16.  ``test_every_row_count_instantiation`` compares the
+others with reference A on the raw training sets tests/test_hip_moments.py lists for them (its table gives each one's environment,
+label rows and NRP; B 5, H 7, beta 2, l_mu 0.3 / l_sigma 0.05 on the pendulum map, 0.1 / 0.05 on the car map):
+
+    case         mean     Q        r2       sd       jz        instantiation (max|Q| of reference A)
+    raw12        1.2e-13  1.1e-10  1.7e-10  1.3e-10  2.0e-15   pendulum1D 16 (1.8)
+    raw29        1.8e-12  1.3e-08  1.3e-08  2.7e-08  4.4e-14   car 32 (0.4)
+    raw48        5.6e-12  2.1e-07  1.3e-07  2.1e-07  1.3e-13   car 48, exact fit (8e-2)
+    raw56        2.2e-12  3.1e-08  2.6e-08  1.5e-07  2.4e-14   pendulum1D 56, exact fit (4e-2)
+    raw64        7.4e-12  1.9e-07  2.2e-07  3.4e-07  1.1e-13   car 64, exact fit (9e-2)
+    grad10       1.3e-12  2.6e-08  2.6e-08  2.8e-08  2.9e-14   pendulum1D 32 with derivative labels (4e-2)
+    grad16       3.9e-12  1.7e-07  1.9e-07  2.9e-07  1.4e-13   car 48 with derivative labels, exact fit (5e-2)
+    grad21       7.5e-12  1.6e-07  1.7e-07  1.7e-07  7.0e-14   pendulum1D 64 with derivative labels (1e-2)
+    grad21car    8.7e-12  1.2e-07  1.3e-07  1.7e-07  1.8e-13   car 64 with derivative labels (6e-2)
+    pend_raw24   5.2e-13  3.6e-09  3.6e-09  3.0e-08  9.0e-15   pendulum1D 24, exact fit (0.2)
+    pend_raw32   2.3e-12  1.7e-08  1.9e-08  6.1e-08  3.6e-14   pendulum1D 32, exact fit (0.1)
+    pend_raw48   1.2e-12  4.1e-08  4.2e-08  8.1e-08  9.0e-14   pendulum1D 48, exact fit (4e-2)
+    pend_raw64   3.7e-12  1.0e-07  1.0e-07  1.3e-07  8.1e-14   pendulum1D 64, exact fit (4e-2)
+    car_raw8     6.1e-14  1.2e-11  1.0e-11  1.4e-11  4.3e-15   car 8, exact fit (1e2: eight points leave the variance large)
+    car_raw16    4.5e-13  8.0e-10  1.2e-09  2.0e-09  2.3e-14   car 16, exact fit (1.0)
+    car_raw40    5.7e-12  3.3e-08  4.6e-08  3.3e-08  9.2e-14   car 40, exact fit (0.5)
+    car_raw56    4.3e-12  1.9e-07  2.0e-07  2.4e-07  1.4e-13   car 56, exact fit (0.1)
+    pend_grad16  1.8e-12  9.7e-08  1.0e-07  9.7e-08  3.1e-14   pendulum1D 48 with derivative labels, exact fit (3e-2)
+    car_grad10   1.9e-12  4.1e-08  5.2e-08  1.1e-07  6.9e-14   car 32 with derivative labels (9e-2)
 """
 import pytest
 import torch
@@ -30,7 +56,7 @@ from sampling_gpmpc_amd.robust_tube import (RobustTube, estimate_lipschitz, pair
                                             robust_tube_rollout_plan)
 from tests import moments_reference as mref
 from tests import robust_tube_reference as ref
-from tests.test_hip_moments import agent_of, plan_env_of
+from tests.test_hip_moments import INSTANTIATION, agent_of, nrp_of, plan_env_of
 
 pytestmark = pytest.mark.gpu
 F64 = torch.float64
@@ -46,6 +72,25 @@ WORST_AB = {
     "car_lper": {"mean": 1.4e-10, "Q": 1.8e-04, "r2": 1.8e-04, "sd": 2.6e-04, "jz": 9.3e-11},
     "pend_lper": {"mean": 1.1e-14, "Q": 1.2e-08, "r2": 1.3e-08, "sd": 1.3e-08, "jz": 1.5e-14},
     "grad5": {"mean": 1.4e-12, "Q": 4.0e-08, "r2": 8.0e-09, "sd": 4.9e-08, "jz": 5.2e-14},
+    "raw12": {"mean": 1.2e-13, "Q": 1.1e-10, "r2": 1.7e-10, "sd": 1.3e-10, "jz": 2.0e-15},
+    "raw29": {"mean": 1.8e-12, "Q": 1.3e-08, "r2": 1.3e-08, "sd": 2.7e-08, "jz": 4.4e-14},
+    "raw48": {"mean": 5.6e-12, "Q": 2.1e-07, "r2": 1.3e-07, "sd": 2.1e-07, "jz": 1.3e-13},
+    "raw56": {"mean": 2.2e-12, "Q": 3.1e-08, "r2": 2.6e-08, "sd": 1.5e-07, "jz": 2.4e-14},
+    "raw64": {"mean": 7.4e-12, "Q": 1.9e-07, "r2": 2.2e-07, "sd": 3.4e-07, "jz": 1.1e-13},
+    "grad10": {"mean": 1.3e-12, "Q": 2.6e-08, "r2": 2.6e-08, "sd": 2.8e-08, "jz": 2.9e-14},
+    "grad16": {"mean": 3.9e-12, "Q": 1.7e-07, "r2": 1.9e-07, "sd": 2.9e-07, "jz": 1.4e-13},
+    "grad21": {"mean": 7.5e-12, "Q": 1.6e-07, "r2": 1.7e-07, "sd": 1.7e-07, "jz": 7.0e-14},
+    "grad21car": {"mean": 8.7e-12, "Q": 1.2e-07, "r2": 1.3e-07, "sd": 1.7e-07, "jz": 1.8e-13},
+    "pend_raw24": {"mean": 5.2e-13, "Q": 3.6e-09, "r2": 3.6e-09, "sd": 3.0e-08, "jz": 9.0e-15},
+    "pend_raw32": {"mean": 2.3e-12, "Q": 1.7e-08, "r2": 1.9e-08, "sd": 6.1e-08, "jz": 3.6e-14},
+    "pend_raw48": {"mean": 1.2e-12, "Q": 4.1e-08, "r2": 4.2e-08, "sd": 8.1e-08, "jz": 9.0e-14},
+    "pend_raw64": {"mean": 3.7e-12, "Q": 1.0e-07, "r2": 1.0e-07, "sd": 1.3e-07, "jz": 8.1e-14},
+    "car_raw8": {"mean": 6.1e-14, "Q": 1.2e-11, "r2": 1.0e-11, "sd": 1.4e-11, "jz": 4.3e-15},
+    "car_raw16": {"mean": 4.5e-13, "Q": 8.0e-10, "r2": 1.2e-09, "sd": 2.0e-09, "jz": 2.3e-14},
+    "car_raw40": {"mean": 5.7e-12, "Q": 3.3e-08, "r2": 4.6e-08, "sd": 3.3e-08, "jz": 9.2e-14},
+    "car_raw56": {"mean": 4.3e-12, "Q": 1.9e-07, "r2": 2.0e-07, "sd": 2.4e-07, "jz": 1.4e-13},
+    "pend_grad16": {"mean": 1.8e-12, "Q": 9.7e-08, "r2": 1.0e-07, "sd": 9.7e-08, "jz": 3.1e-14},
+    "car_grad10": {"mean": 1.9e-12, "Q": 4.1e-08, "r2": 5.2e-08, "sd": 1.1e-07, "jz": 6.9e-14},
 }
 
 
@@ -129,7 +174,20 @@ def test_raw_training_set_with_derivative_labels():
     assert int(rt.info.cpu().abs().max()) == 0
 
 
-@pytest.mark.parametrize("name", ["pend_nofb", "pend_fb", "car_nofb", "car_fb", "car_q0", "grad5"])
+@pytest.mark.parametrize("name", ref.INSTANTIATION_CASES)
+def test_every_row_count_instantiation(name):
+    """The forward kernel itself against reference A at the instantiations the cases above do not reach."""
+    rc = ref.CASES[name]()
+    c = mref.CASES[rc.base]()
+    plan, _ = plan_env_of(rc.base)
+    env, nrp, hg = INSTANTIATION[name]
+    assert plan.n_r == c.n_rows and nrp_of(plan.n_r, hg) == nrp and plan.desc.real_has_grad == int(hg) and c.env_id == env
+    rt = run(name)
+    check_against_reference(name, rt)
+    assert int(rt.info.cpu().abs().max()) == 0
+
+
+@pytest.mark.parametrize("name", ["pend_nofb", "pend_fb", "car_nofb", "car_fb", "car_q0", "grad5"] + list(ref.INSTANTIATION_CASES))
 def test_centres_are_the_bits_of_the_moment_rollout(name):
     c, rc, x0, U, Q0, l_mu, l_sigma = inputs(name)
     rt = rollout(c, rc, x0, U, Q0, l_mu, l_sigma, want_parts=False)

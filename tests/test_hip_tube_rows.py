@@ -6,6 +6,9 @@ Shapes ``(Ns, H, nx, n_lin, n_quad)``:
     (65, 3, 4, 8, 4)     one sample over a wave; M with zero rows and columns
     (257, 8, 4, 16, 8)   both caps; a ragged last block; five partial records per (stage, row)
     (3, 64, 1, 1, 1)     nx = 1; T = 65 crosses a wave and four stage groups
+    (70, 20, 3, 5, 3)    trows_kernel<3>; two sample tiles x two stage groups (T = 21) with nx > 1
+    (130, 33, 2, 3, 2)   three sample tiles x three stage groups (T = 34) with nx = 2: the staging index [dimension][stage][sample]
+                         with all three running at once
 
 Tolerances are derived, not measured.  The reference values are longdouble.  With u = 2^-52:
     affine   |val - ref| <= 4 nx u (sum_k |E_rk x_k| + |off|)       a chain of nx fused terms and one addition: nx + 1 roundings

@@ -9,6 +9,7 @@ import torch
 
 from sampling_gpmpc_amd import _lib
 from tests import moments_reference as ref
+from tests.moments_grad_reference import RAW_GRAD            # the import registers these sets in ref.CASES
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "gpmpc_moment_rollout"
@@ -121,7 +122,7 @@ def test_wrappers_need_a_hip_device_and_are_exported():
 # ---------------------------------------------------------------------------------------------------------------------
 # the references
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ref.SHIPPED + ref.RAW)
+@pytest.mark.parametrize("name", ref.SHIPPED + ref.RAW + RAW_GRAD + ref.RAW_FILL)
 def test_a_agrees_with_b_within_the_recorded_table(name):
     """tests/test_hip_moments.py takes its tolerances from WORST_AB, the A-against-B differences as measured when the table was
     written.  Re-measured here; another BLAS may round differently, so each figure may be up to twice the recorded one (plus the
@@ -131,6 +132,27 @@ def test_a_agrees_with_b_within_the_recorded_table(name):
     assert sorted(got) == sorted(WORST_AB[name]) == ["A", "P", "S", "mean"]
     for q, v in got.items():
         assert v <= 2.0 * WORST_AB[name][q] + ref.FLOOR, (name, q, v)
+
+
+def test_the_instantiation_cases_cover_the_whole_dispatch_table_and_stay_off_the_variance_floor():
+    """tests/test_hip_moments.py names one case per (environment, NRP, derivative labels) instantiation of mom_dispatch; the sets that
+    exist for that purpose hit every exact fit n_r == NRP, stay out of the VJP tables, and keep reference A's variance ten times
+    above the floor (so that info == 0 is the right answer on the device)."""
+    from tests import moments_grad_reference as gref
+    from tests.test_hip_moments import INSTANTIATION, nrp_of
+    want = {(env, nrp, hg) for env in (ref.PEND, ref.CAR) for hg, step in ((False, 8), (True, 16)) for nrp in range(step, 65, step)}
+    assert len(want) == 24 and len(INSTANTIATION) == 24 and set(INSTANTIATION.values()) == want
+    for name, (env, nrp, hg) in INSTANTIATION.items():
+        c = ref.CASES[name]()
+        assert (c.env_id, nrp_of(c.n_rows, c.has_grad), c.has_grad) == (env, nrp, hg), name
+    only = RAW_GRAD + ref.RAW_FILL
+    assert set(only) <= set(INSTANTIATION) and set(only) | set(ref.RAW) == set(INSTANTIATION)
+    assert sorted({ref.CASES[nm]().n_rows for nm in only if ref.CASES[nm]().n_rows == INSTANTIATION[nm][1]}) == [8, 16, 24, 32, 40, 48, 56, 64]
+    assert not set(ref.RAW_FILL) & set(gref.NAMED)
+    for name in only:
+        c = ref.CASES[name]()
+        assert tuple(c.x0.shape) == (5, ref.DIMS[c.env_id][0]) and c.U.shape[1] == 7
+        assert float(ref.reference(name)["S"].min()) >= 10.0 * c.var_floor, name
 
 
 @pytest.mark.parametrize("name", ["pend_nofb", "car_fb", "raw17", "grad5"])

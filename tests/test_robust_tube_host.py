@@ -185,7 +185,24 @@ def test_lipschitz_workspace_is_proportional_to_the_grid_not_to_n(lib):
 # the references
 # ---------------------------------------------------------------------------------------------------------------------
 def test_the_cases_are_those_the_issue_lists():
-    assert sorted(ref.CASES) == sorted(["pend_nofb", "pend_fb", "car_nofb", "car_fb", "pend_q0", "car_q0", "car_lper", "pend_lper", "grad5"])
+    from tests import moments_grad_reference as mgref
+    from tests import robust_tube_grad_reference as rgref
+    from tests.test_hip_moments import INSTANTIATION
+    assert sorted(ref.CASES) == sorted(["pend_nofb", "pend_fb", "car_nofb", "car_fb", "pend_q0", "car_q0", "car_lper", "pend_lper", "grad5"]
+                                       + list(ref.INSTANTIATION_CASES))
+    # one raw set per row-count instantiation the nine do not reach: with the moment rollout's raw cases, all 24 of mom_dispatch
+    assert ref.INSTANTIATION_CASES == mgref.RAW_GRAD + mref.RAW_FILL and len(set(ref.INSTANTIATION_CASES)) == 19
+    assert set(ref.INSTANTIATION_CASES) | set(mref.RAW) == set(INSTANTIATION)
+    for name in ref.INSTANTIATION_CASES:
+        rc, c = ref.CASES[name](), mref.CASES[name]()
+        lm, ls = ref.PEND_RAW_L if c.env_id == mref.PEND else ref.CAR_RAW_L
+        assert rc.base == name and rc.H == 7 and rc.beta == 2.0 and c.x0.shape[0] == 5 and c.P0 is None
+        assert torch.equal(rc.l_mu, lm) and torch.equal(rc.l_sigma, ls)
+    # the exact fits are forward-only; the sets of RAW_GRAD keep the constants the VJP module runs them with
+    assert not set(mref.RAW_FILL) & set(rgref.NAMED) and set(mgref.RAW_GRAD) <= set(rgref.NAMED)
+    for name in mgref.RAW_GRAD:
+        a, b = ref.CASES[name](), rgref.CASES[name]()
+        assert (a.base, a.H, a.beta) == (b.base, b.H, b.beta) and torch.equal(a.l_mu, b.l_mu) and torch.equal(a.l_sigma, b.l_sigma)
     for name in ("pend_nofb", "pend_fb", "car_nofb", "car_fb"):
         rc = ref.CASES[name]()
         c = mref.CASES[rc.base]()

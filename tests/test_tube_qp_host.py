@@ -234,6 +234,13 @@ def test_gram_specific_argument_checks_and_the_workspace(lib):
     # the number of partials is a function of Ns only: the workspace per lower tile does not move with H, nx or nu
     per_tile = lambda Ns, H, nx, nu: (lib.gpmpc_tube_gram_workspace_bytes(Ns, H, nx, nu) / 8) / ((((H * nu + 15) // 16) * ((H * nu + 15) // 16 + 1) // 2) * 256 + 128)   # noqa: E731
     assert per_tile(257, 8, 4, 2) == per_tile(257, 64, 2, 1) == per_tile(257, 3, 1, 2) == 65
+    # four samples per block up to 2048 blocks, then ceil(Ns / 2048) rounded up to a multiple of four: the block counts of the large shapes
+    ceil_div = lambda a, b: -(-a // b)                                              # noqa: E731
+    blocks = lambda Ns: ceil_div(Ns, max(4, 4 * ceil_div(ceil_div(Ns, 2048), 4)))   # noqa: E731
+    assert [blocks(Ns) for Ns in (1, 4, 5, 257, 8192, 8193, 8195, 16384, 16385, 16389)] == [1, 1, 2, 65, 2048, 1025, 1025, 2048, 1366, 1366]
+    for Ns in (1, 4, 5, 8192, 8193, 8195, 16384, 16385, 16389, 10 ** 6):
+        assert per_tile(Ns, 2, 4, 2) == per_tile(Ns, 3, 2, 1) == per_tile(Ns, 2, 1, 1) == blocks(Ns), Ns
+    assert per_tile(8193, 3, 2, 1) == 1025 and per_tile(16389, 2, 1, 1) == 1366
     assert _apply(lib, V=None) == -1 and _apply(lib, X=None) == -1 and _apply(lib, n_seq=0) == -1
     assert _apply(lib, Ns=2 ** 30, n_seq=4) == -4
 

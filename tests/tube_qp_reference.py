@@ -5,7 +5,9 @@ is a forward simulation, G^T w the adjoint (backward) recursion, and W is built 
 Mehrotra predictor-corrector method over A's dense matrices, ``kkt_residuals`` the three residuals in the scaling
 ``solve_tube_qp`` documents.  ``make_case`` generates seeded problems: per-sample noisy damped oscillators (nx = 2, two blocks
 for nx = 4), a state box with a growing tightening, and input rows - under feedback ``u_min <= K (x - x_goal) + v <= u_max``
-with a stabilising K (the caller's A is then the closed loop A + B K), otherwise plain bounds on v.
+with a stabilising K (the caller's A is then the closed loop A + B K), otherwise plain bounds on v.  Every other ``nx <= 4``,
+``nu <= 2`` comes from a second generator of the same construction (a first-order lag for an odd last state, inputs dealt round
+the velocity-like states); the shapes of the first generator keep their arrays bit for bit.
 """
 from dataclasses import dataclass
 from functools import lru_cache
@@ -41,13 +43,26 @@ class Case:
 
 # the shapes of the kernel test (tests/test_hip_tube_qp.py) and of the solver test
 GRAM_SHAPES = [(1, 1, 2, 1), (5, 7, 2, 1), (3, 16, 2, 1), (3, 17, 2, 1), (7, 9, 4, 2), (257, 8, 4, 2), (2, 40, 4, 2), (2, 50, 4, 2),
-               (2, 64, 4, 2)]
-SOLVER_CASES = {(3, 4, 2, 1): False, (5, 6, 2, 1): False, (17, 9, 4, 2): True, (70, 17, 2, 1): False, (33, 40, 4, 2): True}
+               (2, 64, 4, 2),
+               # every other (nx, nu) instantiation, H = 128 stepped one column a stage, and more than four samples per block
+               (5, 7, 1, 1), (6, 9, 1, 2), (5, 9, 3, 1), (7, 11, 3, 2), (5, 9, 2, 2), (6, 17, 4, 1), (2, 128, 2, 1), (3, 128, 1, 1),
+               (8195, 2, 4, 2), (8193, 3, 2, 1), (16389, 2, 1, 1)]
+# the first two are the SLSQP cases and the first four the soft cases: new cases go to the end
+SOLVER_CASES = {(3, 4, 2, 1): False, (5, 6, 2, 1): False, (17, 9, 4, 2): True, (70, 17, 2, 1): False, (33, 40, 4, 2): True,
+                (9, 8, 3, 2): True, (6, 10, 1, 1): False}
 
 
 @lru_cache(maxsize=None)
 def make_case(Ns, H, nx, nu, feedback=False, seed=0):
-    assert nx in (2, 4) and nu == nx // 2
+    """Any 1 <= nx <= 4, 1 <= nu <= 2.  nx in (2, 4) with nu == nx // 2 - every shape the recorded tables were measured on - keeps its
+    own generator, so those arrays never move; everything else comes from ``_make_case_general``."""
+    assert 1 <= nx <= 4 and 1 <= nu <= 2
+    if nx in (2, 4) and nu == nx // 2:
+        return _make_case_blocks(Ns, H, nx, nu, feedback, seed)
+    return _make_case_general(Ns, H, nx, nu, feedback, seed)
+
+
+def _make_case_blocks(Ns, H, nx, nu, feedback, seed):
     rng = np.random.default_rng(1000 * seed + 7 * Ns + 13 * H + nx)
     dt, nb = 0.1, nx // 2
     A = np.zeros((Ns, nx, H, nx))
@@ -80,6 +95,65 @@ def make_case(Ns, H, nx, nu, feedback=False, seed=0):
     eps = 0.002 * np.arange(H + 1)[:, None] * np.ones((1, nx))
     x_max = np.tile(np.array([1.5, 0.25, 1.5, 0.25])[:nx], (H + 1, 1)) - eps
     x_min = -np.tile(np.array([1.5, 0.25, 1.5, 0.25])[:nx], (H + 1, 1)) + eps
+    u_lo, u_hi = np.full((H + 1, nu), -np.inf), np.full((H + 1, nu), np.inf)
+    u_lo[:H], u_hi[:H] = -1.0 + Kfb @ x_goal, 1.0 + Kfb @ x_goal
+    E = np.vstack([np.eye(nx), Kfb])
+    F = np.vstack([np.zeros((nx, nu)), np.eye(nu)])
+    return Case(A=A, B=B, c=c, x0=x0, omega=omega, q=q, r=r, Qu=Qu, lm=0.05, v_prev=v_prev, E=E, F=F, lo=np.hstack([x_min, u_lo]),
+                hi=np.hstack([x_max, u_hi]), n_state_rows=nx)
+
+
+def _make_case_general(Ns, H, nx, nu, feedback, seed):
+    """The same construction for every other (nx, nu): oscillator blocks for the state pairs, a first-order lag for an odd last
+    state; input m drives the velocity-like state (the blocks' second states, then the lag) number m mod their count, a second
+    round of inputs with 1.3 x the gain; the same small dense noise on A, B and c, so that no entry is structurally zero.  The lag
+    state is pushed outwards: its target lies at twice its start and its box ends 0.1 beyond the start, which it reaches within a
+    few stages at a saturated input - an oscillator's velocity bound does the same for the pairs."""
+    rng = np.random.default_rng(1000 * seed + 7 * Ns + 13 * H + nx + 101 * nu)
+    dt, nb = 0.1, nx // 2
+    lag = nx - 1 if nx % 2 else None
+    vel = [2 * blk + 1 for blk in range(nb)] + ([lag] if lag is not None else [])
+    A = np.zeros((Ns, nx, H, nx))
+    B = np.zeros((Ns, nx, H, nu))
+    for blk in range(nb):
+        k = 1.0 + 0.5 * blk + 0.03 * rng.standard_normal((Ns, H))
+        d = 0.3 + 0.02 * rng.standard_normal((Ns, H))
+        p, w = 2 * blk, 2 * blk + 1
+        A[:, p, :, p], A[:, p, :, w] = 1.0, dt
+        A[:, w, :, p], A[:, w, :, w] = -k * dt, 1.0 - d * dt
+    if lag is not None:
+        A[:, lag, :, lag] = 1.0 - (0.5 + 0.02 * rng.standard_normal((Ns, H))) * dt
+    for m in range(nu):
+        B[:, vel[m % len(vel)], :, m] = dt * (1.0 + 0.3 * (m // len(vel))) * (1.0 + 0.05 * rng.standard_normal((Ns, H)))
+    A += 0.001 * rng.standard_normal(A.shape)
+    B += 0.002 * rng.standard_normal(B.shape)
+    c = 0.001 * rng.standard_normal((Ns, nx, H))
+    x_goal = np.zeros(nx)
+    start = np.array([1.0, 0.0, -0.8, 0.0])[:nx]
+    x0 = np.tile(start, (Ns, 1))
+    Kfb = np.zeros((nu, nx))
+    if feedback:                                                # u = v + K (x - x_goal): A_cl = A + B K, c absorbs - B K x_goal
+        for m in range(nu):
+            w = vel[m % len(vel)]
+            if w == lag:
+                Kfb[m, w] = -1.0
+            else:
+                Kfb[m, w - 1], Kfb[m, w] = -2.0, -1.5
+        A = A + np.einsum("irta,ac->irtc", B, Kfb)
+        c = c - np.einsum("irta,a->irt", B, Kfb @ x_goal)
+    omega = np.full(Ns, 1.0 / Ns)
+    q = np.tile(np.array([10.0, 1.0, 6.0, 0.5])[:nx], (H + 1, 1))
+    q[H] *= 3.0
+    r = np.tile(x_goal, (H + 1, 1))
+    Qu = np.array([0.01, 0.02])[:nu]
+    v_prev = 0.1 * rng.standard_normal((H, nu))
+    bound = np.array([1.5, 0.25, 1.5, 0.25])[:nx]
+    if lag is not None:
+        r[:, lag] = 2.0 * start[lag]
+        bound[lag] = abs(start[lag]) + 0.1
+    eps = 0.002 * np.arange(H + 1)[:, None] * np.ones((1, nx))
+    x_max = np.tile(bound, (H + 1, 1)) - eps
+    x_min = -np.tile(bound, (H + 1, 1)) + eps
     u_lo, u_hi = np.full((H + 1, nu), -np.inf), np.full((H + 1, nu), np.inf)
     u_lo[:H], u_hi[:H] = -1.0 + Kfb @ x_goal, 1.0 + Kfb @ x_goal
     E = np.vstack([np.eye(nx), Kfb])

@@ -14,7 +14,8 @@ import numpy as np
 
 EPS = 2.0 ** -52
 LD = np.longdouble
-SHAPES = [(1, 1, 2, 0, 1), (5, 7, 2, 3, 1), (65, 3, 4, 8, 4), (257, 8, 4, 16, 8), (3, 64, 1, 1, 1)]     # (Ns, H, nx, n_lin, n_quad)
+SHAPES = [(1, 1, 2, 0, 1), (5, 7, 2, 3, 1), (65, 3, 4, 8, 4), (257, 8, 4, 16, 8), (3, 64, 1, 1, 1),     # (Ns, H, nx, n_lin, n_quad)
+          (70, 20, 3, 5, 3), (130, 33, 2, 3, 2)]
 TOL = 1e-3                                          # the violation tolerance the device test runs with
 GAP = 1e-9                                          # no active margin of the inputs lies this close to -TOL
 
