@@ -21,11 +21,16 @@ SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce
 HEADERS = ["gpmpc_device.hpp", "gpmpc_host.hpp", "rollout_args.hpp", "rollout_plan.hpp", "joint_args.hpp", "joint_eigh.hpp", "joint_plan.hpp", "hull_geom.hpp", "min_index.hpp", "base_stream.hpp", "moments_step.hpp", "pathwise_step.hpp", "robust_step.hpp", "contraction_math.hpp",
-           "rollout_one_gen.inc", "rollout_tiles_mfma.inc", "joint_mfma_gen.inc",
+           "rollout_one_gen.inc", "rollout_one_steps_gen.inc", "rollout_tiles_mfma.inc", "joint_mfma_gen.inc",
            os.path.join(REPO, "include", "gpmpc_hip.h")]
 GENERATED = {"rollout_one_gen.inc": os.path.join(REPO, "tools", "gen_rollout_one.py"),
              "rollout_tiles_mfma.inc": os.path.join(REPO, "tools", "gen_mfma_chains.py"),
              "joint_mfma_gen.inc": os.path.join(REPO, "tools", "gen_joint_mfma.py")}
+# Generated at build time and NOT committed (git-ignored): rollout_one_steps_gen.inc, the thirty static solve statements of
+# rollout_one_steps_kernel - 7 400 lines that repeat, row by row, what the run-time statements of rollout_one_gen.inc hold.
+# generate() writes a file when it is missing or older than its generator; it runs when this module is loaded (the ISA tools
+# compile rollout_one.hip with this module's flags) and at the head of build().
+BUILD_GENERATED = {"rollout_one_steps_gen.inc": (os.path.join(REPO, "tools", "gen_rollout_one.py"), "--steps-out")}
 OUT = os.path.join(os.path.dirname(HERE), "libgpmpc_hip.so")
 OBJDIR = os.path.join(HERE, "build")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -98,7 +103,22 @@ def clean_objdir():
             os.remove(p)
 
 
+def generate():
+    for inc, (gen, flag) in BUILD_GENERATED.items():
+        out = os.path.join(HERE, inc)
+        if _mtime(out) < _mtime(gen):
+            tmp = out + f".{os.getpid()}.tmp"          # (written aside and renamed: two processes may get here at once)
+            r = subprocess.run([sys.executable, gen, flag, tmp], capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError(f"{os.path.basename(gen)} {flag} failed:\n{r.stdout}\n{r.stderr}")
+            os.replace(tmp, out)
+
+
+generate()
+
+
 def build(force=False, verbose=False):
+    generate()
     os.makedirs(OBJDIR, exist_ok=True)
     clean_objdir()
     digest = flags_digest()

@@ -521,6 +521,7 @@ static RolloutKnobs rollout_knobs() {
     k.pin = g_rollout_pin;
     k.one = knob("GPMPC_ROLLOUT_ONE");
     k.tiles = knob("GPMPC_ROLLOUT_TILES");
+    k.one_steps = knob("GPMPC_ROLLOUT_ONE_STEPS");
     k.disable_fast = knob("GPMPC_DISABLE_FAST_ROLLOUT") > 0;
     k.disable_grid_root = knob("GPMPC_DISABLE_GRID_ROOT") > 0;
     k.force_global_factor = knob("GPMPC_FORCE_GLOBAL_FACTOR") > 0;

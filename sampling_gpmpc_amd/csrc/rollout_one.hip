@@ -52,6 +52,14 @@
 //     (one_solve, the extraction) reads; GPMPC_ONE_DEBUG checks the invariant in every block.  The values written are the
 //     ones the run-time selects produced: results are bit-identical (profiles/one_append_steps.md).
 //
+//   * the WHOLE step is selected by the step index in rollout_one_steps_kernel, the form a LEAN launch takes (the knob
+//     GPMPC_ROLLOUT_ONE_STEPS=0 keeps the epoch loop of rollout_one_kernel; rollout_one_launch): the body below is shared and its
+//     step takes the step index TS as a compile-time argument.  For TS >= 0 t, n_h = 3 TS, the columns, the readlane lanes and the
+//     append's block are constants, the solve is one_solve_t<TS> - exactly the step's tile rows, no branch inside - and the thirty
+//     bodies stand in a straight line: no dispatch, no back-edge, no copy of ud / drow / dcol, ONE rare branch per step (the root
+//     retry, the cold block and the launch's end behind it).  Same operations in the same order: bit-identical
+//     (profiles/one_static_steps.md: -7.7 %).
+//
 //   * the inverse of group K's diagonal tiles (P.gd[K]) is not read before the NEXT step's forward substitution reaches the
 //     first tile row of group K: from epoch K = 3 on one_solve<K> computes it - the three MFMAs and six VALU instructions of
 //     inverse_tiles, same operands and order, in the wait states of tile rows 0 and 1 - and the append only selects ud / drow /
@@ -70,6 +78,7 @@
 namespace gpmpc {
 
 #include "rollout_one_gen.inc"
+#include "rollout_one_steps_gen.inc"                              // one_solve_t<t>: written by build.py, not committed
 
 __device__ long long g_one_phase_cycles[16];
 __device__ double g_one_dbg[64 * 64];
@@ -98,6 +107,12 @@ __device__ double g_one_dbg[64 * 64];
 #else
 #define OPH_MARK(name)
 #endif
+// the static steps' own marks (rollout_one_steps_kernel): "; one_steps_head <t>" where the body of step t begins
+#ifdef GPMPC_ONE_PHASE_MARKS
+#define OPH_STEP(ts) asm volatile("; one_steps_head %0" : : "n"(ts))
+#else
+#define OPH_STEP(ts)
+#endif
 #ifndef GPMPC_ONE_DEBUG_STEP
 #define GPMPC_ONE_DEBUG_STEP 2
 #endif
@@ -105,7 +120,7 @@ __device__ double g_one_dbg[64 * 64];
 #define GPMPC_ONE_DEBUG_ROW 0
 #endif
 #ifdef GPMPC_ONE_DEBUG
-#define ODBG(slot, val) do { if (blockIdx.x == 0 && t == GPMPC_ONE_DEBUG_STEP) g_one_dbg[(slot) * 64 + lane] = (val); } while (0)
+#define ODBG(slot, val) do { if (blockIdx.x == 0 && tl == GPMPC_ONE_DEBUG_STEP) g_one_dbg[(slot) * 64 + lane] = (val); } while (0)
 #else
 #define ODBG(slot, val)
 #endif
@@ -436,8 +451,10 @@ struct OneLds {
 
 // LEAN: no optional outputs (Y, Xi) and the variance-is-zero replacement off - what RolloutRunner and the benchmark launch;
 // the three launch-uniform tests and their branches leave the step's spine
-template <int N0, int ENV, bool LEAN>
-__global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a) {
+// STEPS: the step loop as one body per step index (rollout_one_steps_kernel below); the loop over the epochs otherwise
+constexpr int one_epoch_of(int t) { return (kOneNKT + ((3 * t) >> 2)) >> 2; }      // group of the incomplete tile at n_h = 3 t
+template <int N0, int ENV, bool LEAN, bool STEPS>
+__device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
     static_assert(ENV == GPMPC_ENV_PENDULUM1D && N0 == 4, "instantiated for the pendulum1D 4 x 9 grid");
     constexpr int D = 2, T = 3, N1 = 9, NR = N0 * N1, NX = 2;
     constexpr int NKT = kOneNKT;
@@ -668,12 +685,44 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #endif
     OPH_MARK("end prologue");
 
-    auto step = [&](auto Kc) {
+    // ---- the epilogue: the launch's outputs.  The static steps run it where the launch's last step ends and end the wave
+    // there - joined behind the bodies, every exit's state would stay alive through all the bodies behind it
+    auto finish = [&](double xe0, double xe1) __attribute__((always_inline)) {
+        const double xe[NX] = {xe0, xe1};                         // the state behind the launch's last step
+        if (s_min < gp.var_floor) info_acc |= GPMPC_INFO_VAR_CLAMPED;
+        // (the output pointers and the sample index are fetched again here: held in SGPRs across the step loop they would be
+        // spilled - the loop leaves no scalar register free)
+        {
+            const OneArgsPtr ak = one_cold_args(ak0);
+            const long se = one_cold_sample(s32);
+            double* const X_traj = ak->X_traj;
+            if (lane <= H) {
+#pragma unroll
+                for (int d = 0; d < NX; ++d) X_traj[(se * NX + d) * (H + 1) + lane] = (lane == H) ? xe[d] : xq[d];
+            }
+            if (lane == 0) ak->info[se] = info_acc;
+        }
+        OPH_STORE;
+#ifdef GPMPC_PHASE_TIMERS
+        if (blockIdx.x == 0 && threadIdx.x == 0) g_one_phase_cycles[9] = __builtin_readcyclecounter() - opk0_;   // whole kernel
+#endif
+    };
+
+    // TS >= 0: the step index is static - t, n_h = 3 t and everything derived from them (the columns, the readlane lanes, the
+    // solve's row count, the append's block) are constants of the body, `next` is the rest of the launch and runs behind the
+    // append; TS = -1: the run-time form of the epoch loop, which reads t and n_h and advances them
+    auto step = [&](auto Kc, auto TSc, auto&& next) {
         constexpr int K = decltype(Kc)::value;                    // group of the incomplete tile (unified tile 9 + (n_h >> 2))
+        constexpr int TS = decltype(TSc)::value;
+        constexpr bool ST = TS >= 0;
+        static_assert(!ST || (one_epoch_of(TS) == K && TS >= OneEpoch<K>::t_begin && TS < OneEpoch<K>::t_end), "step outside its epoch");
         constexpr int R0 = 4 * K - NKT;                           // first tile row of the group (may be negative: real-data tiles)
-        const int i0 = n_h & 3, ycol = (i0 + 3) & 3, npts = t;
+        const int tl = ST ? TS : t, nhl = ST ? T * TS : n_h;
+        const int i0 = nhl & 3, ycol = (i0 + 3) & 3, npts = tl;
         const int cb0 = i0, cb1 = (i0 + 1) & 3, cb2 = (i0 + 2) & 3;
-        const bool more = t + 1 < H;
+        // (the last static step appends nothing whatever H is: H <= kOneAppendSteps + 1)
+        const bool more = (ST && TS >= kOneAppendSteps) ? false : tl + 1 < H;
+        if constexpr (ST) OPH_STEP(TS);
         // ---- (i) this step's entries are in LDS (written by the prologue or behind the previous step's sample) -------------
         one_sync_lds();
         // the solution, one natural register per group: the real-data tiles now, the appended tiles as they are solved
@@ -696,7 +745,8 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         double S0, S1;                                            // the Gram product's two accumulators (it rides in the last row's wait states)
         // (K >= kOneSolveInvK: the statement also inverts group K's diagonal tiles from ud / drow / dcol - what the previous
         // step's append left - and writes P.gd[K], in the wait states of tile rows 0 and 1; see section (vi))
-        one_solve<K>(P, Vu, RN, MK, n_h, S0, S1, ud, drow, dcol, Inat);
+        if constexpr (ST) one_solve_t<TS>(P, Vu, RN, MK, S0, S1, ud, drow, dcol, Inat);
+        else one_solve<K>(P, Vu, RN, MK, n_h, S0, S1, ud, drow, dcol, Inat);
         ODBG(0, Vu[0]);
         ODBG(1, Vu[1]);
         ODBG(2, Vu[2]);
@@ -726,7 +776,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         auto fetch = [&](auto bc) {
             constexpr int bq = decltype(bc)::value;
             mu[bq] = readlane_f64(Stot, 16 * cb[bq] + ycol);
-            zt[bq] = readlane_f64(zq[bq], t);
+            zt[bq] = readlane_f64(zq[bq], tl);
         };
         extract(std::integral_constant<int, 0>{});
         fetch(std::integral_constant<int, 0>{});
@@ -750,7 +800,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
         double earg;
         {
             const double xs[NX] = {x0n, x[1] + y0s};
-            earg = ent_a(t + 1, more, xs, un);
+            earg = ent_a(tl + 1, more, xs, un);
         }
         extract(std::integral_constant<int, 1>{});
         extract(std::integral_constant<int, 2>{});
@@ -768,7 +818,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 #pragma unroll
                 for (int c = 0; c < T; ++c) Sn[bq][c] = S[bq][c] + ((bq == c) ? gp.noise[bq] : 0.0);
             one_chol_rest(Sn, S, ch, earg, ek, C, Rt, cinv, rinv, c_ok, r_ok, ea);
-            ent_b(t + 1, ea, x0n, un, kk, Rq0, Rq1);
+            ent_b(tl + 1, ea, x0n, un, kk, Rq0, Rq1);
         }
         fetch(std::integral_constant<int, 1>{});
         fetch(std::integral_constant<int, 2>{});
@@ -790,9 +840,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 y[bq] = yb;
             }
         };
-        if (__builtin_expect(!r_ok, 0)) info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
-        draw();
-        if (__builtin_expect(clip || all_zero || !r_ok, 0)) {
+        auto cold = [&]() __attribute__((always_inline)) {
             OPH_MARK("cold begin");
             if (all_zero) {                                       // (uniform; only with a threshold >= 0) the mean, nothing to clip
 #pragma unroll
@@ -812,18 +860,50 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
             // repair: y[0] itself changed - the next state, input, exponential and axis factors again, from the final value
             if (y[0] != y0s) {
                 const double xs[NX] = {x0n, x[1] + y[0]};
-                const double ea = one_exp_neg(ent_a(t + 1, more, xs, un), ek);
-                ent_b(t + 1, ea, x0n, un, kk, Rq0, Rq1);
+                const double ea = one_exp_neg(ent_a(tl + 1, more, xs, un), ek);
+                ent_b(tl + 1, ea, x0n, un, kk, Rq0, Rq1);
             }
             OPH_MARK("cold end");
+        };
+        if constexpr (!ST) {
+            if (__builtin_expect(!r_ok, 0)) info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
+            draw();
+            if (__builtin_expect(clip || all_zero || !r_ok, 0)) cold();
+        } else {
+            // Static steps: ONE rare branch per step.  The bodies are longer than a conditional branch reaches, so every rare
+            // block costs the spine a taken branch around a long jump: the root retry, the cold block and the launch's end share
+            // one.  The draw runs before the retry is known to be needed and again behind it - the same values in the same order.
+            // The launch's end is a LEAF: the epilogue, then an s_endpgm the compiler does not see.  For the compiler the
+            // bodies are one straight line with thirty small ifs - as real exits it keeps the state of every exit alive up to a
+            // join behind the last body and structurises the bodies around them (spills, two long jumps per step) - and no
+            // state is merged between two bodies.
+            draw();
+            if (__builtin_expect(clip || all_zero || !r_ok || !more, 0)) {
+                if (!r_ok) {
+                    info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
+                    draw();
+                }
+                if (clip || all_zero || !r_ok) cold();
+                if (!more) {
+                    finish(x0n, x[1] + y[0]);
+                    asm volatile("s_endpgm" : : : "memory");         // (behind the epilogue's stores)
+                }
+            }
         }
         if (!LEAN && lane == 0 && one_wanted(Y_s)) {
 #pragma unroll
-            for (int bq = 0; bq < T; ++bq) Y_s[t * T + bq] = y[bq];
+            for (int bq = 0; bq < T; ++bq) Y_s[tl * T + bq] = y[bq];
         }
         OPH(4);
 
-        if (more) {
+        // ---- state hand-over (behind the append) -----------------------------------------------------------------------------
+        auto handover = [&]() __attribute__((always_inline)) {
+            x[1] = x[1] + y[0];
+            x[0] = x0n;
+            ucur = un;
+        };
+        if constexpr (!ST || TS < kOneAppendSteps)
+        if (ST || more) {
             if (!c_ok) info_acc |= GPMPC_INFO_TRAIN_CHOL_FAIL;
             {
                 const bool mine = jpt == npts;
@@ -856,7 +936,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
             // statement that reads it next; the last step of a launch appends nothing.
             constexpr bool INV_IN_SOLVE = K >= kOneSolveInvK;
             constexpr int TB = OneEpoch<K>::t_begin, TE = OneEpoch<K>::t_end < kOneAppendSteps ? OneEpoch<K>::t_end : kOneAppendSteps;
-            one_pick_row<TB, TE>(t, [&](auto tc) {
+            auto block = [&](auto tc) {
                 constexpr int TT = decltype(tc)::value, NH = T * TT;
                 constexpr int i0 = NH & 3;
                 constexpr int tn = NH >> 2;                       // the incomplete tile row; its unified tile is 4 K + bt
@@ -864,7 +944,7 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 constexpr int lo = NH - 4 * R0;                   // first new row inside group K's 16 rows
                 static_assert(((NKT + tn) >> 2) == K && lo == 4 * bt + i0 && tn >= 0 && tn < kOneNTR, "step outside its epoch");
 #ifdef GPMPC_ONE_DEBUG
-                if (n_h != NH) g_one_dbg[63 * 64 + lane] = (double)(n_h - NH);   // the invariant n_h == 3 t does not hold
+                if (nhl != NH) g_one_dbg[63 * 64 + lane] = (double)(nhl - NH);   // the invariant n_h == 3 t does not hold
 #endif
                 ent_c_put(std::integral_constant<int, NH + T>{}, ec);
                 OPH(1);
@@ -898,7 +978,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                     one_hset_gd<K + 1>(G1);                       // (hidden write under the dispatch, see above)
                 }
                 if constexpr (INV_IN_SOLVE && TT == OneEpoch<K>::t_end - 1) one_hset_gd<K>(inverse_tiles(ud, drow, dcol));
-            });
+            };
+            if constexpr (!ST) one_pick_row<TB, TE>(t, block);
+            else if constexpr (TS < kOneAppendSteps) block(TSc);  // the step's own block: no dispatch
             one_for<(R0 > 0 ? R0 : 0), (R0 + 5 < kOneNTR ? R0 + 5 : kOneNTR)>([&](auto rc) { one_touch_row<decltype(rc)::value>(P); });
             if constexpr (K < KLAST) one_touch_gd<K + 1>(P);
             OPH_T(8);
@@ -910,43 +992,53 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
                 ODBG(9, Gt);
                 one_put_gd<K>(P, Gt);
             }
-            n_h += T;
+            if constexpr (!ST) n_h += T;
         }
         OPH(6);
-
-        // ---- state hand-over ---------------------------------------------------------------------------------------------
-        x[1] = x[1] + y[0];
-        x[0] = x0n;
-        ucur = un;
-        t += 1;
+        handover();
+        if constexpr (!ST) t += 1;
         OPH(7);
+        if constexpr (ST) next();                                 // the next body, or nothing behind the last one
     };
 
-    one_for<KFIRST, KLAST + 1>([&](auto Kc) {
-        constexpr int K = decltype(Kc)::value;
+    if constexpr (!STEPS) {
+        one_for<KFIRST, KLAST + 1>([&](auto Kc) {
+            constexpr int K = decltype(Kc)::value;
 #pragma unroll 1
-        while (t < H && t < OneEpoch<K>::t_end) step(Kc);           // (n_h == 3 t: ((NKT + (n_h >> 2)) >> 2) == K as one compare)
-        ud = ud1, drow = drow1, dcol = dcol1;                     // the next group becomes the current one
-        ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
-    });
-
-    if (s_min < gp.var_floor) info_acc |= GPMPC_INFO_VAR_CLAMPED;
-    // (the output pointers and the sample index are fetched again here: held in SGPRs across the step loop they would be
-    // spilled - the loop leaves no scalar register free)
-    {
-        const OneArgsPtr ak = one_cold_args(ak0);
-        const long se = one_cold_sample(s32);
-        double* const X_traj = ak->X_traj;
-        if (lane <= H) {
-#pragma unroll
-            for (int d = 0; d < NX; ++d) X_traj[(se * NX + d) * (H + 1) + lane] = (lane == H) ? x[d] : xq[d];
-        }
-        if (lane == 0) ak->info[se] = info_acc;
+            while (t < H && t < OneEpoch<K>::t_end) step(Kc, std::integral_constant<int, -1>{}, [] {});   // (n_h == 3 t: ((NKT + (n_h >> 2)) >> 2) == K as one compare)
+            ud = ud1, drow = drow1, dcol = dcol1;                 // the next group becomes the current one
+            ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
+        });
+    } else {
+        // one body per step index, each continuing into the next: no dispatch, no back-edge, the epoch change is a renaming
+        auto run = [&](auto& self, auto tc) __attribute__((always_inline)) -> void {
+            constexpr int TS = decltype(tc)::value, K = one_epoch_of(TS);
+            step(std::integral_constant<int, K>{}, tc, [&]() __attribute__((always_inline)) {
+                if constexpr (TS < kOneAppendSteps) {
+                    if constexpr (TS + 1 == OneEpoch<K>::t_end) {
+                        ud = ud1, drow = drow1, dcol = dcol1;
+                        ud1 = Inat, drow1 = 1.0, dcol1 = 1.0;
+                    }
+                    self(self, std::integral_constant<int, TS + 1>{});
+                }
+            });
+        };
+        run(run, std::integral_constant<int, 0>{});
     }
-    OPH_STORE;
-#ifdef GPMPC_PHASE_TIMERS
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_one_phase_cycles[9] = __builtin_readcyclecounter() - opk0_;   // whole kernel
-#endif
+
+    if constexpr (!STEPS) finish(x[0], x[1]);
+}
+
+template <int N0, int ENV, bool LEAN>
+__global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a) {
+    rollout_one_body<N0, ENV, LEAN, false>(a);
+}
+// The LEAN form with one generated body per step index (n_h == 3 t: the whole step is a function of t, not only its append):
+// one_solve_t<t> holds exactly the step's tile rows, the readlane lanes are immediates, the append is the step's block without a
+// dispatch and the diagonal tiles' state is handed to the next body by name.  Same operations in the same order: bit-identical.
+template <int N0, int ENV>
+__global__ __launch_bounds__(64, 1) void rollout_one_steps_kernel(const RolloutArgs a) {
+    rollout_one_body<N0, ENV, true, true>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -954,6 +1046,9 @@ __global__ __launch_bounds__(64, 1) void rollout_one_kernel(const RolloutArgs a)
 // ---------------------------------------------------------------------------------------------------------------
 // instantiated for the pendulum1D 4 x 9 grid with value-only real labels, every appended row observed with T = 3 tasks; the
 // factor lives in registers (no workspace), the other layout fields are the generic kernel's
+constexpr bool kOneStepsDefault = true;                          // what a LEAN launch takes with GPMPC_ROLLOUT_ONE_STEPS unset
+static int g_one_last_form = -1;                                 // gpmpc_debug_last_rollout_one_form
+
 RolloutLaunch rollout_one_sizing(const RolloutShape& s, const RolloutLaunch& g) {
     RolloutLaunch p = g;
     p.kernel = GPMPC_KERNEL_AUTO;
@@ -971,7 +1066,11 @@ RolloutLaunch rollout_one_sizing(const RolloutShape& s, const RolloutLaunch& g) 
 
 int rollout_one_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStream_t st) {
     const bool lean = args.Y == nullptr && args.Xi == nullptr && !(args.var_zero_thr >= 0.0);
-    auto k = lean ? rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, true> : rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, false>;
+    // the steps form exists for LEAN launches; GPMPC_ROLLOUT_ONE_STEPS (p.one_steps) chooses between it and the epoch loop
+    const bool steps = lean && (p.one_steps != 0 ? p.one_steps > 0 : kOneStepsDefault);
+    auto k = steps ? rollout_one_steps_kernel<4, GPMPC_ENV_PENDULUM1D>
+                   : (lean ? rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, true> : rollout_one_kernel<4, GPMPC_ENV_PENDULUM1D, false>);
+    g_one_last_form = steps ? 1 : 0;
     GPMPC_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
     hipLaunchKernelGGL(k, dim3((unsigned)p.grid), dim3(p.block), p.lds_bytes, st, args);
     GPMPC_HIP_CHECK(hipGetLastError());
@@ -980,6 +1079,9 @@ int rollout_one_launch(const RolloutArgs& args, const RolloutLaunch& p, hipStrea
 
 }  // namespace gpmpc
 
+// the form of the step loop the last launch of ONE took: 0 the epoch loop (rollout_one_kernel), 1 one body per step index
+// (rollout_one_steps_kernel), -1 no launch yet
+extern "C" int gpmpc_debug_last_rollout_one_form(void) { return gpmpc::g_one_last_form; }
 extern "C" int gpmpc_debug_read_one_phases(long long* out /*[host] 16*/) {
     GPMPC_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(gpmpc::g_one_phase_cycles), 16 * sizeof(long long)));
     return GPMPC_OK;

@@ -30,11 +30,14 @@ struct RolloutShape {
 //     pin is set or ONE is forced.
 //   * GPMPC_DISABLE_FAST_ROLLOUT=1: ONE, TILES, FAST (unless pinned) and INDEP off.
 //   * GPMPC_DISABLE_GRID_ROOT=1: ONE and TILES off; FAST and INDEP take their instance without the grid root (the tests compare both).
+//   * GPMPC_ROLLOUT_ONE_STEPS=1 / =0: a LEAN launch of ONE takes rollout_one_steps_kernel (one body per step index) / the epoch
+//     loop of rollout_one_kernel; unset: the launcher's default (rollout_one_launch).  Which kernel is chosen does not depend on it.
 //   * GPMPC_FORCE_GLOBAL_FACTOR=1: ONE off, the fast kernel's L_hh and the generic kernel's factor in HBM; TILES unaffected.
 struct RolloutKnobs {
     int pin;                    // GPMPC_KERNEL_AUTO or the pinned kernel
     int one, tiles;             // GPMPC_ROLLOUT_ONE / _TILES: 1 forced, -1 off, 0 unset
     int disable_fast, disable_grid_root, force_global_factor;
+    int one_steps = 0;          // GPMPC_ROLLOUT_ONE_STEPS: 1 the steps form, -1 the loop form, 0 unset
 };
 
 struct RolloutLaunch {
@@ -46,6 +49,7 @@ struct RolloutLaunch {
     int T, rpl, fac_lds;
     int env_id, lhh_lds, grid_root;
     int n0, nt, seed;
+    int one_steps;              // ONE: the form of the step loop (RolloutKnobs::one_steps, passed through)
     long grid;
     int block;
     size_t lds_bytes;
@@ -99,7 +103,12 @@ inline RolloutLaunch plan_rollout_launch(const RolloutShape& s, const RolloutKno
     // seed points without a kept factor state are conditioning-only passes of the tiled kernel's step body; a kept / resumed
     // state is the generic kernel's own factor layout
     if (seeded) return (!s.state && use_tiles) ? tiles : g;
-    return use_one ? one : use_tiles ? tiles : use_fast ? fast : use_indep ? indep : g;
+    if (use_one) {
+        RolloutLaunch p = one;
+        p.one_steps = k.one_steps;
+        return p;
+    }
+    return use_tiles ? tiles : use_fast ? fast : use_indep ? indep : g;
 }
 
 }  // namespace gpmpc

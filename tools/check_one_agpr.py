@@ -4,7 +4,8 @@ PHYSICAL register constraints, and some of its writes are hidden from hipcc (EXE
 declared afterwards by an instruction-free statement: csrc/rollout_one.hip).  That is only sound while hipcc itself
 never touches those registers between the statements: no copy (v_accvgpr_mov / read / write of its own), no live-range split, no
 AGPR used as a spill slot for a VGPR.  This script compiles rollout_one.hip exactly as csrc/build.py does and scans the ISA of
-every rollout_one_kernel instantiation: ANY instruction outside an inline-asm statement (between ;;#ASMEND and the next
+every rollout_one_kernel instantiation and of rollout_one_steps_kernel (to the function's end: the static steps leave through
+s_endpgm inside asm statements, one per step): ANY instruction outside an inline-asm statement (between ;;#ASMEND and the next
 ;;#ASMSTART) that names an AGPR, and any scratch spill inside the kernel, is reported.  A toolchain or flag change that makes the
 compiler move a panel fails here (a CPU test runs it), not in a wrong trajectory.
 
@@ -40,7 +41,7 @@ def check(path):
         t = raw.strip()
         m = re.match(r"^(_Z\w+):", t)
         if m:
-            kernel = m.group(1) if "rollout_one_kernel" in m.group(1) else None
+            kernel = m.group(1) if ("rollout_one_kernel" in m.group(1) or "rollout_one_steps_kernel" in m.group(1)) else None
             in_asm = False
             continue
         if kernel is None:
@@ -51,7 +52,7 @@ def check(path):
         if t.startswith(";;#ASMEND"):
             in_asm = False
             continue
-        if t.startswith("s_endpgm"):
+        if t.startswith(".Lfunc_end"):
             kernel = None
             continue
         code = t.split(";")[0].strip()

@@ -19,7 +19,8 @@ forward substitution of a step is ONE statement per epoch (solve_stmt) whose wai
 MFMAs; tools/check_dpp_hazard.py checks the ISA of the result.  The subtracting form uses the FP64 MFMA's neg modifier
 (neg:[1,0,0]: -A B + C).  The append is selected by the step index (n_h = 3 t): emit_append writes the steps of every epoch and,
 per (tile row, first new row), the two EXEC masks of the row's masked panel writes as constants (append_row_masks;
-tests/test_one_append_masks.py checks them against the lane rule).  --variant ... --out ...: schedule experiments of tools/ubench/one_solve_chain.hip.
+tests/test_one_append_masks.py checks them against the lane rule).  --steps-out FILE writes the static solve statements of
+rollout_one_steps_kernel (emit_steps: one per step index) into a file of their own, which csrc/build.py generates.  --variant ... --out ...: schedule experiments of tools/ubench/one_solve_chain.hip.
 """
 import os
 import sys
@@ -127,7 +128,7 @@ def inverse_ops(m, K):
                     f"v_accvgpr_write_b32 a{n}, v{X}", f"v_accvgpr_write_b32 a{n + 1}, v{X + 1}"]}
 
 
-def solve_stmt(f, m, K, member):
+def solve_stmt(f, m, K, member, nh=None):
     """Row r: acc = rhs_r - sum_g panel(r, g) Vu[g]; W = G_r (block sum of acc); block b of Vu[g_r] := W.  Left to the compiler
     (one statement per chain, per MFMA, per DPP pair) every MFMA result is fenced by s_nop 5 (the compiler neither sees the
     MFMA nor may it schedule into the statement), twice per row: 48 of a row's ~190 cycles.  Here the row is software
@@ -135,9 +136,17 @@ def solve_stmt(f, m, K, member):
     issued INSIDE the previous row - behind its dependent MFMA, behind its diagonal MFMA and in the wait states in front of
     the three DPP reads (tools/ubench/mfma64_fill.hip: ONE independent FP64 MFMA between an MFMA and the reader of its result
     leaves nothing to pad).  The rows that may be absent this step (4 r >= n_h) are left by scalar branches inside the
-    statement; the last row of a step has nothing to hide behind and takes the padded form."""
+    statement; the last row of a step has nothing to hide behind and takes the padded form.
+
+    nh: the STATIC form for a step that finds exactly nh rows (one_solve_t<t>, nh = 3 t in epoch K): only the rows with 4 r < nh,
+    the last of them in the nxt = None form reached by fall-through, no compare, branch, label or nh operand - the MFMA, DPP and
+    VALU instructions of the run-time statement's path for that nh, in its order, with its operands; only the padding differs."""
     R0 = 4 * K - NKT
+    STATIC = nh is not None
+    assert not STATIC or (K == epoch_of(nh // T_ROWS) and nh % T_ROWS == 0)
     rows = list(range(0, min(R0 + 4, NTR)))
+    if STATIC:
+        rows = [r for r in rows if 4 * r < nh]
     L = []
     used = []
 
@@ -153,7 +162,7 @@ def solve_stmt(f, m, K, member):
     NOUT = K + 1 + 2 + (1 if INV else 0)                # Vu[0 .. K], S0, S1, (gd[K])
     rn_op = lambda g: f"%{NOUT + (g - m.gd[0])}"
     nh_op = f"%{NOUT + (K - m.gd[0] + 1)}"
-    mk_op = lambda b: f"%{NOUT + (K - m.gd[0] + 1) + 1 + b}"      # 1.0 in the lanes of block b, 0.0 elsewhere
+    mk_op = lambda b: f"%{NOUT + (K - m.gd[0] + 1) + (0 if STATIC else 1) + b}"      # 1.0 in the lanes of block b, 0.0 elsewhere
     GRAM = "nogram" not in VARIANT
 
     def gram_items(gs):
@@ -285,44 +294,60 @@ def solve_stmt(f, m, K, member):
             emit_ra(gram_items([g])[0])
         return True
 
-    if R0 <= 0:
-        L.append(f"s_cmp_eq_u32 {nh_op}, 0")
-        L.append("s_cbranch_scc1 .Lone_none_%=")
-    if FOLD:
-        emit_rnm(0)
-    L.append("s_nop 1")
-    first = ra_list(0)
-    for i, it in enumerate(first):
-        emit_ra(it)
-        if i + 1 < len(first):
-            L.append("s_nop 1")
-    lasts = []
-    head = False                                        # (the prologue ends on MFMAs)
-    for r in rows:
-        if r + 1 in rows:
-            if r + 1 >= R0:                             # row r + 1 may be absent this step
-                L.append(f"s_cmp_gt_u32 {nh_op}, {4 * (r + 1)}")
-                L.append(f"s_cbranch_scc0 .Lone_last{r}_%=")
-                lasts.append((r, head))
-            head = row(r, ra_list(r + 1), head)
-        else:
-            row(r, None, head)
-    L.append("s_branch .Lone_end_%=")
-    for r, hd in lasts:
-        L.append(f".Lone_last{r}_%=:")
-        row(r, None, True)                              # (reached by a branch: padded whatever stood in front - 8 cycles per step)
-        L.append("s_branch .Lone_end_%=")
-    if R0 <= 0:                                         # no appended row yet: the Gram product of the real-data tiles alone
-        L.append(".Lone_none_%=:")
+    def gram_only():
+        """no appended row yet: the Gram product of the real-data tiles alone"""
         if GRAM:
             L.append("s_nop 1")
             for i, it in enumerate(gram_items(range(0, K + 1))):
                 if i:
                     L.append("s_nop 1")
                 emit_ra(it)
+
+    def prologue():
+        if FOLD:
+            emit_rnm(0)
+        L.append("s_nop 1")
+        first = ra_list(0)
+        for i, it in enumerate(first):
+            emit_ra(it)
+            if i + 1 < len(first):
+                L.append("s_nop 1")
+
+    if STATIC:
+        if rows:
+            prologue()
+            head = False
+            for r in rows:
+                head = row(r, ra_list(r + 1) if r + 1 in rows else None, head)
+        else:
+            gram_only()
     else:
-        L.pop()                                         # the last of them falls through
-    L.append(".Lone_end_%=:")
+        if R0 <= 0:
+            L.append(f"s_cmp_eq_u32 {nh_op}, 0")
+            L.append("s_cbranch_scc1 .Lone_none_%=")
+        prologue()
+        lasts = []
+        head = False                                        # (the prologue ends on MFMAs)
+        for r in rows:
+            if r + 1 in rows:
+                if r + 1 >= R0:                             # row r + 1 may be absent this step
+                    L.append(f"s_cmp_gt_u32 {nh_op}, {4 * (r + 1)}")
+                    L.append(f"s_cbranch_scc0 .Lone_last{r}_%=")
+                    lasts.append((r, head))
+                head = row(r, ra_list(r + 1), head)
+            else:
+                row(r, None, head)
+        L.append("s_branch .Lone_end_%=")
+        for r, hd in lasts:
+            L.append(f".Lone_last{r}_%=:")
+            row(r, None, True)                              # (reached by a branch: padded whatever stood in front - 8 cycles per step)
+            L.append("s_branch .Lone_end_%=")
+        if R0 <= 0:
+            L.append(".Lone_none_%=:")
+            gram_only()
+        else:
+            L.pop()                                         # the last of them falls through
+        L.append(".Lone_end_%=:")
     if GRAM:
         L.append("s_nop 5")                             # S0 / S1 are read by the compiler's code next
     seen, ins = set(), []
@@ -343,6 +368,17 @@ def solve_stmt(f, m, K, member):
         mk += ', [ud] "v"(ud), [dr] "v"(drow), [dc] "v"(dcol), [inat] "v"(inat)'
     clob = ", ".join(f'"v{n}"' for n in SOLVE_CLOBBER) + ', "scc"'
     body = "\n        ".join(f'"{x}\\n\\t"' for x in L[:-1]) + f'\n        "{L[-1]}"'
+    if STATIC:
+        clob = ", ".join(f'"v{n}"' for n in SOLVE_CLOBBER)
+        # (the block masks are read by the rnfold variant only: as operands of the shipped statement they would pin eight
+        # registers for nothing - the static steps have none to spare in the last two epochs)
+        mk = ", ".join(([f'"v"(MK[{b}])' for b in range(4)] if FOLD else []) +
+                       (['[ud] "v"(ud), [dr] "v"(drow), [dc] "v"(dcol), [inat] "v"(inat)'] if INV else []))
+        ins_txt = ", ".join(x for x in (mk, ("\n          " + ", ".join(ins)) if ins else "") if x)
+        ins_txt = ", " + ins_txt if ins_txt else ""
+        f.write(f"__device__ __forceinline__ void one_solve_t_{nh // T_ROWS}(OnePanels& P, double* Vu, const double* RN, const double* MK, double& S0, double& S1, double ud, double drow, double dcol, double inat) {{\n")
+        f.write(f"    asm volatile({body}\n        : {outs}\n        : {rn}{ins_txt}\n        : {clob});\n}}\n")
+        return
     f.write(f"__device__ __forceinline__ void one_solve_{K}(OnePanels& P, double* Vu, const double* RN, const double* MK, int nh, double& S0, double& S1, double ud, double drow, double dcol, double inat) {{\n")
     f.write(f"    asm volatile({body}\n        : {outs}\n        : {rn}, \"s\"(nh), {mk},\n          {', '.join(ins)}\n        : {clob});\n}}\n")
 
@@ -538,6 +574,22 @@ def emit(f):
     emit_append(f)
 
 
+def emit_steps(f):
+    """rollout_one_steps_gen.inc: the static solve statements one_solve_t<t>, one per step index t with n_h = 3 t
+    (rollout_one_steps_kernel).  7 400 lines that repeat what the run-time statements hold, so the file is NOT committed:
+    csrc/build.py writes it (--steps-out) before it compiles, tests/test_one_steps_stmt.py checks the statements it holds."""
+    m = Map()
+    member = lambda r, g: f"P.p[{m.idx[('p', r, g)]}]"
+    steps = range(APPEND_STEPS + 1)
+    for t in steps:
+        solve_stmt(f, m, epoch_of(t), member, nh=T_ROWS * t)
+    sig = "OnePanels& P, double* Vu, const double* RN, const double* MK, double& S0, double& S1, double ud, double drow, double dcol, double inat"
+    f.write(f"template <int R>\n__device__ __forceinline__ void one_solve_t({sig}) {{\n")
+    for t in steps:
+        f.write(f"    {'if' if t == 0 else 'else if'} constexpr (R == {t}) one_solve_t_{t}(P, Vu, RN, MK, S0, S1, ud, drow, dcol, inat);\n")
+    f.write("}\n")
+
+
 def generic(f):
     """chains with every operand in ordinary registers (the LDS-resident super row, the Gram products)"""
     for neg, fresh in ((False, False), (True, False), (False, True)):
@@ -558,6 +610,13 @@ def generic(f):
 if __name__ == "__main__":
     if "--variant" in sys.argv:
         VARIANT = set(sys.argv[sys.argv.index("--variant") + 1].split(","))
+    if "--steps-out" in sys.argv:                   # the static statements alone, into their own (uncommitted) file
+        path = sys.argv[sys.argv.index("--steps-out") + 1]
+        with open(path, "w") as f:
+            f.write("// GENERATED by tools/gen_rollout_one.py --steps-out - do not edit, do not commit.  The static solve statements of rollout_one.hip.\n")
+            emit_steps(f)
+        print(path)
+        sys.exit(0)
     if "--out" in sys.argv:
         OUT = sys.argv[sys.argv.index("--out") + 1]
     with open(OUT, "w") as f:

@@ -14,6 +14,7 @@ second one ends.  The step blocks of the append (one per step t) each carry thei
 the blocks of the epoch, and `blocks` says how many there are - a step runs ONE of them.
 
     python tools/one_phase_mix.py [--full] [--src DIR]      DIR: another csrc directory (e.g. a checkout of the parent commit)
+    python tools/one_phase_mix.py --steps                   rollout_one_steps_kernel: the mix of every static step's body (scan_steps)
 """
 import collections
 import importlib.util
@@ -129,7 +130,60 @@ def scan(path, lean=True):
     return table, blocks, code_len
 
 
+def scan_steps(path, n_steps=30):
+    """rollout_one_steps_kernel (one body per step index): its own marks are `; one_steps_head <t>` where the body of step t
+    begins; the rare blocks (root retry, cold block, the launch's end with the epilogue) stand behind the last body.  Returns
+    (per step t the Counter of the instructions between its head and the next one - the last body ends at its s_endpgm -,
+    the Counter of what stands behind the bodies, codeLenInByte, spine) with spine = [(line number, code, step or None)] of
+    everything from the prologue's end to the last body's end, for the checks on the spine's branches."""
+    steps, tail, spine = collections.OrderedDict(), collections.Counter(), []
+    inside, cur, done, code_len, started = False, None, False, None, False
+    for ln, raw in enumerate(open(path), 1):
+        t = raw.strip()
+        m = re.match(r"^(_Z\w+):", t)
+        if m:
+            inside = "rollout_one_steps_kernel" in m.group(1)
+            continue
+        if not inside:
+            continue
+        if t.startswith("; codeLenInByte"):
+            code_len = int(t.split("=")[1])
+            inside = False
+            continue
+        if t.startswith("; one_phase_end prologue"):
+            started = True
+            continue
+        m = re.match(r"^; one_steps_head (\d+)", t)
+        if m:
+            cur = int(m.group(1))
+            steps[cur] = collections.Counter()
+            continue
+        code = t.split(";")[0].strip()
+        if not code or code.startswith("."):
+            continue
+        if started and not done:
+            spine.append((ln, code, cur))
+        if code.endswith(":"):
+            continue
+        op = code.split()[0]
+        c = tail if (done or cur is None) else steps[cur]
+        c.update(classes(op, code))
+        c["all"] += 1
+        if op == "s_endpgm" and cur == n_steps - 1 and not done:
+            done = True
+    return steps, tail, code_len, spine
+
+
 def main():
+    if "--steps" in sys.argv:
+        path = compile_to_isa(CSRC)
+        steps, tail, code_len, _ = scan_steps(path)
+        print(f"{path}: rollout_one_steps_kernel<4, pendulum1D>, codeLenInByte = {code_len}\n")
+        print("| step | all | " + " | ".join(COLS) + " |")
+        print("|---|---|" + "---|" * len(COLS))
+        for t, c in list(steps.items()) + [("behind the bodies", tail)]:
+            print(f"| {t} | {c['all']} | " + " | ".join(str(c[k]) for k in COLS) + " |")
+        return
     csrc = CSRC
     if "--src" in sys.argv:
         csrc = os.path.abspath(sys.argv[sys.argv.index("--src") + 1])
