@@ -60,6 +60,16 @@
 //     retry, the cold block and the launch's end behind it).  Same operations in the same order: bit-identical
 //     (profiles/one_static_steps.md: -7.7 %).
 //
+//   * in the static steps the two 3 x 3 roots are ONE stream behind their first pivots: C = chol(S + noise) and 1 / diag(C) are
+//     read by the append's selects alone, lane-locally, in lanes the step index fixes (OneRootLanes<t>, rollout_one_gen.inc), and
+//     slots 1 and 2 of the draw are consumed in the ONE lane of the step's point - so those lanes factor S + noise, all others S
+//     (one_root_in, one_chol_rest1), the draw runs lanewise and its slots are taken from a lane that factors S.  The root and clip
+//     tests are ballots cut to the lanes of each matrix and feed the step's one rare branch as one scalar test.  The selects on
+//     lane conditions that are literals of the step (the point's lane, the trajectory's lane, the existing points, the axis
+//     lanes, tile 8's block) are moves under literal EXEC masks or reads through a per-lane address - on the spine only: the cold
+//     block, where the compiler masks EXEC itself, keeps the select forms.  The loop form keeps two streams and run-time selects
+//     and is the bit-exact partner (profiles/one_root_stream.md: -2.4 %).
+//
 //   * the inverse of group K's diagonal tiles (P.gd[K]) is not read before the NEXT step's forward substitution reaches the
 //     first tile row of group K: from epoch K = 3 on one_solve<K> computes it - the three MFMAs and six VALU instructions of
 //     inverse_tiles, same operands and order, in the wait states of tile rows 0 and 1 - and the append only selects ud / drow /
@@ -425,6 +435,89 @@ __device__ __forceinline__ void one_chol_rest(const double (&A)[3][3], const dou
     invB[0] = p.y0[1], invB[1] = y1[1], invB[2] = y2[1];
 }
 
+// ---- the static steps run ONE root stream (profiles/one_root_stream.md).  C = chol(S + noise) and 1 / diag(C) are read by the
+// append's selects alone, lane-locally and in lanes the step index fixes (OneRootLanes<t>::value, rollout_one_gen.inc; the step's
+// block checks it against its patterns); slots 1 and 2 of the draw are consumed in ONE lane.  So the lanes of that mask factor
+// S + noise and all others S, with the levels of one_chol_rest for one matrix: per lane the operations, their operands and
+// their order are those of chol3_pair_lean for the matrix the lane factors => the same bits where a value is read.
+// The stream's input: in the lanes M the diagonal entries gain the noise and the first pivot's 1 / sqrt is (S + noise)'s.
+// (The off-diagonal entries of S + noise are those of S: S[i][j] = 0.0 - x is never -0.0, so adding 0.0 changes no bit.)
+template <unsigned long long M>
+__device__ __forceinline__ void one_root_in(double& s11, double& s22, double& y0, double n1, double n2, double y0a) {
+    asm("s_mov_b32 exec_lo, %[lo]\n\ts_mov_b32 exec_hi, %[hi]\n\t"
+        "v_add_f64 %[s11], %[s11], %[n1]\n\tv_add_f64 %[s22], %[s22], %[n2]\n\tv_mov_b64 %[y0], %[y0a]\n\t"
+        "s_mov_b64 exec, -1"
+        : [s11] "+v"(s11), [s22] "+v"(s22), [y0] "+v"(y0)
+        : [n1] "s"(n1), [n2] "s"(n2), [y0a] "v"(y0a), [lo] "n"((int)(unsigned)(M & 0xffffffffull)), [hi] "n"((int)(unsigned)(M >> 32)));
+}
+#define GPMPC_ONE_LVL1(stmt, third) \
+    stmt;                           \
+    third;                          \
+    GPMPC_ONE_FENCE()
+// pivots 2 and 3 of ONE matrix per lane, the exponential as the second stream of the levels.  Positive definite <=> d2 > 0: a
+// pivot d that is not > 0 (negative, a zero of either sign, NaN) leaves a NaN as its refined 1 / sqrt (rsq(d) is NaN or
+// infinite and t = (d / 2) rsq(d) is NaN then), the NaN reaches the next pivot through l10 / l21 and fails its test - so the last
+// pivot's test alone is the conjunction of the three that one_chol_rest forms.
+__device__ __forceinline__ void one_chol_rest1(double s10, double s20, double s21, double s11, double s22, double y0, double x,
+                                               const OneExpConsts& k, double& l10, double& l20, double& l21, double& r1, double& r2,
+                                               double& y1, double& y2, double& d2, double& ex) {
+    double d1, h, t, e, n21, p2;
+    double n, r, rr, a0, a1, a2, a4;
+    int ni;
+    GPMPC_ONE_FENCE();
+    GPMPC_ONE_LVL1(l10 = s10 * y0; l20 = s20 * y0, n = x * k.log2e);
+    GPMPC_ONE_LVL1(d1 = fma(-l10, l10, s11); n21 = fma(-l20, l10, s21), n = rint(n));
+    GPMPC_ONE_LVL1(y1 = __builtin_amdgcn_rsq(d1); h = 0.5 * d1; p2 = fma(-l20, l20, s22), r = fma(n, k.nln2h, x));
+    GPMPC_ONE_LVL1(t = h * y1, r = fma(n, k.nln2l, r); ni = (int)n);
+    GPMPC_ONE_LVL1(e = fma(-t, y1, 0.5), rr = r * r; a0 = 1.0 + r; a1 = fma(k.c3, r, k.c2));
+    GPMPC_ONE_LVL1(y1 = fma(y1, e, y1), a0 = fma(a1, rr, a0); a4 = fma(k.c9, r, k.c8); a1 = fma(k.c11, r, k.c10));
+    GPMPC_ONE_LVL1(l21 = n21 * y1; r1 = d1 * y1, a4 = fma(a1, rr, a4); a2 = fma(k.c5, r, k.c4));
+    GPMPC_ONE_LVL1(d2 = fma(-l21, l21, p2), a1 = fma(k.c7, r, k.c6));
+    GPMPC_ONE_LVL1(y2 = __builtin_amdgcn_rsq(d2); h = 0.5 * d2, a2 = fma(a1, rr, a2); rr = rr * rr);
+    GPMPC_ONE_LVL1(t = h * y2, a2 = fma(a4, rr, a2));
+    GPMPC_ONE_LVL1(e = fma(-t, y2, 0.5), a0 = fma(a2, rr, a0));
+    GPMPC_ONE_LVL1(y2 = fma(y2, e, y2), ex = ldexp(a0, ni));
+    GPMPC_ONE_LVL1(r2 = d2 * y2, (void)0);
+    asm volatile("" ::"v"(r1), "v"(r2));
+}
+// x_i := v_i in the ONE lane L (a point's lane, a step's lane), in place: s_bfm_b64 forms the mask in one instruction
+template <int L>
+__device__ __forceinline__ void one_lane_put(double& x0, double& x1, double v0, double v1) {
+    asm("s_bfm_b64 exec, 1, %[l]\n\tv_mov_b64 %[x0], %[v0]\n\tv_mov_b64 %[x1], %[v1]\n\ts_mov_b64 exec, -1"
+        : [x0] "+v"(x0), [x1] "+v"(x1)
+        : [v0] "v"(v0), [v1] "v"(v1), [l] "n"(L));
+}
+template <int L>
+__device__ __forceinline__ void one_lane_put(double& x0, double& x1, double& x2, double v0, double v1, double v2) {
+    asm("s_bfm_b64 exec, 1, %[l]\n\tv_mov_b64 %[x0], %[v0]\n\tv_mov_b64 %[x1], %[v1]\n\tv_mov_b64 %[x2], %[v2]\n\ts_mov_b64 exec, -1"
+        : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2)
+        : [v0] "v"(v0), [v1] "v"(v1), [v2] "v"(v2), [l] "n"(L));
+}
+// the same with v1, v2 wave-uniform values in scalar registers (v_readlane results)
+template <int L>
+__device__ __forceinline__ void one_lane_put_s(double& x0, double& x1, double& x2, double v0, double v1, double v2) {
+    asm("s_bfm_b64 exec, 1, %[l]\n\tv_mov_b64 %[x0], %[v0]\n\tv_mov_b64 %[x1], %[v1]\n\tv_mov_b64 %[x2], %[v2]\n\ts_mov_b64 exec, -1"
+        : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2)
+        : [v0] "v"(v0), [v1] "s"(v1), [v2] "s"(v2), [l] "n"(L));
+}
+// the lanes of a pattern that receive a value of C or 1 / diag(C)
+template <class Pat>
+constexpr unsigned long long one_pat_root_lanes() {
+    unsigned long long m = 0;
+    for (int id = OV_C00; id <= OV_CI2; ++id) m |= OnePatIds<Pat>::mask(id);
+    return m;
+}
+template <int TS>
+constexpr unsigned long long one_root_lanes() {
+    if constexpr (TS >= 0) return OneRootLanes<TS>::value;
+    else return 0;
+}
+template <int TS>
+constexpr int one_root_draw_lane() {
+    if constexpr (TS >= 0) return OneRootLanes<TS>::draw;
+    else return 0;
+}
+
 typedef const __attribute__((address_space(4))) RolloutArgs* OneArgsPtr;
 typedef __attribute__((address_space(3))) double* OneLdsRow;
 // (opaque to the optimiser: a load through the result stays where it is written)
@@ -515,6 +608,15 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
     unsigned hs_wr = (unsigned)(size_t)(OneLdsRow)(HSb + 3 * jpt * kOneRS), vr_wr = (unsigned)(size_t)(OneLdsRow)(VRb + lane * kOneRS);
     asm volatile("" : "+v"(hs_wr), "+v"(vr_wr));                  // (computed once: the add of the LDS base stays out of the step)
     const int rA = 4 * bm + jq;                                   // row of this lane's diagonal-tile entry inside its group
+    // static steps: tile 8 of v_r (group 2 holds this one real-data tile, in block 0) is read through a per-lane address - the
+    // lanes of the other blocks read a slot that holds zero (the pad column of VR's row 0, which no converter write touches), so
+    // the read delivers what the select on the block delivered
+    constexpr int kVrZero = kOneRS - 1;
+    int t8_rd = (bm == 0) ? (32 + kq) * kOneRS + jq : kVrZero;
+    if constexpr (STEPS) {
+        asm volatile("" : "+v"(t8_rd));
+        if (lane == 0) VRb[kVrZero] = 0.0;
+    }
 
     double x[NX];
 #pragma unroll
@@ -555,9 +657,26 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
 #endif
 
     // ---- the kernel entries of a step, in the three pieces the rotated loop issues them in --------------------------------
+    // xh[0] - (the GP input's coordinate the lane measures against: g_sel0 ? xi0 : xi1).  LQ >= 0 (the static steps' spine): the
+    // difference against xi0 everywhere, then against xi1 in the axis-1 lanes N0 .. N0 + N1 - 1 under a literal EXEC mask - the
+    // same subtraction per lane, without the select
+    auto axis_d0 = [&](auto lq, double xi0, double xi1) -> double {
+        if constexpr (decltype(lq)::value >= 0) {
+            double d = xh[0] - xi0;
+            asm("s_bfm_b64 exec, %[w], %[o]\n\tv_add_f64 %[d], %[x], -%[b]\n\ts_mov_b64 exec, -1"
+                : [d] "+v"(d)
+                : [x] "v"(xh[0]), [b] "v"(xi1), [w] "n"(N1), [o] "n"(N0));
+            return d;
+        } else {
+            return xh[0] - (g_sel0 ? xi0 : xi1);
+        }
+    };
     // (a) input and GP input of step tn from the state xs, the trajectory record, the exponent of the lane's kernel factor:
     //     ONE exponential per lane - the grid axis factor (lanes < N0 + N1) or the appended point jpt
-    auto ent_a = [&](int tn, bool store, const double (&xs)[NX], double& un) -> double {
+    // (LQ >= 0: tn is the constant LQ and the trajectory record is a move under a literal EXEC mask - only where control flow is
+    // uniform for the compiler too, i.e. on the static steps' spine: the statement leaves EXEC all ones)
+    auto ent_a = [&](auto lq, int tn, bool store, const double (&xs)[NX], double& un) -> double {
+        constexpr int LQ = decltype(lq)::value;
         double xi[D];
         {
             const double uf = readlane_f64(uq, tn);
@@ -572,22 +691,36 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
             xi[0] = xs[0];
             xi[1] = un;
         }
+        if constexpr (LQ >= 0) {
+            static_assert(NX == 2, "one statement for the two coordinates");
+            one_lane_put<LQ>(xq[0], xq[1], xs[0], xs[1]);
+        } else {
 #pragma unroll
-        for (int d = 0; d < NX; ++d) xq[d] = (lane == tn) ? xs[d] : xq[d];
+            for (int d = 0; d < NX; ++d) xq[d] = (lane == tn) ? xs[d] : xq[d];
+        }
         if (!LEAN && lane == 0 && one_wanted(Xi_s) && store) {
 #pragma unroll
             for (int d = 0; d < D; ++d) Xi_s[tn * D + d] = xi[d];
         }
         // (axis lanes: d1 * q1 is an exact zero, so the sum is round(d0 * q0) and the scaling by -0.5 is exact in either order)
-        const double d0 = xh[0] - (g_sel0 ? xi[0] : xi[1]), d1 = xh[1] - xi[1], q0 = d0 * il0_lane, q1 = d1 * il1_lane;
+        const double d0 = axis_d0(lq, xi[0], xi[1]), d1 = xh[1] - xi[1], q0 = d0 * il0_lane, q1 = d1 * il1_lane;
         return -0.5 * (d0 * q0 + d1 * q1);
     };
     // (b) the factor of the tn existing points, and the axis factors to all DPP rows (requested here, used in (c))
     // (q0, q1 are two instructions each from the GP input (xi0, xi1): computed again where they are used rather than
     // carried across the roots - this kernel has no register to spare)
-    auto ent_b = [&](int tn, double ea, double xi0, double xi1, double& kk, double& Rq0, double& Rq1) {
-        const double gq = (xh[0] - (g_sel0 ? xi0 : xi1)) * il0_lane;   // (an axis lane's q0)
-        kk = (jpt >= 0 && jpt < tn) ? os * ea : 0.0;
+    // (LQ >= 0: tn is the constant LQ, the lanes of the existing points are a literal EXEC mask - the static steps' spine only)
+    auto ent_b = [&](auto lq, int tn, double ea, double xi0, double xi1, double& kk, double& Rq0, double& Rq1) {
+        constexpr int LQ = decltype(lq)::value;
+        const double gq = axis_d0(lq, xi0, xi1) * il0_lane;           // (an axis lane's q0)
+        if constexpr (LQ > 0) {
+            kk = 0.0;
+            asm("s_bfm_b64 exec, %[w], %[o]\n\tv_mul_f64 %[k], %[os], %[ea]\n\ts_mov_b64 exec, -1"
+                : [k] "+v"(kk)
+                : [os] "s"(os), [ea] "v"(ea), [w] "n"(LQ), [o] "n"(kPt0));
+        } else {
+            kk = (jpt >= 0 && jpt < tn) ? os * ea : 0.0;
+        }
         Rq0 = one_bpermute(ea, bp_addr);
         Rq1 = one_bpermute(ea * gq, bp_addr);
     };
@@ -674,8 +807,8 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
     double ucur;                                                  // the input of the step whose entries are in LDS
     {
         double kk, Rq0, Rq1;
-        const double ea = one_exp_neg(ent_a(0, true, x, ucur), ek);
-        ent_b(0, ea, x[0], ucur, kk, Rq0, Rq1);
+        const double ea = one_exp_neg(ent_a(std::integral_constant<int, -1>{}, 0, true, x, ucur), ek);
+        ent_b(std::integral_constant<int, -1>{}, 0, ea, x[0], ucur, kk, Rq0, Rq1);
         OneEntC e;
         ent_c_vals(false, kk, x[0], ucur, Rq0, Rq1, e);
         ent_c_put(std::integral_constant<int, 0>{}, e);
@@ -731,11 +864,12 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
         // s_waitcnt in front of the other reads)
         Vu[0] = VRb[vr_rd];
         Vu[1] = VRb[vr_rd + 16 * kOneRS];
-        double t8 = VRb[(32 + kq) * kOneRS + jq];
+        double t8 = VRb[ST ? t8_rd : (32 + kq) * kOneRS + jq];
 #pragma unroll
         for (int g = KFIRST; g <= K; ++g) RN[g] = HSb[max(hs_rd + 16 * g * kOneRS, 0)];
         asm volatile("" : "+v"(t8), "+v"(RN[K]));                 // t8 is not touched before the last read has been issued
-        Vu[2] = (bm == 0) ? t8 : 0.0;
+        if constexpr (ST) Vu[2] = t8;
+        else Vu[2] = (bm == 0) ? t8 : 0.0;
 #pragma unroll
         for (int g = 3; g <= K; ++g) Vu[g] = 0.0;
         OPH(0);
@@ -792,15 +926,17 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
         }
         double x0n, un, kk, Rq0, Rq1;
         x0n = x[0] + x[1] * a.env.dt;
-        {
-            const bool mine = jpt == npts;                        // the lane of the point this step appends: its GP input
+        if constexpr (ST) {                                       // the lane of the point this step appends: its GP input
+            one_lane_put<kPt0 + (ST ? TS : 0)>(xh[0], xh[1], x[0], ucur);
+        } else {
+            const bool mine = jpt == npts;
             xh[0] = mine ? x[0] : xh[0];
             xh[1] = mine ? ucur : xh[1];
         }
         double earg;
         {
             const double xs[NX] = {x0n, x[1] + y0s};
-            earg = ent_a(tl + 1, more, xs, un);
+            earg = ent_a(std::integral_constant<int, ST ? TS + 1 : -1>{}, tl + 1, more, xs, un);
         }
         extract(std::integral_constant<int, 1>{});
         extract(std::integral_constant<int, 2>{});
@@ -811,14 +947,33 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
         // ---- (iii) + (iv) pivots 2 and 3 with the next step's exponential as a third stream of their levels ------------------
         double Rt[T][T], C[T][T], cinv[T];
         bool c_ok, r_ok;
-        {
+        unsigned long long okb = 0, clipm = 0;                    // static steps: the lanes whose root exists / whose draw clips
+        // static steps: ONE stream - the lanes AT factor S + noise (C, cinv: what the append's selects read there), the others S
+        // (Rt: the draw, whose slots 1 and 2 are taken from lane RL); the tests are ballots cut to the lanes of each matrix
+        constexpr unsigned long long AT = one_root_lanes<TS>();
+        constexpr int RL = one_root_draw_lane<TS>(), PL = kPt0 + (ST ? TS : 0);
+        static_assert(!ST || (!((AT >> RL) & 1) && (RL == PL || ((AT >> PL) & 1))), "the draw's lane factors S");
+        if constexpr (ST) {
+            double s11 = S[1][1], s22 = S[2][2], y0m = ch.y0[1], l10, l20, l21, r1, r2, y1, y2, d2, ea;
+            if constexpr (AT != 0) one_root_in<AT>(s11, s22, y0m, gp.noise[1], gp.noise[2], ch.y0[0]);
+            one_chol_rest1(S[1][0], S[2][0], S[2][1], s11, s22, y0m, earg, ek, l10, l20, l21, r1, r2, y1, y2, d2, ea);
+            okb = __builtin_amdgcn_ballot_w64(d2 > 0.0);
+            c_ok = (okb & AT) == AT;
+            r_ok = (okb & ~AT) == ~AT;
+            C[0][0] = ch.r0[0], C[1][0] = l10, C[2][0] = l20, C[1][1] = r1, C[2][1] = l21, C[2][2] = r2;
+            Rt[0][0] = ch.r0[1], Rt[1][0] = l10, Rt[2][0] = l20, Rt[1][1] = r1, Rt[2][1] = l21, Rt[2][2] = r2;
+            C[0][1] = C[0][2] = C[1][2] = 0.0;
+            Rt[0][1] = Rt[0][2] = Rt[1][2] = 0.0;
+            cinv[0] = ch.y0[0], cinv[1] = y1, cinv[2] = y2;
+            ent_b(std::integral_constant<int, ST ? TS + 1 : -1>{}, tl + 1, ea, x0n, un, kk, Rq0, Rq1);
+        } else {
             double Sn[T][T], rinv[T], ea;
 #pragma unroll
             for (int bq = 0; bq < T; ++bq)
 #pragma unroll
                 for (int c = 0; c < T; ++c) Sn[bq][c] = S[bq][c] + ((bq == c) ? gp.noise[bq] : 0.0);
             one_chol_rest(Sn, S, ch, earg, ek, C, Rt, cinv, rinv, c_ok, r_ok, ea);
-            ent_b(tl + 1, ea, x0n, un, kk, Rq0, Rq1);
+            ent_b(std::integral_constant<int, -1>{}, tl + 1, ea, x0n, un, kk, Rq0, Rq1);
         }
         fetch(std::integral_constant<int, 1>{});
         fetch(std::integral_constant<int, 2>{});
@@ -829,6 +984,7 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
             // the floored bound clips this one catches (a NaN S fails the root and gets there by !r_ok); the cold block repeats
             // the test per slot with the floored variance and decides.  The three maxima leave the spine.
             clip = false;
+            clipm = 0;
 #pragma unroll
             for (int bq = 0; bq < T; ++bq) {
                 double acc = 0.0;
@@ -836,9 +992,13 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
                 for (int c = 0; c <= bq; ++c) acc = fma(Rt[bq][c], zt[c], acc);
                 const double yb = acc + mu[bq];
                 const double dlt = yb - mu[bq];
-                clip = clip || (dlt * dlt > a.beta * a.beta * S[bq][bq]);
+                const bool cl = dlt * dlt > a.beta * a.beta * S[bq][bq];
+                if constexpr (ST) clipm |= __builtin_amdgcn_ballot_w64(cl);
+                else clip = clip || cl;
                 y[bq] = yb;
             }
+            // (static steps: slots 1 and 2 are the draw in the lanes that factor S and nothing in the others)
+            if constexpr (ST) clip = (clipm & ~AT) != 0;
         };
         auto cold = [&]() __attribute__((always_inline)) {
             OPH_MARK("cold begin");
@@ -860,8 +1020,8 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
             // repair: y[0] itself changed - the next state, input, exponential and axis factors again, from the final value
             if (y[0] != y0s) {
                 const double xs[NX] = {x0n, x[1] + y[0]};
-                const double ea = one_exp_neg(ent_a(tl + 1, more, xs, un), ek);
-                ent_b(tl + 1, ea, x0n, un, kk, Rq0, Rq1);
+                const double ea = one_exp_neg(ent_a(std::integral_constant<int, -1>{}, tl + 1, more, xs, un), ek);
+                ent_b(std::integral_constant<int, -1>{}, tl + 1, ea, x0n, un, kk, Rq0, Rq1);
             }
             OPH_MARK("cold end");
         };
@@ -878,7 +1038,8 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
             // join behind the last body and structurises the bodies around them (spills, two long jumps per step) - and no
             // state is merged between two bodies.
             draw();
-            if (__builtin_expect(clip || all_zero || !r_ok || !more, 0)) {
+            // (one scalar test: a root that failed in any lane - either matrix - or a draw that clips in a lane that factors S)
+            if (__builtin_expect(((~okb | (clipm & ~AT)) != 0) || all_zero || !more, 0)) {
                 if (!r_ok) {
                     info_acc |= root_small_fast_retry<T>(S, one_cold_args(ak0)->gp.jitter, Rt);
                     draw();
@@ -888,6 +1049,9 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
                     finish(x0n, x[1] + y[0]);
                     asm volatile("s_endpgm" : : : "memory");         // (behind the epilogue's stores)
                 }
+                // (a step that appends reports a failed root of S + noise - here, off the spine)
+                if constexpr (TS < kOneAppendSteps)
+                    if (!c_ok) info_acc |= GPMPC_INFO_TRAIN_CHOL_FAIL;
             }
         }
         if (!LEAN && lane == 0 && one_wanted(Y_s)) {
@@ -904,11 +1068,17 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
         };
         if constexpr (!ST || TS < kOneAppendSteps)
         if (ST || more) {
-            if (!c_ok) info_acc |= GPMPC_INFO_TRAIN_CHOL_FAIL;
-            {
+            if constexpr (!ST)
+                if (!c_ok) info_acc |= GPMPC_INFO_TRAIN_CHOL_FAIL;
+            // the label column is whitened by the same MFMAs (w_r rides in Vu)
+            if constexpr (ST && RL == PL) {                      // the point's lane holds the draw itself
+                one_lane_put<PL>(yt[0], yt[1], yt[2], y[0], y[1], y[2]);
+            } else if constexpr (ST) {                           // it factors S + noise: slots 1 and 2 from lane RL
+                one_lane_put_s<PL>(yt[0], yt[1], yt[2], y[0], readlane_f64(y[1], RL), readlane_f64(y[2], RL));
+            } else {
                 const bool mine = jpt == npts;
 #pragma unroll
-                for (int bq = 0; bq < T; ++bq) yt[bq] = mine ? y[bq] : yt[bq];   // the label column is whitened by the same MFMAs (w_r rides in Vu)
+                for (int bq = 0; bq < T; ++bq) yt[bq] = mine ? y[bq] : yt[bq];
             }
             // ---- (v) the rest of step t + 1's entries: their LDS writes land while the append runs ---------------------------
             OneEntC ec;
@@ -943,6 +1113,15 @@ __device__ __forceinline__ void rollout_one_body(const RolloutArgs& a) {
                 constexpr int bt = (NKT + tn) & 3;
                 constexpr int lo = NH - 4 * R0;                   // first new row inside group K's 16 rows
                 static_assert(((NKT + tn) >> 2) == K && lo == 4 * bt + i0 && tn >= 0 && tn < kOneNTR, "step outside its epoch");
+                // the lanes in which the selects below read C or cinv are the lanes that factored S + noise
+                static_assert(OneRootLanes<TT>::value ==
+                                  (((i0 >= 2 && tn + 1 < kOneNTR) ? one_pat_root_lanes<OnePatReach<i0, bt>>() : 0ull) |
+                                   one_pat_root_lanes<OnePatDiag<lo>>() | one_pat_root_lanes<OnePatInvRow<lo>>() |
+                                   one_pat_root_lanes<OnePatInvCol<lo>>() |
+                                   ((K < KLAST && lo + 3 > 16) ? (one_pat_root_lanes<OnePatDiag<lo - 16>>() | one_pat_root_lanes<OnePatInvRow<lo - 16>>() |
+                                                                one_pat_root_lanes<OnePatInvCol<lo - 16>>())
+                                                             : 0ull)),
+                              "OneRootLanes (tools/gen_rollout_one.py: root_lanes) against the step's patterns");
 #ifdef GPMPC_ONE_DEBUG
                 if (nhl != NH) g_one_dbg[63 * 64 + lane] = (double)(nhl - NH);   // the invariant n_h == 3 t does not hold
 #endif

@@ -480,6 +480,70 @@ def append_row_masks(r, nh):
     return nib * 0x1111111111111111, row16 * 0x0001000100010001
 
 
+# ---- the lanes of the 3 x 3 root of (S + noise): the static steps run ONE root stream -----------------------------------------
+# The factor C = chol(S + noise) and 1 / diag(C) are read by the append's selects alone (rollout_one.hip: OnePatReach,
+# OnePatDiag, OnePatInvRow, OnePatInvCol for the step's group and, when rows wrap, for the next one), each lane-locally: the lanes
+# that receive one of these values are a function of t.  In them the root stream factors S + noise, in all others S - the root the
+# draw needs, whose slots 1 and 2 are consumed in the lane of the step's point alone.
+KPT0 = 4 + 9                                  # appended point j lives in lane KPT0 + j (behind the N0 + N1 axis lanes)
+KLAST = (NKT + NTR - 1) >> 2                  # the last group that holds diagonal tiles
+
+
+def _new_entry_is_root(ri, rk):
+    """one_new_entry: True where the entry of new row ri against column rk (same origin) is a value of C"""
+    return 0 <= rk <= ri
+
+
+def root_patterns(t):
+    """{pattern name: lanes that receive a value of C or 1 / diag(C)} for the selects step t's block applies"""
+    nh = T_ROWS * t
+    i0, tn, K = nh & 3, nh >> 2, epoch_of(t)
+    bt, lo = (NKT + tn) & 3, nh - 4 * (4 * K - NKT)
+    out = {}
+    if t >= APPEND_STEPS:
+        return out
+
+    def lanes(pred):
+        return sum(1 << l for l in range(64) if pred(l >> 4, (l >> 2) & 3, l & 3))
+
+    def group(tag, LO):
+        out["diag" + tag] = lanes(lambda kq, bm, jq: 0 <= 4 * bm + jq - LO < T_ROWS and _new_entry_is_root(4 * bm + jq - LO, 4 * bm + kq - LO))
+        out["invrow" + tag] = lanes(lambda kq, bm, jq: 0 <= 4 * bm + kq - LO < T_ROWS)
+        out["invcol" + tag] = lanes(lambda kq, bm, jq: 0 <= 4 * bm + jq - LO < T_ROWS)
+
+    if i0 >= 2 and tn + 1 < NTR:
+        out["reach"] = lanes(lambda kq, bm, jq: bm == bt and jq < i0 - 1 and kq >= i0 and _new_entry_is_root(4 + jq - i0, kq - i0))
+    group("", lo)
+    if K < KLAST and lo + T_ROWS > 16:
+        group("1", lo - 16)
+    return out
+
+
+def root_lanes(t):
+    """A_t: the lanes in which step t's root stream factors S + noise"""
+    m = 0
+    for v in root_patterns(t).values():
+        m |= v
+    return m
+
+
+def root_draw_lane(t):
+    """r_t: the lane the draw's slots 1 and 2 are taken from - the lane of the step's point when it factors S, the highest
+    lane that does otherwise"""
+    a = root_lanes(t)
+    if not (a >> (KPT0 + t)) & 1:
+        return KPT0 + t
+    return max(l for l in range(64) if not (a >> l) & 1)
+
+
+def emit_root_lanes(f):
+    f.write("// ---- the root stream of static step t: lanes that factor S + noise (every other lane factors S), the draw's lane ---------\n")
+    f.write("template <int TS> struct OneRootLanes;\n")
+    for t in range(APPEND_STEPS + 1):
+        f.write(f"template <> struct OneRootLanes<{t}> {{ static constexpr unsigned long long value = 0x{root_lanes(t):016x}ull; "
+                f"static constexpr int draw = {root_draw_lane(t)}; }};\n")
+
+
 def emit_append(f):
     f.write("// ---- the append of step t, n_h = 3 t: the steps of an epoch and the EXEC masks of the panel writes as constants ------------\n")
     f.write(f"constexpr int kOneAppendSteps = {APPEND_STEPS};\n")
@@ -572,6 +636,7 @@ def emit(f):
     disp("one_hset_gd", "void", "double v", "v", m.gd)
     disp("one_touch_gd", "void", "OnePanels& P", "P", m.gd)
     emit_append(f)
+    emit_root_lanes(f)
 
 
 def emit_steps(f):
