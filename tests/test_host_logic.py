@@ -10,7 +10,7 @@ import torch
 
 import sampling_gpmpc_amd as sg
 from sampling_gpmpc_amd import _lib
-from tests.helpers import GOLDEN, REPO, load_params
+from tests.helpers import GOLDEN, REPO, load_params, load_tool
 
 
 def g(name):
@@ -200,12 +200,15 @@ def test_inline_asm_dpp_table_reads_have_no_valu_write_hazard():
     """rollout_indep_grid_kernel reads its register-resident tables as the DPP source of inline-asm v_fmac_f64_dpp; the
     compiler cannot insert the two wait states a VALU-written DPP source needs into inline asm, so the ISA is scanned
     for a write of a table register right in front of such a read (tools/check_dpp_hazard.py)."""
-    import subprocess, sys, shutil
+    import shutil
     if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
         pytest.skip("hipcc not available")
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "tools", "check_dpp_hazard.py")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    isa, hz = load_tool("isa"), load_tool("check_dpp_hazard")
+    assert hz.SOURCES == ["rollout_indep.hip", "rollout_tiles.hip", "rollout_one.hip", "joint_chol.hip"]
+    for src in hz.SOURCES:                                              # each as csrc/build.py compiles it; the script's exit code
+        counts, problems = hz.check(isa.functions(open(isa.compile_to_isa(src)).read()), src)
+        print(f"{src}: {counts['dpp']} DPP broadcast reads and {counts['mfma']} MFMAs checked, {len(problems)} hazard(s)")
+        assert (counts["dpp"] or counts["mfma"]) and problems == [], (src, problems[:20])
 
 
 def test_on_disk_formats_are_read_by_the_reference_loaders(tmp_path):

@@ -1,19 +1,15 @@
 """The EXEC masks tools/gen_rollout_one.py writes into rollout_one_gen.inc as constants (append_row_masks) against a brute-force
 evaluation, lane by lane, of the run-time rule they replace; and the steps of the epochs (CPU)."""
-import importlib.util
 import os
 import re
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import REPO, load_tool
 
 
 def _gen():
-    spec = importlib.util.spec_from_file_location("gen_rollout_one", os.path.join(REPO, "tools", "gen_rollout_one.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_tool("gen_rollout_one")
 
 
 def _rule(r, n_h, b):

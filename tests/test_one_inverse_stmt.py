@@ -6,21 +6,16 @@ is an ordinary register and differs from B - a Gram product multiplies a registe
 gd[K]'s register pair stand exactly once in the statement, in front of the first MFMA that reads gd[K] as its A operand: on
 every path through the statement, because they stand in front of its first branch.  The statement of K = 2 holds none of them.
 """
-import importlib.util
 import io
-import os
 import re
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import load_tool
 
 
 def _gen():
-    spec = importlib.util.spec_from_file_location("gen_rollout_one", os.path.join(REPO, "tools", "gen_rollout_one.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_tool("gen_rollout_one")
 
 
 @pytest.fixture(scope="module")

@@ -10,13 +10,9 @@ cross compile with csrc/build.py's flags and -DGPMPC_ONE_PHASE_MARKS, read by to
   * the marked build has no scratch, spills nothing and stays within 252 VGPRs + 244 AGPRs (tests/test_one_steps_isa.py checks the
     shipped build's resources, the AGPR rule and the DPP / MFMA distances).
 """
-import importlib.util
-import os
-import re
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import load_tool
 
 # the parent commit: (VALU, v_cmp, v_cndmask_b32) of the static body of step t
 PARENT = [(279, 12, 27), (278, 12, 23), (291, 12, 23), (293, 12, 23), (288, 12, 23), (312, 12, 23), (324, 12, 23), (319, 12, 23),
@@ -27,10 +23,8 @@ PARENT = [(279, 12, 27), (278, 12, 23), (291, 12, 23), (293, 12, 23), (288, 12, 
 
 @pytest.fixture(scope="module")
 def marked():
-    spec = importlib.util.spec_from_file_location("one_phase_mix", os.path.join(REPO, "tools", "one_phase_mix.py"))
-    mix = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mix)
-    path = mix.compile_to_isa(mix.CSRC)
+    mix = load_tool("one_phase_mix")
+    path = mix.compile_to_isa()
     return path, mix.scan_steps(path)
 
 
@@ -61,19 +55,10 @@ def test_no_body_holds_more_selects_compares_or_valu_than_the_parents(marked):
 
 def test_marked_build_without_scratch_or_spills(marked):
     path, _ = marked
-    cur, meta = None, {}
-    for raw in open(path):
-        t = raw.strip()
-        m = re.match(r"^\.name:\s+(\S+)$", t)
-        if m:
-            cur = meta.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"^\.(\w+):\s+(\d+)$", t)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    ks = [k for k, v in meta.items() if "rollout_one_steps_kernel" in k and "vgpr_count" in v]
+    meta = load_tool("isa").metadata(open(path).read())
+    ks = [k for k in meta if "rollout_one_steps_kernel" in k]
     assert len(ks) == 1
     k = meta[ks[0]]
-    print({x: k.get(x) for x in ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")})
+    print({x: k[x] for x in ("vgpr_count", "agpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")})
     assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0
-    assert k["vgpr_count"] <= 252 + 244 and k.get("agpr_count", 244) <= 244
+    assert k["vgpr_count"] <= 252 + 244 and k["agpr_count"] <= 244

@@ -12,19 +12,16 @@ factor it holds lies in the step's three new rows and, for an entry of L, in one
     all others r_t is the point's lane itself;
   * the committed rollout_one_gen.inc holds exactly these constants (the kernel static_asserts them against its patterns).
 """
-import importlib.util
 import os
 import re
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import REPO, load_tool
+
 NKT, NTR, T_ROWS, KPT0 = 9, 22, 3, 13
 
 
 def _gen():
-    spec = importlib.util.spec_from_file_location("gen_rollout_one", os.path.join(REPO, "tools", "gen_rollout_one.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_tool("gen_rollout_one")
 
 
 def _lane(kq, bm, jq):

@@ -1,46 +1,29 @@
 """The sample phase of rollout_one_kernel's step (between the marks "Gram + extract" and "sample" of tools/one_phase_mix.py) after
 the bookkeeping left its spine (profiles/one_spine.md): one exponent formula for axis lanes and point lanes instead of two EXEC
 regions, the INFO_VAR_CLAMPED test as a running minimum that is read once behind the step loop, the variance floor in the cold
-block.  CPU only: hipcc cross-compiles the LEAN instantiation with the phase marks (about 8 s, once per module).
+block.  CPU only: hipcc cross-compiles rollout_one.hip with the phase marks (tools/isa.py: about a minute, once per pytest process
+whichever test asks first).
 
 Bounds: the counts of the commit before this change (profiles/one_append_steps.md, "change" table: 216 instructions in the
 epoch K = 2, 207 in every later one); the phase has to stay below them.
 """
-import importlib.util
-import os
 import re
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import load_tool
+
 PARENT_SAMPLE = {2: 216, 3: 207, 4: 207, 5: 207, 6: 207, 7: 207}
 LEAN = "ILi4ELi0ELb1EEE"
-
-
-def _mix():
-    spec = importlib.util.spec_from_file_location("one_phase_mix", os.path.join(REPO, "tools", "one_phase_mix.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 @pytest.fixture(scope="module")
 def sample_phases():
     """{epoch K: [instruction text, ...]} of the sample phase, by the attribution rule of one_phase_mix.scan: what stands between
     two marks belongs to the phase the second one ends; the epoch advances at every mark "7"."""
-    mix = _mix()
-    path = mix.compile_to_isa(mix.CSRC)
-    phases, cur, inside, started, k = {}, [], False, False, mix.KFIRST
-    for raw in open(path):
-        t = raw.strip()
-        m = re.match(r"^(_Z\w+):", t)
-        if m:
-            inside = "rollout_one_kernel" in m.group(1) and LEAN in m.group(1)
-            continue
-        if not inside:
-            continue
-        if t.startswith("; codeLenInByte"):
-            break
+    mix, isa = load_tool("one_phase_mix"), load_tool("isa")
+    phases, cur, started, k = {}, [], False, mix.KFIRST
+    for _, t, _ in mix.kernel_lines(mix.compile_to_isa(), lambda name: "rollout_one_kernel" in name and LEAN in name):
         m = re.match(r"^; one_phase_(\w+) (\w+)", t)
         if m:
             kind, what = m.groups()
@@ -53,8 +36,8 @@ def sample_phases():
                 k += 1
             cur = []
             continue
-        code = t.split(";")[0].strip()
-        if started and code and not code.startswith(".") and not code.endswith(":"):
+        code = isa.instruction(t)
+        if started and code is not None:
             cur.append(code)
     return phases
 

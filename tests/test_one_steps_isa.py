@@ -1,5 +1,5 @@
 """The ISA of rollout_one_steps_kernel - one body per step index, laid out as a straight line (csrc/rollout_one.hip).  CPU only:
-hipcc cross-compiles rollout_one.hip twice, as csrc/build.py ships it (resources, the AGPR and hazard checks) and with
+hipcc cross-compiles rollout_one.hip (tools/isa.py: once per flavour and pytest process), as csrc/build.py ships it (resources, the AGPR and hazard checks) and with
 -DGPMPC_ONE_PHASE_MARKS (tools/one_phase_mix.py: scan_steps reads the steps' own marks) for the shape of the spine:
 
   * the shipped build has exactly one rollout_one_steps_kernel, without scratch and without a spilled register, within
@@ -12,81 +12,49 @@ hipcc cross-compiles rollout_one.hip twice, as csrc/build.py ships it (resources
     spine is read up to their entry;
   * a body's solve statement holds no branch at all, and no body compares against the row count.
 """
-import importlib.util
-import os
 import re
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import load_tool
+
 STEPS_NAME = "rollout_one_steps_kernel"
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REPO, "tools", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+isa = load_tool("isa")
 
 
 @pytest.fixture(scope="module")
 def shipped():
-    return _load("check_one_agpr").compile_to_isa()
+    return open(isa.compile_to_isa("rollout_one.hip")).read()
 
 
 @pytest.fixture(scope="module")
 def marked():
-    mix = _load("one_phase_mix")
-    path = mix.compile_to_isa(mix.CSRC)
+    mix = load_tool("one_phase_mix")
+    path = mix.compile_to_isa()
     return path, mix.scan_steps(path)
 
 
-def _meta(path):
-    """{kernel name: {key: int}} from the .amdhsa metadata notes"""
-    out, cur = {}, None
-    for raw in open(path):
-        t = raw.strip()
-        m = re.match(r"^\.name:\s+(\S+)$", t)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"^\.(\w+):\s+(\d+)$", t)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return out
-
-
 def test_one_steps_kernel_without_scratch_or_spills(shipped):
-    meta = {k: v for k, v in _meta(shipped).items() if "vgpr_count" in v}
+    meta = isa.metadata(shipped)
     steps = [k for k in meta if STEPS_NAME in k]
     loops = [k for k in meta if "rollout_one_kernel" in k]
-    print({k: (v["vgpr_count"], v.get("agpr_count"), v["private_segment_fixed_size"]) for k, v in meta.items()})
+    print({k: (v["vgpr_count"], v["agpr_count"], v["private_segment_fixed_size"]) for k, v in meta.items()})
     assert len(steps) == 1 and len(loops) == 2
     assert not [k for k in steps if "rollout_one_kernel" in k]
     for k in steps + loops:
         assert meta[k]["private_segment_fixed_size"] == 0, k
         assert meta[k]["vgpr_spill_count"] == 0 and meta[k]["sgpr_spill_count"] == 0, k
     assert meta[steps[0]]["vgpr_count"] <= 252 + 244
-    assert meta[steps[0]].get("agpr_count", 244) <= 244
+    assert meta[steps[0]]["agpr_count"] <= 244
 
 
-def test_compiler_leaves_the_panels_alone_and_distances_hold(shipped, tmp_path):
-    agpr = _load("check_one_agpr")
-    # the new kernel alone: its text from the function's label to its end
-    text, keep = [], False
-    for raw in open(shipped):
-        if re.match(r"^_Z\w+:", raw):
-            keep = STEPS_NAME in raw
-        if keep:
-            text.append(raw)
-        if keep and raw.startswith(".Lfunc_end"):
-            keep = False
-    p = tmp_path / "rollout_one_steps.s"                            # (the file name selects the rules of rollout_one.hip)
-    p.write_text("".join(text))
-    n_asm, n_out, problems = agpr.check(str(p))
+def test_compiler_leaves_the_panels_alone_and_distances_hold(shipped):
+    alone = [f for f in isa.functions(shipped) if STEPS_NAME in f[0]]      # the new kernel alone
+    assert len(alone) == 1
+    n_asm, n_out, problems = load_tool("check_one_agpr").check(alone)
     print(f"{n_asm} instructions inside asm statements, {n_out} compiler-generated, {len(problems)} touch an AGPR or spill")
     assert n_asm > 10000 and n_out > 10000 and problems == []
-    counts, hazards = _load("check_dpp_hazard").check(str(p))
+    counts, hazards = load_tool("check_dpp_hazard").check(alone, "rollout_one.hip")
     print(f"{counts['dpp']} DPP reads and {counts['mfma']} MFMAs checked, {len(hazards)} hazard(s)")
     assert counts["mfma"] > 1000 and hazards == []
 
@@ -98,9 +66,10 @@ FAR = re.compile(r"^s_add_u32 .*\((\.LBB\w+)-\.Lpost_getpc\d+\)")
 def test_spine_is_a_straight_line(marked):
     path, (steps, tail, code_len, spine) = marked
     assert list(steps) == list(range(30))
+    lines = [x for _, fl in isa.functions(open(path).read()) for x in fl]        # of every function of the file
     labels = {}
-    for ln, raw in enumerate(open(path), 1):
-        m = re.match(r"^(\.LBB\w+):", raw.strip())
+    for ln, tx, _ in lines:
+        m = re.match(r"^(\.LBB\w+):", tx)
         if m:
             labels.setdefault(m.group(1), []).append(ln)
     lo, hi = spine[0][0], spine[-1][0]
@@ -125,20 +94,19 @@ def test_spine_is_a_straight_line(marked):
         if code.startswith("s_cbranch") and t is not None:
             cond[t] += 1
     # a solve statement = the asm statement that holds the body's MFMAs with a panel operand: no control flow inside
-    in_asm, has_panel, ctrl = False, False, []
-    for raw in open(path).read().split("\n")[lo - 1:hi]:
-        tx = raw.strip()
-        if tx.startswith(";;#ASMSTART"):
-            in_asm, has_panel, ctrl = True, False, []
-        elif tx.startswith(";;#ASMEND"):
-            if has_panel and ctrl:
-                in_solve.append(ctrl)
-            in_asm = False
-        elif in_asm:
+    has_panel, ctrl = False, []
+    for ln, tx, in_asm in lines:
+        if not lo <= ln <= hi:
+            continue
+        if in_asm:
             if re.match(r"^v_mfma_f64_4x4x4_4b_f64 v\[\d+:\d+\], a\[", tx):
                 has_panel = True
             if tx.startswith(("s_cbranch", "s_branch", "s_cmp", "s_setpc")) or re.match(r"^\.L\w+:", tx):
                 ctrl.append(tx)
+        else:                                                       # a statement's bounds, or what stands between two
+            if has_panel and ctrl:
+                in_solve.append(ctrl)
+            has_panel, ctrl = False, []
     print(f"codeLenInByte = {code_len}; conditional branches per body: {sorted(set(cond.values()))}; "
           f"instructions per body {min(c['all'] for c in steps.values())} .. {max(c['all'] for c in steps.values())}, "
           f"{tail['all']} behind the bodies")

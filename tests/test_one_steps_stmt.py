@@ -8,22 +8,15 @@ v_accvgpr_write, in the same order with the same operands, the stages of the rid
 statements hold no branch, no compare and no label, and pass the distance rules of tools/check_dpp_hazard.py (a row reached by
 fall-through drops the padded head the branched-to copy carries: the rules say whether what is left suffices).
 """
-import importlib.util
 import io
 import os
 import re
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import REPO, load_tool
+
 STEPS = list(range(30))
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REPO, "tools", name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
 
 
 def _lines(text):
@@ -35,7 +28,7 @@ def _lines(text):
 
 @pytest.fixture(scope="module")
 def gen():
-    g = _load("gen_rollout_one")
+    g = load_tool("gen_rollout_one")
     m = g.Map()
     member = lambda r, gg: f"P.p[{m.idx[('p', r, gg)]}]"
     run, static, operands = {}, {}, {}
@@ -106,15 +99,11 @@ def test_static_statement_has_no_branch_label_or_row_count(gen, t):
     assert '"s"(' not in operands[t] and "nh" not in operands[t] and '"scc"' not in operands[t]
 
 
-def test_static_statements_pass_the_distance_rules(gen, tmp_path):
+def test_static_statements_pass_the_distance_rules(gen):
     _, _, static, _ = gen
-    chk = _load("check_dpp_hazard")
-    p = tmp_path / "rollout_one_static_stmts.s"                       # (the file name selects the rules of rollout_one.hip)
-    with open(p, "w") as f:
-        for t in STEPS:
-            f.write(f"_Zone_solve_t_{t}:\n")
-            f.write("\n".join("\t" + x for x in static[t]) + "\n")
-    counts, problems = chk.check(str(p))
+    # each statement as a function of its own: (name, [(line number, text, inside an asm statement)])
+    stmts = [(f"one_solve_t{t}", [(i, x, True) for i, x in enumerate(static[t], 1)]) for t in STEPS]
+    counts, problems = load_tool("check_dpp_hazard").check(stmts, "rollout_one.hip")
     print(f"{counts['dpp']} DPP reads and {counts['mfma']} MFMAs checked, {len(problems)} hazard(s)")
     for k, ln, code, rule, rg in problems[:10]:
         print(f"  [{rule}] {k} line {ln}: `{code}` <- {rg}")
@@ -126,9 +115,7 @@ def test_build_writes_the_statements_file_and_depends_on_it(gen):
     """rollout_one_steps_gen.inc is not committed: csrc/build.py writes it when the module is loaded and before it compiles, and
     treats it as a header of rollout_one.hip"""
     g = gen[0]
-    spec = importlib.util.spec_from_file_location("gpmpc_build", os.path.join(REPO, "sampling_gpmpc_amd", "csrc", "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
+    b = load_tool("isa").build
     assert list(b.BUILD_GENERATED) == ["rollout_one_steps_gen.inc"] and "rollout_one_steps_gen.inc" in b.HEADERS
     f = io.StringIO()
     g.emit_steps(f)

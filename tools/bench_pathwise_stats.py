@@ -13,7 +13,6 @@ around work that ends in a synchronise.  Reported: median and min .. max of the 
 each side, and the fused kernel's VGPR / LDS / scratch figures read from the code object in libgpmpc_hip.so.  Needs a HIP device."""
 import argparse
 import os
-import re
 import struct
 import subprocess
 import sys
@@ -24,7 +23,9 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import isa                                                                   # noqa: E402  (beside this script)
 import sampling_gpmpc_amd as sg                                              # noqa: E402
 from sampling_gpmpc_amd import _lib                                          # noqa: E402
 from sampling_gpmpc_amd.pathwise import (PathwiseSamples, draw_omega, merge_tube_stats, pathwise_tube_stats,   # noqa: E402
@@ -60,14 +61,12 @@ def kernel_figures(lib_path=_lib.LIB_PATH):
                     f.write(blob[at + off:at + off + size])
                     f.flush()
                     notes = subprocess.run([READELF, "--notes", f.name], capture_output=True, text=True, check=True).stdout
-                for entry in notes.split("- .agpr_count:")[1:]:
-                    get = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", entry).group(1))
-                    name = re.search(r"\.name:\s+(\S+)", entry).group(1)
+                for name, m in isa.metadata(notes).items():
                     if "pathwise_tube_stats" in name:
-                        out[name] = (get("vgpr_count"), int(entry.split()[0]), get("group_segment_fixed_size"), get("private_segment_fixed_size"),
-                                     get("sgpr_spill_count"), get("vgpr_spill_count"))
+                        out[name] = (m["vgpr_count"], m["agpr_count"], m["group_segment_fixed_size"], m["private_segment_fixed_size"],
+                                     m["sgpr_spill_count"], m["vgpr_spill_count"])
             at = blob.find(magic, at + len(magic))
-    except (OSError, subprocess.CalledProcessError, AttributeError, struct.error):
+    except (OSError, subprocess.CalledProcessError, KeyError, struct.error):
         return {}
     return out
 

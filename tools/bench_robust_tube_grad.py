@@ -16,7 +16,7 @@ round times ``--iters`` back-to-back calls between two events), with the minimum
   compared with autograd's before anything is timed.
 
 The register table is read from the metadata of the code objects hipcc emits for ``robust_tube_grad.hip`` and ``moments_grad.hip``
-with the flags of csrc/build.py (``--registers-only`` stores it as JSON, a timing run embeds that file or compiles itself);
+with the flags of csrc/build.py through tools/isa.py (``--registers-only`` stores it as JSON, a timing run embeds that file or compiles itself);
 ``--bit-identity`` names a markdown file whose text is copied into the report (the record of the moment VJP's bit-for-bit check).
 Timing needs a HIP device."""
 import argparse
@@ -24,9 +24,7 @@ import json
 import os
 import re
 import statistics
-import subprocess
 import sys
-import tempfile
 
 import torch
 
@@ -39,7 +37,6 @@ from sampling_gpmpc_amd.workloads import load_params                         # n
 
 F64 = torch.float64
 B, BETA = 1024, 2.0
-CSRC = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
 KERNELS = (("robust_tube_grad.hip", "robust_tube_vjp_kernel"), ("moments_grad.hip", "moment_rollout_vjp_kernel"))
 FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_spill_count", ".vgpr_spill_count", ".private_segment_fixed_size", ".group_segment_fixed_size")
 
@@ -49,33 +46,22 @@ FIELDS = (".vgpr_count", ".agpr_count", ".sgpr_spill_count", ".vgpr_spill_count"
 # ---------------------------------------------------------------------------------------------------------------------
 def register_table():
     """{kernel: {"<env, NRP, HG>": {field: value}}} for the two VJP kernels."""
-    sys.path.insert(0, CSRC)
-    import build as csrc_build
+    import isa
     out = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        for src, kernel in KERNELS:
-            asm = os.path.join(tmp, src.replace(".hip", ".s"))
-            cmd = [csrc_build.HIPCC, "-x", "hip", "-S", "--cuda-device-only", os.path.join(CSRC, src), "-o", asm] + csrc_build.FLAGS \
-                + csrc_build.EXTRA_FLAGS.get(src, [])
-            subprocess.run(cmd, check=True, capture_output=True)
-            text = open(asm).read()
-            meta = text[text.index("amdhsa.kernels:"):]
-            rows = {}
-            for block in meta.split("  - .agpr_count:")[1:]:
-                block = ".agpr_count:" + block
-                name = re.search(r"\.name:\s+(\S+)", block).group(1)
-                m = re.search(kernel + r"ILi(\d+)ELi(\d+)ELb([01])EE", name)
-                if not m:
-                    continue
+    for src, kernel in KERNELS:
+        rows = {}
+        for name, fields in isa.metadata(open(isa.compile_to_isa(src)).read()).items():
+            m = re.search(kernel + r"ILi(\d+)ELi(\d+)ELb([01])EE", name)
+            if m:
                 key = f"<{m.group(1)}, {m.group(2)}, {'true' if m.group(3) == '1' else 'false'}>"
-                rows[key] = {f: int(re.search(re.escape(f) + r":\s+(\d+)", block).group(1)) for f in FIELDS}
-            out[kernel] = rows
+                rows[key] = {f: fields[f[1:]] for f in FIELDS}
+        out[kernel] = rows
     return out
 
 
 def write_registers(f, regs):
     f.write("## Registers and scratch\n\n"
-            "From the metadata of the code objects (`hipcc -x hip -S --cuda-device-only` with the flags of `csrc/build.py`; the form of "
+            "From the metadata of the code objects (`tools/isa.py`: `hipcc -S` of the device side with the flags of `csrc/build.py`; the form of "
             "`profiles/moments_step_isa.md`): `<env, NRP, HG>` with env 0 = pendulum1D, 1 = car.  VGPR counts the AGPRs in (above 256 the "
             "excess lives in AGPRs, moved by `v_accvgpr` instead of going to memory); private B is the scratch (private segment) size.\n\n")
     rv, mv = regs["robust_tube_vjp_kernel"], regs["moment_rollout_vjp_kernel"]

@@ -21,27 +21,18 @@ are written a phase earlier: D1 can only arise if the register allocator puts a 
 asm statement - which is exactly what this script looks for in the ISA hipcc produced.  M1-M4 guard the MFMA chains of
 rollout_tiles.hip (statements open with s_nop 1 and close with s_nop 5; a regression in the generator shows up here).
 
-    python tools/check_dpp_hazard.py [file.s ...]          exit code 0 = clean
+Every file is scanned as csrc/build.py compiles it (tools/isa.py).
+
+    python tools/check_dpp_hazard.py [file.s ...]          exit code 0 = clean (a file.s takes the rules its basename names)
 """
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))     # isa.py stands beside this file, however it is loaded
+import isa                                                          # noqa: E402
+
 SOURCES = ["rollout_indep.hip", "rollout_tiles.hip", "rollout_one.hip", "joint_chol.hip"]
-EXTRA = {"rollout_one.hip": ["-mllvm", "-disable-machine-licm"]}        # as csrc/build.py compiles it
-
-
-def compile_to_isa(src):
-    out = os.path.join(tempfile.mkdtemp(prefix="gpmpc_isa_"), src.replace(".hip", ".s"))
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "-S", "--cuda-device-only",
-           os.path.join(CSRC, src), "-o", out, "--offload-arch=gfx950", "-O3", "-std=c++17",
-           "-fno-gpu-rdc", "-ffp-contract=on", "-I", os.path.join(REPO, "include"), "-I", CSRC] + EXTRA.get(src, [])
-    subprocess.run(cmd, check=True, capture_output=True)
-    return out
 
 
 def regs(tok):
@@ -61,75 +52,72 @@ RELAXED_FILES = ("rollout_one",)
 DPP_ONLY_FILES = ("joint_chol", "jc")
 
 
-def check(path, mfma_ws=None):
+def check(functions, source, mfma_ws=None):
+    """functions: (name, lines) as isa.functions yields them - a whole file's, one kernel's, or statements that never were a file;
+    source: the kernel file (or an .s named after it) whose rule set applies"""
     if mfma_ws is None:     # STRICT by default: an MFMA is one wait state like any instruction; relaxed only for the named files
-        mfma_ws = MFMA_WS_RELAXED if os.path.basename(path).startswith(RELAXED_FILES) else 1
+        mfma_ws = MFMA_WS_RELAXED if os.path.basename(source).startswith(RELAXED_FILES) else 1
     counts = {"dpp": 0, "mfma": 0}
-    dpp_only = os.path.basename(path).startswith(DPP_ONLY_FILES)
-    problems, kernel = [], None
-    window = []          # preceding instructions, newest last: (wait states, wait states for M2-M4, kind, set of ('v'|'a', n) written)
-    for ln, raw in enumerate(open(path), 1):
-        t = raw.strip()
-        if re.match(r"^_Z\w+:", t):
-            kernel, window = t.split(":")[0], []
-            continue
-        if not t or t.startswith(";") or t.startswith(".") or t.endswith(":"):
-            continue
-        code = t.split(";")[0].strip()
-        if not code:
-            continue
-        op = code.split()[0]
-        toks = re.findall(TOK, code)
-        ops = [regs(x) for x in toks]
-        tagged = [{(f, n) for n in ns} for f, ns in ops]
+    dpp_only = os.path.basename(source).startswith(DPP_ONLY_FILES)
+    problems = []
+    for kernel, lines in functions:
+        window = []      # preceding instructions, newest last: (wait states, wait states for M2-M4, kind, set of ('v'|'a', n) written)
+        for ln, t, _ in lines:
+            code = isa.instruction(t)
+            if code is None:
+                continue
+            op = code.split()[0]
+            toks = re.findall(TOK, code)
+            ops = [regs(x) for x in toks]
+            tagged = [{(f, n) for n in ns} for f, ns in ops]
 
-        def scan(read, rule, need, kinds):
-            ws = 0
-            for states, mstates, kind, written in reversed(window):
-                if ws >= need:
-                    return
-                if kind in kinds and (written & read):
-                    problems.append((kernel, ln, code, rule, sorted(written & read)))
-                    return
-                ws += mstates if rule in ("M2", "M3", "M4") else states
+            def scan(read, rule, need, kinds):
+                ws = 0
+                for states, mstates, kind, written in reversed(window):
+                    if ws >= need:
+                        return
+                    if kind in kinds and (written & read):
+                        problems.append((kernel, ln, code, rule, sorted(written & read)))
+                        return
+                    ws += mstates if rule in ("M2", "M3", "M4") else states
 
-        is_mfma = op.startswith("v_mfma")
-        if (op == "v_fmac_f64_dpp" and "row_newbcast" in code) or op == "v_mov_b32_dpp":
-            counts["dpp"] += 1
-            if len(tagged) > 1:
-                scan(tagged[1], "D1", 2, ("valu",))
-        if is_mfma and dpp_only:
-            counts["mfma"] += 1
-        elif is_mfma:
-            counts["mfma"] += 1
-            srcs = tagged[1:]
-            for i, rd in enumerate(srcs):
-                scan(rd, "M1", 2, ("valu",))
-                scan(rd, "M2" if i == 2 else "M3", 4 if i == 2 else 6, ("mfma",))
-        else:
-            reads = set().union(*tagged[(1 if (op.startswith("v_") or op.startswith("ds_read") or op.startswith("buffer_load")
-                                               or op.startswith("global_load") or op.startswith("scratch_load")) else 0):]) if tagged else set()
-            if reads and not dpp_only:
-                scan(reads, "M4", 6, ("mfma",))
-        if op == "s_nop":
-            m = re.search(r"s_nop\s+(\d+)", code)
-            n = int(m.group(1)) + 1 if m else 1
-            window.append((n, n, "nop", set()))
-        elif is_mfma:
-            window.append((1, mfma_ws, "mfma", tagged[0] if tagged else set()))
-        elif op.startswith("v_") and tagged:
-            window.append((1, 1, "valu", tagged[0]))      # VALU: the destination is the first operand
-        else:
-            window.append((1, 1, "other", set()))
-        window = window[-12:]
+            is_mfma = op.startswith("v_mfma")
+            if (op == "v_fmac_f64_dpp" and "row_newbcast" in code) or op == "v_mov_b32_dpp":
+                counts["dpp"] += 1
+                if len(tagged) > 1:
+                    scan(tagged[1], "D1", 2, ("valu",))
+            if is_mfma and dpp_only:
+                counts["mfma"] += 1
+            elif is_mfma:
+                counts["mfma"] += 1
+                srcs = tagged[1:]
+                for i, rd in enumerate(srcs):
+                    scan(rd, "M1", 2, ("valu",))
+                    scan(rd, "M2" if i == 2 else "M3", 4 if i == 2 else 6, ("mfma",))
+            else:
+                reads = set().union(*tagged[(1 if (op.startswith("v_") or op.startswith("ds_read") or op.startswith("buffer_load")
+                                                   or op.startswith("global_load") or op.startswith("scratch_load")) else 0):]) if tagged else set()
+                if reads and not dpp_only:
+                    scan(reads, "M4", 6, ("mfma",))
+            if op == "s_nop":
+                m = re.search(r"s_nop\s+(\d+)", code)
+                n = int(m.group(1)) + 1 if m else 1
+                window.append((n, n, "nop", set()))
+            elif is_mfma:
+                window.append((1, mfma_ws, "mfma", tagged[0] if tagged else set()))
+            elif op.startswith("v_") and tagged:
+                window.append((1, 1, "valu", tagged[0]))      # VALU: the destination is the first operand
+            else:
+                window.append((1, 1, "other", set()))
+            window = window[-12:]
     return counts, problems
 
 
 if __name__ == "__main__":
-    paths = sys.argv[1:] or [compile_to_isa(s) for s in SOURCES]
+    paths = sys.argv[1:] or [isa.compile_to_isa(s) for s in SOURCES]
     bad = 0
     for src in paths:
-        c, probs = check(src)
+        c, probs = check(isa.functions(open(src).read()), src)
         print(f"{src}: {c['dpp']} DPP broadcast reads and {c['mfma']} MFMAs checked, {len(probs)} hazard(s)")
         for k, ln, code, rule, rg in probs[:20]:
             print(f"  [{rule}] {k} line {ln}: `{code}` <- {rg}")

@@ -15,8 +15,10 @@ import subprocess
 import sys
 import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))     # isa.py stands beside this file, however it is loaded
+import isa                                                          # noqa: E402
+from isa import build                                               # noqa: E402
+
 LLVM = "/opt/rocm/lib/llvm/bin"
 NT = 26
 
@@ -24,9 +26,9 @@ NT = 26
 def symbols():
     with tempfile.TemporaryDirectory() as d:
         obj, dev = os.path.join(d, "jm.o"), os.path.join(d, "jm_gfx950.o")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-x", "hip", "-c", os.path.join(CSRC, "joint_mfma.hip"), "-o", obj, "--offload-arch=gfx950",
-                        "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-ffp-contract=on", "-I", os.path.join(REPO, "include"), "-I", CSRC,
-                        "--cuda-device-only", "-w"], check=True)
+        # csrc/build.py's own command for this file (the symbols are read from the object, so not through isa.compile_to_isa)
+        subprocess.run([build.HIPCC, "-x", "hip", "-c", os.path.join(isa.CSRC, "joint_mfma.hip"), "-o", obj, "--cuda-device-only"]
+                       + build.FLAGS + build.EXTRA_FLAGS["joint_mfma.hip"], check=True)
         subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + obj,
                         "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + dev], check=True)
         out = subprocess.run([os.path.join(LLVM, "llvm-objdump"), "-t", dev], check=True, capture_output=True, text=True).stdout

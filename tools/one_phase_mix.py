@@ -17,32 +17,23 @@ the blocks of the epoch, and `blocks` says how many there are - a step runs ONE 
     python tools/one_phase_mix.py --steps                   rollout_one_steps_kernel: the mix of every static step's body (scan_steps)
 """
 import collections
-import importlib.util
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "sampling_gpmpc_amd", "csrc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))     # isa.py stands beside this file, however it is loaded
+import isa                                                          # noqa: E402
+
+CSRC = isa.CSRC
 PHASES = {"0": "entries: LDS reads", "1": "entries: products + writes", "2": "solve", "3": "Gram + extract", "4": "sample",
           "5": "append: panel writes", "6": "append: diagonal tiles", "7": "state"}
 COLS = ["VALU", "v_cmp", "v_cndmask", "DPP", "v_accvgpr_write", "MFMA", "SALU", "branch", "s_nop", "LDS", "wait", "mem"]
 KFIRST = 2
 
 
-def compile_to_isa(csrc):
-    spec = importlib.util.spec_from_file_location("gpmpc_build", os.path.join(CSRC, "build.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
-    out = os.path.join(tempfile.mkdtemp(prefix="gpmpc_mix_"), "rollout_one.s")
-    # (the quoted includes of rollout_one.hip are found beside it first: --src compiles that directory's headers)
-    flags = [f for f in b.FLAGS if f != "-fPIC"] + ["-DGPMPC_ONE_PHASE_MARKS"]
-    cmd = [b.HIPCC, "-x", "hip", "-S", "--cuda-device-only", os.path.join(csrc, "rollout_one.hip"), "-o", out] + flags + \
-        b.EXTRA_FLAGS.get("rollout_one.hip", [])
-    subprocess.run(cmd, check=True, capture_output=True)
-    return out
+def compile_to_isa(csrc=CSRC):
+    """the marked flavour: the shared compile with the phase marks switched on"""
+    return isa.compile_to_isa("rollout_one.hip", ("-DGPMPC_ONE_PHASE_MARKS",), csrc)
 
 
 def classes(op, text):
@@ -74,11 +65,18 @@ def classes(op, text):
     return []
 
 
+def kernel_lines(path, want):
+    """the lines (isa.functions) of the kernels of an .s whose mangled name `want` accepts"""
+    for name, lines in isa.functions(open(path).read()):
+        if want(name):
+            yield from lines
+
+
 def scan(path, lean=True):
     want = "ILi4ELi0ELb1EEE" if lean else "ILi4ELi0ELb0EEE"
     table = collections.OrderedDict()           # (epoch label, phase label) -> Counter
     blocks = collections.Counter()              # epoch label -> marks "1" seen (step blocks)
-    inside, cold, epoch = False, False, "prologue"
+    epoch = "prologue"
     pending = collections.Counter()
     code_len = None
 
@@ -88,17 +86,9 @@ def scan(path, lean=True):
         pending = collections.Counter()
 
     k = KFIRST
-    for raw in open(path):
-        t = raw.strip()
-        m = re.match(r"^(_Z\w+):", t)
-        if m:
-            inside = "rollout_one_kernel" in m.group(1) and want in m.group(1)
-            continue
-        if not inside:
-            continue
+    for _, t, _ in kernel_lines(path, lambda name: "rollout_one_kernel" in name and want in name):
         if t.startswith("; codeLenInByte"):
             code_len = int(t.split("=")[1])
-            inside = False
             continue
         m = re.match(r"^; one_phase_(\w+) (\w+)", t)
         if m:
@@ -108,10 +98,8 @@ def scan(path, lean=True):
                 epoch = f"K = {k}"
             elif kind == "cold" and what == "begin":
                 flush((epoch, "(between the marks: loop control, joins)"))
-                cold = True
             elif kind == "cold" and what == "end":
                 flush((epoch, "cold block (clip, repair)"))
-                cold = False
             elif kind == "end":
                 flush((epoch, PHASES[what]))
                 if what == "1":
@@ -120,8 +108,8 @@ def scan(path, lean=True):
                     k += 1
                     epoch = f"K = {k}"
             continue
-        code = t.split(";")[0].strip()
-        if not code or code.startswith(".") or code.endswith(":"):
+        code = isa.instruction(t)
+        if code is None:
             continue
         op = code.split()[0]
         pending.update(classes(op, code))
@@ -137,18 +125,10 @@ def scan_steps(path, n_steps=30):
     the Counter of what stands behind the bodies, codeLenInByte, spine) with spine = [(line number, code, step or None)] of
     everything from the prologue's end to the last body's end, for the checks on the spine's branches."""
     steps, tail, spine = collections.OrderedDict(), collections.Counter(), []
-    inside, cur, done, code_len, started = False, None, False, None, False
-    for ln, raw in enumerate(open(path), 1):
-        t = raw.strip()
-        m = re.match(r"^(_Z\w+):", t)
-        if m:
-            inside = "rollout_one_steps_kernel" in m.group(1)
-            continue
-        if not inside:
-            continue
+    cur, done, code_len, started = None, False, None, False
+    for ln, t, _ in kernel_lines(path, lambda name: "rollout_one_steps_kernel" in name):
         if t.startswith("; codeLenInByte"):
             code_len = int(t.split("=")[1])
-            inside = False
             continue
         if t.startswith("; one_phase_end prologue"):
             started = True
@@ -158,13 +138,11 @@ def scan_steps(path, n_steps=30):
             cur = int(m.group(1))
             steps[cur] = collections.Counter()
             continue
-        code = t.split(";")[0].strip()
-        if not code or code.startswith("."):
+        code = isa.instruction(t)
+        if code is None:
             continue
         if started and not done:
             spine.append((ln, code, cur))
-        if code.endswith(":"):
-            continue
         op = code.split()[0]
         c = tail if (done or cur is None) else steps[cur]
         c.update(classes(op, code))
@@ -176,7 +154,7 @@ def scan_steps(path, n_steps=30):
 
 def main():
     if "--steps" in sys.argv:
-        path = compile_to_isa(CSRC)
+        path = compile_to_isa()
         steps, tail, code_len, _ = scan_steps(path)
         print(f"{path}: rollout_one_steps_kernel<4, pendulum1D>, codeLenInByte = {code_len}\n")
         print("| step | all | " + " | ".join(COLS) + " |")
@@ -184,9 +162,7 @@ def main():
         for t, c in list(steps.items()) + [("behind the bodies", tail)]:
             print(f"| {t} | {c['all']} | " + " | ".join(str(c[k]) for k in COLS) + " |")
         return
-    csrc = CSRC
-    if "--src" in sys.argv:
-        csrc = os.path.abspath(sys.argv[sys.argv.index("--src") + 1])
+    csrc = os.path.abspath(sys.argv[sys.argv.index("--src") + 1]) if "--src" in sys.argv else CSRC
     path = compile_to_isa(csrc)
     table, blocks, code_len = scan(path, lean="--full" not in sys.argv)
     print(f"{path}: rollout_one_kernel<4, pendulum1D, {'LEAN' if '--full' not in sys.argv else 'full'}>, codeLenInByte = {code_len}\n")
