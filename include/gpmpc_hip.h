@@ -1204,6 +1204,72 @@ int     gpmpc_optimistic_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_
                                      void* stream);
 
 /*
+ * gpmpc_rollout_vjp - the reverse-mode derivative (vector-Jacobian product) of the map (x0, u_ff) -> (X_traj, Y) that gpmpc_rollout
+ * computes in GPMPC_MODE_RECONDITIONED with hall_tasks == T == 3, for FIXED base samples z.  With z fixed that map is a deterministic,
+ * almost-everywhere differentiable recursion whose state is the chain's append-row Cholesky factor; the rows of that factor never
+ * change once written, so the final factor holds every step's v = L^-1 k and the sweep needs only the forward's X_traj, Xi, Y, z
+ * and info (the forward is not run again, and it does not matter which kernel of the dispatcher produced them).  One launch, one
+ * workgroup per sample, one wave per output (the generic forward's mapping).  Additive entry points: the ABI version stays 12.
+ * Replaces: nothing the reference has - its sampler (sample_gp under forward_sampling, src/agent.py:629-730) is never differentiated;
+ * this makes a first-order planner on the exact sampler possible next to the pathwise one.
+ *
+ * Two phases per chain:
+ *   1. rebuild: H conditioning-only passes over (Xi, Y) give the factor [L_hr | L_hh], w = L^-1 y and, per step, mu and S.
+ *   2. sweep t = H-1..0 with adjoints Lbar_hr, Lbar_hh, wbar, xibar[0..H):
+ *        ybar[0]  = (B_d(x_t)^T xbar_{t+1})_o (+ g_Y[s,o,t,:] for all three slots);
+ *        rows appended by the step (none at t = H-1): vbar, Cbar, wnbar;  r = C^-T wnbar, ybar += r, mubar -= r,
+ *                   Cbar -= tril(r wn^T), Sbar += chol_adjoint(C, Cbar)        [C = chol(S + diag(noise)), wn = C^-1 (y - mu)]
+ *        the draw, per slot b:  free     mubar_b += ybar_b, Rbar_b: += ybar_b z^T (lower part)
+ *                               clipped  mubar_b += ybar_b, varbar_b -+= ybar_b beta / (2 sqrt(var_b))
+ *                               all-zero mubar_b += ybar_b
+ *                   Sbar += chol_adjoint(R, Rbar), Sbar_bb += varbar_b
+ *        vbar += w mubar^T - v (Sbar + Sbar^T),  wbar[:n] += v mubar
+ *        kbar_h = L_hh^-T vbar_h,  kbar_r = L_rr^-T (vbar_r - L_hr^T kbar_h),  Lbar_hr -= kbar_h v_r^T,  Lbar_hh -= tril(kbar_h v_h^T)
+ *                   (v_r and kbar_r by substitutions with the plan's L_rr, not by products with its stored L_rr^-1: at the car's
+ *                   cond(K_rr + noise) = 1.3e7 the stored inverse costs two digits of the gradient when g_Y is given)
+ *        xibar_t += sum kbar dk/dxi,  xibar_j -= the same for the chain's earlier points j < t (every kernel entry is a function of
+ *                   xi_t - x_j; the real points are constants)
+ *        xbar_t, g_U[s,t] from xibar_t (summed over the outputs) through the adjoints of gp_input, apply_feedback and env_step,
+ *        xbar_t += g_X[s,:,t];   g_x0[s] = xbar_0.
+ * Conventions where the recursion is not differentiable:
+ *   - a variance on its floor (var_b < var_floor) is the constant var_floor: no gradient passes through it (as in
+ *     gpmpc_optimistic_rollout_vjp);
+ *   - the clip branch of a slot is decided by recomputing mu + R z against mu -+ beta sqrt(var); at a tie the slot counts as clipped;
+ *   - a jitter retry of the root is differentiated as taken: the jitter is a constant on the diagonal (the rebuild repeats the chain,
+ *     so it takes the retries the forward took);
+ *   - a sample whose forward info carries GPMPC_INFO_ROOT_FAIL, _NEG_1x1, _TRAIN_CHOL_FAIL or _STATE_FULL, or whose rebuild hits
+ *     one of them, has NaN in all its gradients; info = info_fwd | what the rebuild and the sweep found;
+ *   - a sample with a non-finite x0, u, X_traj, cotangent or computed value has NaN in all its gradients and GPMPC_INFO_NONFINITE;
+ *     no other sample is touched.
+ *   gp, env, plan, X_r, var_zero_thr, beta, Ns, H, x0, x0_per_sample, u_ff, z, z_step_stride     the forward's arguments
+ *   X_traj [dev] (Ns, nx, H+1), Y [dev] (Ns, g_ny, H, T), Xi [dev] (Ns, H, D), info_fwd [dev] (Ns) int32 or NULL    the forward's outputs
+ *   g_X  [dev] (Ns, nx, H+1) or NULL    cotangent of X_traj; NULL is zero
+ *   g_Y  [dev] (Ns, g_ny, H, T) or NULL cotangent of Y; NULL is zero          (both NULL: the gradients are zero)
+ *   g_x0 [dev] (Ns, nx)                 out: d / d x0, per sample
+ *   g_U  [dev] (Ns, H, nu)              out: d / d u_ff, per sample: u_ff is shared and the host sums over Ns (no atomics)
+ *   info [dev] (Ns) int32               out
+ *   workspace                           gpmpc_rollout_vjp_workspace_bytes(gp, Ns, H); a chain's factor and its adjoint are
+ *                                       2 (n_r nh + nh (nh + 1) / 2) doubles with nh = 3 H (pendulum H = 30: 117 KB, car H = 40: 203 KB).
+ *                                       They stay in LDS when the workgroup's g_ny chains and their vectors fit into 160 KiB - 256 B of
+ *                                       dynamic LDS (the pendulum up to H = 35; then the workspace is not touched), otherwise
+ *                                       they live in the workspace.
+ * Reproducibility: a sample's gradient bits do not depend on Ns or on its place in the launch.
+ * Limits: GPMPC_MODE_RECONDITIONED with hall_tasks == T == 3, D == 2, the two environments with and without feedback, no seed
+ * points and no kept factor state, real_has_grad == 0 (value-only real labels, what Agent builds), 3 (H - 1) <= 256 and whatever
+ * else the generic forward accepts for the shape, Ns < 2^31: GPMPC_E_UNSUPPORTED beyond, before any device work.  GPMPC_E_ARG
+ * (before any device work): a bad descriptor, Ns < 0, H < 0, beta < 0 or NaN, and with Ns > 0 NULL plan, X_r, x0, X_traj, g_x0, info,
+ * with H > 0 also NULL u_ff, z, Y, Xi, g_U.  GPMPC_E_WORKSPACE: the workspace is needed and NULL or too small.  Ns == 0: nothing is
+ * launched.  H == 0: g_x0 = g_X[:, :, 0].  No allocation, no host round trip, everything goes to `stream`.
+ */
+size_t  gpmpc_rollout_vjp_workspace_bytes(const gpmpc_gp_desc_t* gp, int64_t Ns, int32_t H);
+int     gpmpc_rollout_vjp(const gpmpc_gp_desc_t* gp, const gpmpc_env_desc_t* env, const void* plan, const double* X_r,
+                          double var_zero_thr, double beta, int64_t Ns, int32_t H, const double* x0, int32_t x0_per_sample,
+                          const double* u_ff, const double* z, int64_t z_step_stride, const double* X_traj, const double* Y,
+                          const double* Xi, const int32_t* info_fwd, const double* g_X /* (Ns, nx, H+1) or NULL */,
+                          const double* g_Y /* (Ns, g_ny, H, T) or NULL */, double* g_x0 /* (Ns, nx) */, double* g_U /* (Ns, H, nu) */,
+                          int32_t* info /* (Ns) */, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * gpmpc_pairwise_lipschitz - the sampled Lipschitz constant of G vector functions over N points: for every group g
  *   out_max[g] = max over i < j of |F[i,g,:] - F[j,g,:]|_2 / (|X[i,:] - X[j,:]|_2 + eps),
  * as a tiled sweep over the N (N - 1) / 2 pairs that never forms an N x N array.  Additive entry points: the ABI version stays 12.

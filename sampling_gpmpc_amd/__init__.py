@@ -25,6 +25,7 @@ from .robust_tube import (RobustTube, robust_tube_rollout, robust_tube_rollout_p
                           robust_tube_rollout_vjp, robust_tube_rollout_vjp_plan, plan_inputs_robust, plan_inputs_robust_plan)
 from .optimistic import (OptimisticTube, optimistic_rollout, optimistic_rollout_plan, optimistic_rollout_vjp,  # noqa: F401
                          optimistic_rollout_vjp_plan, plan_inputs_optimistic, plan_inputs_optimistic_plan)
+from .reconditioned import reconditioned_rollout, reconditioned_rollout_vjp, plan_inputs_reconditioned  # noqa: F401
 from .terminal_set import (ContractionCheck, TerminalSet, contraction_rates, sample_terminal_jacobians, fit_terminal_set,  # noqa: F401
                            terminal_to_params)
 
@@ -42,4 +43,5 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "robust_tube_rollout_vjp_plan", "plan_inputs_robust", "plan_inputs_robust_plan", "pairwise_lipschitz",
            "estimate_lipschitz", "ContractionCheck", "TerminalSet", "contraction_rates", "sample_terminal_jacobians", "fit_terminal_set",
            "terminal_to_params", "OptimisticTube", "optimistic_rollout", "optimistic_rollout_plan", "optimistic_rollout_vjp",
-           "optimistic_rollout_vjp_plan", "plan_inputs_optimistic", "plan_inputs_optimistic_plan"]
+           "optimistic_rollout_vjp_plan", "plan_inputs_optimistic", "plan_inputs_optimistic_plan", "reconditioned_rollout",
+           "reconditioned_rollout_vjp", "plan_inputs_reconditioned"]

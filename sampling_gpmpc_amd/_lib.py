@@ -136,6 +136,9 @@ SYMBOLS = {
                                            _P, _P, _P, _P, _P]),
     "gpmpc_optimistic_rollout_vjp": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _I64, _I32, _P, _I32, _P, _I32, _P, _I32, _D,
                                                _P, _P, _P, _P, _P, _P, _P]),
+    "gpmpc_rollout_vjp_workspace_bytes": (_SZ, [C.POINTER(GpDesc), _I64, _I32]),
+    "gpmpc_rollout_vjp": (C.c_int, [C.POINTER(GpDesc), C.POINTER(EnvDesc), _P, _P, _D, _D, _I64, _I32, _P, _I32, _P, _P, _I64, _P, _P, _P, _P,
+                                    _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "gpmpc_pairwise_lipschitz_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32]),
     "gpmpc_pairwise_lipschitz": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _D, _P, _P, _P, _I32, _P, _SZ, _P]),
     "gpmpc_contraction_rates_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32]),

@@ -16,11 +16,11 @@ SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
            "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
            "pathwise_stats.hip", "pathwise_grad.hip", "pathwise_cand.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip",
-           "optimistic.hip"]
+           "optimistic.hip", "rollout_grad.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce
-HEADERS = ["gpmpc_device.hpp", "gpmpc_host.hpp", "rollout_args.hpp", "rollout_plan.hpp", "joint_args.hpp", "joint_eigh.hpp", "joint_plan.hpp", "hull_geom.hpp", "min_index.hpp", "base_stream.hpp", "moments_step.hpp", "pathwise_step.hpp", "robust_step.hpp", "contraction_math.hpp",
+HEADERS = ["gpmpc_device.hpp", "gpmpc_host.hpp", "rollout_args.hpp", "rollout_plan.hpp", "joint_args.hpp", "joint_eigh.hpp", "joint_plan.hpp", "hull_geom.hpp", "min_index.hpp", "base_stream.hpp", "moments_step.hpp", "pathwise_step.hpp", "robust_step.hpp", "contraction_math.hpp", "kern_grad.hpp",
            "rollout_one_gen.inc", "rollout_one_steps_gen.inc", "rollout_tiles_mfma.inc", "joint_mfma_gen.inc",
            os.path.join(REPO, "include", "gpmpc_hip.h")]
 GENERATED = {"rollout_one_gen.inc": os.path.join(REPO, "tools", "gen_rollout_one.py"),

@@ -97,7 +97,10 @@ def rollout_device(agent: Agent, u_ff, z: torch.Tensor, z_step_stride: int, *, H
     lo, hi = (0, agent.ns) if sample_slice is None else sample_slice
     Ns = hi - lo
     nx, g_ny, D = agent.nx, agent.g_ny, agent.in_dim_x
-    u_ff_d = torch.as_tensor(np.asarray(u_ff), dtype=F64).reshape(H, agent.nu).to(dev).contiguous()
+    if torch.is_tensor(u_ff) and u_ff.is_cuda:                  # already on a device: no host round trip
+        u_ff_d = u_ff.detach().to(device=dev, dtype=F64).reshape(H, agent.nu).contiguous()
+    else:
+        u_ff_d = torch.as_tensor(np.asarray(u_ff), dtype=F64).reshape(H, agent.nu).to(dev).contiguous()
     if x0 is None:
         x0_d = torch.as_tensor(np.asarray(p["env"]["start"], dtype=np.float64)[:nx]).to(dev).contiguous()
         per_sample = 0
