@@ -1340,6 +1340,69 @@ int     gpmpc_contraction_rates(int64_t Ns, int32_t H, int32_t nx, int32_t nu, i
                                 int64_t* argmax /* (C) */, int64_t* n_above /* (C) */, double* rates /* (C, N) or NULL */,
                                 uint32_t* info /* (C) */, int32_t max_blocks, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * gpmpc_ws_condition / gpmpc_ws_variance - weight-space GP samples that learn from measurements: a Bayesian linear regression over the
+ * random Fourier features of the pathwise samples, conditioned on a block of k new measurements.  The data enter only through the
+ * M x M posterior covariance of the feature weights, so the number of measurements a run may take is unbounded (the pathwise samples'
+ * correction lives on the real points: N_r <= 64), and every sample stays the same prior draw, re-conditioned.  Additive entry points:
+ * the ABI version stays 12.
+ * Replaces: the measure / re-train / re-sample loop of reference extra/approx_sampling_mpc (DEMPC.py:64-84 measures the plant at every
+ * MPC step, agent.py:270-273 online_learnt_datapoints appends it, agent.py:793-845 train_BLR_multioutput / sample_weights re-train the
+ * regression on ALL data and draw new weights before the next solve) by a rank-k update of the state shared by the samples and a
+ * recursive-least-squares correction of every sample's weight vector, O(M k) per sample.
+ *
+ * The model, all FP64, per output o < g_ny; M even, F = M / 2:
+ *   features     phi_o(xi)[2f] = c_o cos(omega_{o,f} . xi), phi_o(xi)[2f+1] = c_o sin(omega_{o,f} . xi), c_o = sqrt(outputscale_o / F):
+ *                the features and the scale of gpmpc_pathwise_eval, so f_i(xi) = phi_o(xi)^T w_{i,o} is what gpmpc_pathwise_eval returns
+ *                for the weights w in the feature columns of Z with V = 0 (to rounding: the scale is applied per feature here)
+ *   prior        w ~ N(0, I);  observation y = phi^T w + e, e ~ N(0, s2), s2 = gp->noise[0] (the reference's BLR with lambda_reg =
+ *                noise_var = s2)
+ *   state        mu [dev] (g_ny, M) and P [dev] (g_ny, M, M), in/out: mean and covariance of the weights given the data so far.  Plain
+ *                arrays the caller initialises (0 and I for no data).  P is read as a full matrix and must be symmetric.
+ *   samples      w_{i,o,j} at W[i*ldw + o*stride_output + j], in/out, each distributed N(mu_o, P_o); ldw = ldz and stride_output =
+ *                M + N_r address the feature columns of a pathwise Z buffer in place
+ * gpmpc_ws_condition conditions state and samples on X_new [dev] (k, D), Y_new [dev] (g_ny, k) with the per-sample noise normals
+ * E [dev] (Ns, g_ny, k):
+ *   Phi = phi_o(X_new) (k x M), T = P Phi^T, S = Phi T + s2 I = L L^T, U = L^-1 T^T (k x M), G = U^T L^-1
+ *   var_prior[o, j] = (Phi T)_jj = S_jj - s2   [dev] (g_ny, k) out or NULL: the variance of f at the new points BEFORE this update
+ *   mu <- mu + G (y_o - Phi mu);   w_i <- w_i + G (y_o + sqrt(s2) E_{i,o} - Phi w_i);   P <- P - U^T U
+ *   info_state [dev] (g_ny) int32 out: 0, GPMPC_INFO_NONFINITE or GPMPC_INFO_TRAIN_CHOL_FAIL;  info [dev] (Ns) int32 out: 0 or
+ *   GPMPC_INFO_NONFINITE.  omega [dev] (g_ny, F, D) as for gpmpc_pathwise_fit.  E, W and info may be NULL when Ns == 0 (the state alone).
+ *   workspace [dev], 32-byte aligned, workspace_bytes >= gpmpc_ws_condition_workspace_bytes(g_ny, M, k) (0 for sizes it rejects): Phi, T,
+ *   S, L, U and G of the call; every record that is read was written by the same call.
+ * gpmpc_ws_variance: var[o, p] = phi_o(x_p)^T P_o phi_o(x_p), x [dev] (m, D), var [dev] (g_ny, m) out - the posterior variance of f
+ * (without observation noise), the reference's get_posterior_uncertainity for this model.  A non-finite x_p or P gives a non-finite var.
+ * Non-finite and failure rule: an output o with a non-finite entry in X_new, in Y_new[o] or in its mu / P (or for which T or S
+ * overflows) carries GPMPC_INFO_NONFINITE, one whose S has a non-positive pivot GPMPC_INFO_TRAIN_CHOL_FAIL; NOTHING of such an output is
+ * changed: mu_o, P_o and the output's columns of every sample keep their bits (var_prior[o] is still written and may be NaN).  The flag
+ * is decided before anything is written.  A sample whose weights or E entries for an updated output are not finite (or whose residual
+ * overflows) gets NaN weights for that output and GPMPC_INFO_NONFINITE; no other sample and no other output of it is touched.
+ * Reproducibility: mu, P and var_prior depend on the state and the block alone - not on Ns, W or the grid.  A sample's new weights
+ * depend on its own row of W and E and on the shared state alone - not on Ns or on the sample's position.  So a sharded run, the state
+ * replicated and W sharded by global id, reproduces the single-GPU run bit for bit.  No atomics; every sum runs in an order fixed by
+ * (M, k).  P is written as lower 16 x 16 tiles and mirrored: exactly symmetric after every call.
+ * Limits (the contract): M a multiple of 128 and at most 1024; 1 <= k <= 64 per call (cut longer blocks: conditioning on blocks in
+ * sequence is conditioning on their union); Ns < 2^31; D <= GPMPC_MAX_D; g_ny <= GPMPC_MAX_NY.  GPMPC_E_UNSUPPORTED beyond, before any
+ * device work.  GPMPC_E_ARG (before any device work): NULL gp or a bad descriptor (g_ny, D out of range; noise[0] or an outputscale not
+ * finite and positive); M < 2 or odd; k < 1; Ns or m < 0; a negative ldw or stride_output, and with Ns > 0 stride_output < M or ldw <
+ * (g_ny - 1) stride_output + M; NULL omega, X_new, Y_new, mu, P or info_state, with Ns > 0 NULL W, E or info; variance with m > 0: NULL
+ * omega, P, x or var.  GPMPC_E_WORKSPACE: a NULL, misaligned or too small workspace.  m == 0: nothing is launched.  No plan and no X_r
+ * is read (N_r, T and the other noise slots of the descriptor are not used); no hidden allocation, no host round trip, everything goes
+ * to `stream`.
+ * Measured (MI355X, one run, Python wrapper included; profiles/weight_space_bench.md): car Ns 4096, M 512, g_ny 3: 0.24 / 0.25 / 0.54 ms
+ * per call at k = 1 / 16 / 64 (the same arithmetic in torch operations: 0.74 / 0.68 / 1.08 ms); pendulum1D Ns 1024, M 256: 0.10 / 0.12 /
+ * 0.28 ms (0.24 / 0.24 / 0.31 ms).  Not measured: per-kernel times, M = 1024, a VALU form of the sample update.
+ */
+size_t  gpmpc_ws_condition_workspace_bytes(int32_t g_ny, int32_t M, int32_t k);
+int     gpmpc_ws_condition(const gpmpc_gp_desc_t* gp, int32_t M, const double* omega /* (g_ny, F, D) */, int32_t k,
+                           const double* X_new /* (k, D) */, const double* Y_new /* (g_ny, k) */, double* mu /* (g_ny, M) in/out */,
+                           double* P /* (g_ny, M, M) in/out */, int64_t Ns, double* W, int64_t ldw, int64_t stride_output,
+                           const double* E /* (Ns, g_ny, k) */, double* var_prior /* (g_ny, k) or NULL */,
+                           int32_t* info_state /* (g_ny) */, int32_t* info /* (Ns) */, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int     gpmpc_ws_variance(const gpmpc_gp_desc_t* gp, int32_t M, const double* omega, const double* P /* (g_ny, M, M) */, int32_t m,
+                          const double* x /* (m, D) */, double* var /* (g_ny, m) */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

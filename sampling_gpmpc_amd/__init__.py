@@ -21,6 +21,7 @@ from .closed_loop import ClosedLoop, SurrogateSolver, CondensedSolver  # noqa: F
 from .pathwise import (PathwiseSamples, draw_omega, rff_kernel_error, TubeStats, pathwise_tube_stats, merge_tube_stats,  # noqa: F401
                        tube_stats_of, pathwise_rollout_vjp, sampled_tube_penalty, plan_inputs_sampled, pathwise_rollout_cand_vjp,
                        plan_inputs_sampled_population)
+from .weight_space import WeightSpaceSamples, learn_online  # noqa: F401
 from .robust_tube import (RobustTube, robust_tube_rollout, robust_tube_rollout_plan, pairwise_lipschitz, estimate_lipschitz,  # noqa: F401
                           robust_tube_rollout_vjp, robust_tube_rollout_vjp_plan, plan_inputs_robust, plan_inputs_robust_plan)
 from .optimistic import (OptimisticTube, optimistic_rollout, optimistic_rollout_plan, optimistic_rollout_vjp,  # noqa: F401
@@ -44,4 +45,4 @@ __all__ = ["Agent", "make_env", "Pendulum", "CarKinematicsModel", "get_reachable
            "estimate_lipschitz", "ContractionCheck", "TerminalSet", "contraction_rates", "sample_terminal_jacobians", "fit_terminal_set",
            "terminal_to_params", "OptimisticTube", "optimistic_rollout", "optimistic_rollout_plan", "optimistic_rollout_vjp",
            "optimistic_rollout_vjp_plan", "plan_inputs_optimistic", "plan_inputs_optimistic_plan", "reconditioned_rollout",
-           "reconditioned_rollout_vjp", "plan_inputs_reconditioned"]
+           "reconditioned_rollout_vjp", "plan_inputs_reconditioned", "WeightSpaceSamples", "learn_online"]

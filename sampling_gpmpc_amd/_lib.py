@@ -143,6 +143,9 @@ SYMBOLS = {
     "gpmpc_pairwise_lipschitz": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _D, _P, _P, _P, _I32, _P, _SZ, _P]),
     "gpmpc_contraction_rates_workspace_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I32, _I32]),
     "gpmpc_contraction_rates": (C.c_int, [_I64, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
+    "gpmpc_ws_condition_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "gpmpc_ws_condition": (C.c_int, [C.POINTER(GpDesc), _I32, _P, _I32, _P, _P, _P, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _SZ, _P]),
+    "gpmpc_ws_variance": (C.c_int, [C.POINTER(GpDesc), _I32, _P, _P, _I32, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

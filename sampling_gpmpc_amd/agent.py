@@ -427,6 +427,27 @@ class Agent(object):
         self._pathwise = PathwiseSamples.draw(self, self.ns, int(n_features), int(seed), offset=(self.shard[0] if self.shard else 0))
         return self._pathwise
 
+    def use_weight_space_samples(self, n_features, seed=0):
+        """Opt in to weight-space samples that learn online (``sampling_gpmpc_amd.weight_space``): the hook of
+        ``use_pathwise_samples`` - ``get_batch_gp_sensitivities`` evaluates ``self.ns`` fixed sample functions, a sharded Agent draws
+        its shard by global sample id - with samples that ``online_learnt_datapoints`` re-conditions on measurements.
+        ``use_weight_space_samples(None)`` restores the joint draw."""
+        if n_features is None:
+            self._pathwise = None
+            return None
+        from .weight_space import WeightSpaceSamples
+        self._pathwise = WeightSpaceSamples.draw(self, self.ns, int(n_features), int(seed), offset=(self.shard[0] if self.shard else 0))
+        return self._pathwise
+
+    def online_learnt_datapoints(self, X, Y):
+        """The reference's ``src/agent.py:270-273`` for the weight-space samples: condition the active samples on the measurements
+        ``X (k, D)``, ``Y (g_ny, k)`` and return the posterior variance at each point before its block.  The Agent's real data, plan,
+        factor cache, joint draw and mode R are not touched; without active weight-space samples this is an error."""
+        from .weight_space import WeightSpaceSamples
+        if not isinstance(self._pathwise, WeightSpaceSamples):
+            raise RuntimeError("online_learnt_datapoints needs the weight-space samples: call use_weight_space_samples(n_features) first")
+        return self._pathwise.condition(X, Y)
+
     def _pathwise_sensitivities(self, g_in, pinned):
         """``get_batch_gp_sensitivities`` with the pathwise samples: value + gradient of every sample function at ``g_in``; the pinned
         leading samples are overwritten as on the joint path (the mean is the ``Z = 0`` sample function)."""

@@ -16,7 +16,7 @@ SOURCES = ["capi.hip", "rollout.hip", "rollout_fast.hip", "rollout_tiles.hip", "
            "joint_mfma.hip", "joint_chol.hip", "assemble.hip", "base_samples.hip", "hull.hip",
            "hull_query.hip", "sup_dev.hip", "mll.hip", "moments.hip", "moments_grad.hip", "tube_qp.hip", "tube_rows.hip", "pathwise.hip",
            "pathwise_stats.hip", "pathwise_grad.hip", "pathwise_cand.hip", "robust_tube.hip", "robust_tube_grad.hip", "lipschitz.hip", "contraction.hip",
-           "optimistic.hip", "rollout_grad.hip"]
+           "optimistic.hip", "rollout_grad.hip", "weight_space.hip"]
 # everything a source may include: the generated statement files (.inc) count like headers - editing a generator's OUTPUT
 # rebuilds the kernels that include it; tests/test_generated_sources.py checks that the committed .inc files are what the
 # generators (tools/gen_rollout_one.py, tools/gen_mfma_chains.py) produce
